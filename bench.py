@@ -2,9 +2,15 @@
 """bench.py -- frames/sec of the watermark embed -> JPEG -> decode GAN training step (BASELINE.json
 metric) on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the JSON line (`ms_per_step`: wall clock of the K timed steps / K,
+`value`: frames/s of the same region); --dump-outputs DIR then writes what the last timed step returned to its caller -- the seven
+logged losses and (encoded, noised, decoded) of Hidden.train_on_batch -- as DIR/<name>.npy (25 MB at the default size; dump_outputs).
+Weights and inputs are seeded, so two runs with the same arguments see the same inputs.  Everything else the line can carry (kernel
+events and rooflines, the reference-state and 512 x 512 regions, the CPU baseline, per-step event times) is measured with --full only.
 
 Workload (config.workload): BASELINE.json configs[1] -- 256x256, batch 16 PER GPU (weak scaling),
 HiDDeN order (hidden_models/hidden.py:54-118): D(cover) fwd/bwd, encoder -> Jpeg(50) -> decoder,
@@ -18,15 +24,16 @@ gradients into the DISCRIMINATOR's parameters, which no optimiser step uses and 
 (Hidden(keep_dead_discriminator_grads=False): 2 x 4.832 + 0.226 GFLOP per 256x256 frame); (2) round 4 -- Jpeg(Q) quantises with torch.round,
 whose gradient is identically zero (noise_layers/jpeg.py:226-240), so the decoder's gradient wrt its input is multiplied by zero
 (Hidden.skip_zero_attack_gradient: 0.226 GFLOP).  Every loss, output and parameter update is identical (tests/test_gpu_configs.py,
-tests/test_gpu_graph.py).  The SAME invocation times the step with every launch of the reference's autograd (`reference_state`, 249.0 GFLOP
-per frame) and the 512 x 512 / 8-frame shard of BASELINE's C4 (`c4_shard_512`); --keep-dead-grads makes the former the headline.
+tests/test_gpu_graph.py).  With --full the SAME invocation also times the step with every launch of the reference's autograd
+(`reference_state`, 249.0 GFLOP per frame) and the 512 x 512 / 8-frame shard of BASELINE's C4 (`c4_shard_512`); --keep-dead-grads makes
+the former the headline.
 
 Round 4, one GPU: the step runs as its two independent chains on two streams (Hidden.two_streams) and is replayed from a hipGraph
-(Hidden.enable_graph) -- bit-identical to the eager one-stream step; --one-stream / --no-graph switch either off.  The steps whose kernels
-are bracketed with events (the last of every --kernel-events-every) run on one stream, eagerly, so that an event pair times the kernel
-alone.  With a gradient all-reduce (N > 1) the step runs eagerly on one stream as in round 3.
+(Hidden.enable_graph) -- bit-identical to the eager one-stream step; --one-stream / --no-graph switch either off.  With --full, the steps
+whose kernels are bracketed with events (the last of every --kernel-events-every) run on one stream, eagerly, so that an event pair times
+the kernel alone.  With a gradient all-reduce (N > 1) the step runs eagerly on one stream as in round 3.
 
-The JSON line carries, besides the driver contract:
+With --full the JSON line also carries:
   roofline     -- the dominant kernel (most time per step, 13 launches): bwd_ws8_kernel (csrc/bwd_ws8.hip; csrc/bwd_ws.hip for shapes that
                   are not whole 8x16 tiles) = the whole backward of a 64->64 body layer in one pass: input gradient with the BatchNorm-backward apply fused, the feeding layer's
                   BatchNorm sums, and the weight gradient, from one staged dy / activation tile.  Its 154.6 GFLOP ride on 4 tensor
@@ -67,9 +74,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=16, help="frames per GPU")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--noise", default="Jpeg50")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: kernel events and rooflines inside the timed region, per-step "
+                         "event times, the reference_state and c4_shard_512 regions, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (losses, encoded, noised, decoded) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--kernel-events-every", type=int, default=20,
-                    help="the roofline kernels are bracketed with HIP events on every n-th timed step only: an event pair idles the GPU for ~11 us "
+                    help="(--full) the roofline kernels are bracketed with HIP events on every n-th timed step only: an event pair idles the GPU for ~11 us "
                          "around the launch it brackets (28 bracketed launches = 0.31 ms of a 5.5 ms step when every step is instrumented)")
     ap.add_argument("--keep-dead-grads", action="store_true", help="also compute the discriminator weight gradients of the generator pass (the reference's state; nothing reads them)")
     ap.add_argument("--graph", dest="graph", action="store_true", default=None,
@@ -79,11 +91,14 @@ def parse():
     ap.add_argument("--two-streams", dest="two_streams", action="store_true", default=None,
                     help="the step's two independent chains (discriminator passes | encoder -> attack -> decoder) on two streams (Hidden.two_streams)")
     ap.add_argument("--one-stream", dest="two_streams", action="store_false")
-    ap.add_argument("--no-extra", action="store_true", help="skip the two secondary timed regions (reference_state, c4_shard_512)")
-    ap.add_argument("--extra-steps", type=int, default=25, help="timed steps of each secondary region (after 5 warm-up steps)")
-    ap.add_argument("--cpu-frames", type=int, default=16, help="frames per step of the bounded CPU-baseline sample")
-    ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-baseline steps (median reported) after one warm-up step")
-    return ap.parse_args()
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the two secondary timed regions (reference_state, c4_shard_512)")
+    ap.add_argument("--extra-steps", type=int, default=25, help="(--full) timed steps of each secondary region (after 5 warm-up steps)")
+    ap.add_argument("--cpu-frames", type=int, default=16, help="(--full) frames per step of the bounded CPU-baseline sample")
+    ap.add_argument("--cpu-steps", type=int, default=3, help="(--full) timed CPU-baseline steps (median reported) after one warm-up step")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _physical_cores():
@@ -125,8 +140,9 @@ def cpu_baseline(size, frames, steps=3):
     except (AttributeError, OSError):
         usable = logical
     # torch's CPU convolution stops scaling past a few dozen threads (256 threads measured 20x slower than 32 on the
-    # GPU box's host), so the baseline runs on min(32, usable) threads and says so
-    cores = min(32, usable)
+    # GPU box's host), so the baseline runs on min(32, usable) threads and says so -- fewer when OMP_NUM_THREADS grants this process fewer
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    cores = min(32, usable, int(omp) if omp.isdigit() and int(omp) > 0 else 32)
     torch.set_num_threads(cores)
     torch.manual_seed(10)
     cfg = hidden_ref.HiDDenConfiguration(H=size, W=size)
@@ -220,6 +236,26 @@ def file_sha16(path):
         return hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]
     except OSError:
         return None
+
+
+DUMP_BUDGET = 64 << 20   # bytes of .npy data --dump-outputs may write
+
+
+def dump_outputs(path, losses, outs):
+    """what Hidden.train_on_batch returned for the last timed step, as its caller receives it: the seven logged losses
+    (DIR/loss_<key>.npy, float64 [1]) and encoded / noised / decoded (DIR/<name>.npy, float32, full shape).  Outputs that would take the
+    files past DUMP_BUDGET are replaced by a fixed sample: the same seeded flat indices for the same shape, sorted, as a 1-D array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss_" + k.strip(): np.array([losses[k]], dtype=np.float64) for k in losses if not k.startswith("_")}
+    arrays.update((name, t.detach().float().cpu().numpy()) for name, t in zip(("encoded", "noised", "decoded"), outs))
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET and a.size > 4096:
+            keep = int(a.size * DUMP_BUDGET / total * 0.95)
+            idx = np.unique(np.random.default_rng(10).integers(0, a.size, keep))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def timed_steps(h, batch, steps, warmup, barrier, world, dev, timer=None, every=5):
@@ -324,9 +360,10 @@ def main():
     Q = int("".join(c for c in args.noise if c.isdigit()) or 50)
     noise = {"Jpeg": NL.Jpeg, "JpegSS": NL.JpegSS, "JpegMask": NL.JpegMask}[kind](Q) if kind != "Identity" else NL.Identity()
 
+    full = args.full
     torch.manual_seed(10)  # identical initial weights on every rank (plus the DDP-style broadcast below)
     cfg = HiDDenConfiguration(H=S, W=S)
-    sync = GradSync(profile=True) if world > 1 else None
+    sync = GradSync(profile=full) if world > 1 else None
     h = Hidden(cfg, dev, noise, None, compute_dtype=dtype, grad_sync=sync, keep_dead_discriminator_grads=args.keep_dead_grads)
     h.skip_zero_attack_gradient = not args.keep_dead_grads
     broadcast_parameters([h.encoder_decoder.encoder, h.encoder_decoder.decoder, h.discriminator])
@@ -348,8 +385,8 @@ def main():
     for w in range(args.warmup):
         # the first warm-up step takes the path of the timed region's bracketed steps (one stream, eagerly, kernel events on): its buffers come
         # from the main stream's pool, which the replayed / two-chain steps never touch -- left cold, the first bracketed step of the timed
-        # region pays the allocator's hipMallocs (~10 ms, once)
-        bracket = w == 0 and (use_graph or two_streams)
+        # region pays the allocator's hipMallocs (~10 ms, once).  Without --full no step is bracketed
+        bracket = full and w == 0 and (use_graph or two_streams)
         if bracket:
             ops.set_kernel_timer(ops.KernelTimer(lambda name, i: name in ("conv3x3_bwd_fused", "conv3x3_fwd", "jpeg_fwd", "jpeg_bwd")))
             h.two_streams = False
@@ -364,7 +401,7 @@ def main():
     timer = ops.KernelTimer(lambda name, i: (name == "conv3x3_bwd_fused" and not i["gvec"]) or
                             (name == "conv3x3_fwd" and i["Cin"] == 64 and i["CoutP"] == 64 and i["xform"]) or
                             name in ("jpeg_fwd", "jpeg_bwd"))
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # per-step events on the launch stream (§8d: median)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if full else None   # per-step events on the launch stream (§8d: median)
     every = max(1, args.kernel_events_every)
     barrier()
     t0 = time.perf_counter()
@@ -375,18 +412,20 @@ def main():
         # roofline kernels are bracketed on every `every`-th timed step, all their launches of that step.
         # (the LAST step of every `every`, not the first: the first steps behind the barrier + synchronize run on a chip whose clock is still
         # ramping up, and an eagerly enqueued step there also starts from an empty queue -- 6.2 ms instead of 5.5)
-        bracket = (i + 1) % every == 0 or (args.steps < every and i == args.steps - 1)
+        bracket = full and ((i + 1) % every == 0 or (args.steps < every and i == args.steps - 1))
         ops.set_kernel_timer(timer if bracket else None)
         # a bracketed step runs its launches ONE AFTER THE OTHER (one stream, eagerly): beside a launch of the other chain a kernel's event
         # pair would time the sharing of the chip, not the kernel (178 us instead of 149 for the dominant one)
         h.two_streams = two_streams and not bracket
         if sync is not None:
             sync.profile = bracket    # (the same for the events around the gradient all-reduces' waits)
-        marks[i].record()
+        if full:
+            marks[i].record()
         th = time.perf_counter()
-        losses, _ = h.train_on_batch([images, messages])
+        losses, outs = h.train_on_batch([images, messages])
         (host_ms_eager if (use_graph and bracket) else host_ms).append(1e3 * (time.perf_counter() - th))
-    marks[args.steps].record()
+    if full:
+        marks[args.steps].record()
     host_ms.sort(); host_ms_eager.sort()
     if not host_ms:
         host_ms = host_ms_eager
@@ -394,15 +433,58 @@ def main():
     dt = time.perf_counter() - t0
     ops.set_kernel_timer(None)
     h.two_streams = two_streams
+    if args.dump_outputs and rank == 0:
+        # before anything else runs the model: a replayed step returns its graph's own tensors, which the next replay overwrites
+        dump_outputs(args.dump_outputs, losses, outs)
+    if world > 1:
+        t = torch.tensor([dt], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    peak = 2500.0 if dtype == torch.bfloat16 else 157.3
+    # FLOPs per frame as executed: the reference autograd's 249.0 GFLOP at 256x256 minus, unless --keep-dead-grads, the
+    # two 64->64 and the 3->64 discriminator weight-gradient GEMMs of the generator pass (2 x 4.832 + 0.226 GFLOP)
+    step_gflop = step_gflop_per_frame(args, S)
+    out = {
+        "metric": f"frames/sec training step (embed->JPEG->decode), {S}x{S}",
+        "value": world * B * args.steps / dt, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": f"C2: HiDDeN GAN step enc(4x64)->{args.noise}->dec(7x64)+disc(3x64), L=30, {S}x{S}, batch {B}/GPU"
+                               + ("" if args.keep_dead_grads else "; not launched (results identical): the generator pass's dead discriminator weight gradients"
+                                  + (", the decoder's input gradient that Jpeg's zero-gradient rounding multiplies by 0" if zero_attack(args) else "")
+                                  + " -- reference_state (--full) times the step with them"),
+                   "global_batch": world * B, "parallelism": f"dp{world}"},
+        "graph": use_graph and not graph_failures(h), "graph_capture_failed": graph_failures(h) or None, "two_streams": bool(two_streams),
+        "step_gflop_per_frame": step_gflop,
+        "step_flops_frac_of_peak": (step_gflop * 1e9 * world * B * args.steps / dt) / (peak * 1e12 * world),
+        "kernel_sources_sha": kernel_sources_sha(), "library": os.path.relpath(_wm_lib.loaded_path(), ROOT), "library_sha16": file_sha16(_wm_lib.loaded_path()),
+        "last_losses": {k.strip(): v for k, v in losses.items()},
+        "full": full,
+    }
+    if full:
+        out.update(full_measurements(args, h, images, messages, timer, marks, host_ms, host_ms_eager, dt, sync, barrier, world, rank, dev,
+                                     noise, use_graph, two_streams, every))
+    if rank == 0:
+        print(json.dumps(out))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_measurements(args, h, images, messages, timer, marks, host_ms, host_ms_eager, dt, sync, barrier, world, rank, dev,
+                      noise, use_graph, two_streams, every):
+    """--full: the keys of the line beyond the headline -- the kernel events and rooflines of the timed region's bracketed steps, the
+    per-step event times, the reference_state and c4_shard_512 regions, the CPU baseline (rank 0 returns them; the other ranks {})"""
+    from video_watermarking_forgery_detection_amd import ops
+    from video_watermarking_forgery_detection_amd.distributed import broadcast_parameters
+    from video_watermarking_forgery_detection_amd.hidden_models import Hidden
+    from video_watermarking_forgery_detection_amd.options import HiDDenConfiguration
+    S, B = args.size, args.batch
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     sync_rep = sync.report(max(1, args.steps // every)) if sync is not None else None
     if sync_rep is not None:   # every rank: its buckets and how long its compute stream stood waiting for them (the exposed part of the all-reduces)
         sys.stderr.write(f"[bench rank {rank}] grad sync: {json.dumps(sync_rep)}\n")
     step_ms_order = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     step_ms = sorted(step_ms_order)
-    if world > 1:
-        t = torch.tensor([dt], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
     kms = timer.elapsed_ms("conv3x3_fwd")
     dms = timer.elapsed_ms("conv3x3_bwd_fused")
     # ---- two more timed regions of the SAME invocation (secondary keys of the line; north_star asks for 256x256 AND 512x512, and the headline
@@ -453,69 +535,50 @@ def main():
         del h2, im2, ms2
     if sync is not None:
         sync.report()
-    if rank == 0:
-        fps = world * B * args.steps / dt
-        esz = 2 if dtype == torch.bfloat16 else 4
-        tensor_bytes = float(B * S * S * 64 * esz)
-        flops_per_launch = 2.0 * B * S * S * 64 * 9 * 64
-        avg_ms = sum(kms) / max(1, len(kms))
-        achieved = flops_per_launch / (avg_ms * 1e-3) / 1e12
-        peak = 2500.0 if dtype == torch.bfloat16 else 157.3
-        mfma = {"bound": "mfma",
-                "kernel": ("conv3x3_ws_kernel<64,64,XFORM,STATS,M16>" if dtype == torch.bfloat16 else "conv3x3_kernel<float,64,true>") + " (forward 64->64 implicit GEMM, fused BN+ReLU input, BN statistics)",
-                "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                "traffic": pmc_traffic(args, S, B, "fwd_hbm_bytes_per_launch"), "mfma_util_pmc": pmc_traffic(args, S, B, "fwd.mfma_util"),
-                "launches_timed": len(kms), "avg_launch_ms": avg_ms,
-                "flops_per_launch": flops_per_launch, "hbm_algorithmic_bytes_per_launch": 2.0 * tensor_bytes}
-        # FLOPs per frame as executed: the reference autograd's 249.0 GFLOP at 256x256 minus, unless --keep-dead-grads, the
-        # two 64->64 and the 3->64 discriminator weight-gradient GEMMs of the generator pass (2 x 4.832 + 0.226 GFLOP)
-        step_gflop = step_gflop_per_frame(args, S)
-        if dms:   # bf16: the one-pass backward kernel is the dominant one; 288 FLOP/B sits just under the ridge: HBM-bound
-            davg = sum(dms) / len(dms)
-            dbytes = 4.0 * tensor_bytes   # reads g, y, y of the layer below; writes dx
-            dflops = 2.0 * flops_per_launch   # the input gradient and the weight gradient
-            roof = {"bound": "hbm",
-                    "kernel": "bwd_ws8_kernel (64->64 body layer, one pass: input gradient + BatchNorm-backward apply + the feeding layer's BatchNorm sums + weight gradient; the two GEMMs on different waves)",
-                    "achieved": dbytes / (davg * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s", "frac": dbytes / (davg * 1e-3) / 1e9 / 8000.0,
-                    "traffic": pmc_traffic(args, S, B), "mfma_util_pmc": pmc_traffic(args, S, B, "bwd_fused.mfma_util"),
-                    "launches_timed": len(dms), "avg_launch_ms": davg,
-                    "algorithmic_bytes_per_launch": dbytes, "flops_per_launch": dflops,
-                    "flops_frac_of_mfma_peak": dflops / (davg * 1e-3) / 1e12 / peak}
-        else:
-            roof = mfma
-        out = {
-            "metric": f"frames/sec training step (embed->JPEG->decode), {S}x{S}",
-            "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"C2: HiDDeN GAN step enc(4x64)->{args.noise}->dec(7x64)+disc(3x64), L=30, {S}x{S}, batch {B}/GPU"
-                                   + ("" if args.keep_dead_grads else "; not launched (results identical): the generator pass's dead discriminator weight gradients"
-                                      + (", the decoder's input gradient that Jpeg's zero-gradient rounding multiplies by 0" if zero_attack(args) else "")
-                                      + " -- reference_state times the step with them"),
-                       "global_batch": world * B, "parallelism": f"dp{world}"},
-            "ms_per_step_median_events": step_ms[len(step_ms) // 2], "ms_per_step_min_events": step_ms[0], "ms_per_step_max_events": step_ms[-1],
-            "graph": use_graph and not graph_failures(h), "graph_capture_failed": graph_failures(h) or None, "two_streams": bool(two_streams),
-            "kernel_events_note": "the steps whose kernels are bracketed with events run on one stream, eagerly (every kernel alone on the chip): avg_launch_ms is the kernel's own duration; the other steps run as two chains" + (" replayed from a hipGraph" if use_graph else "") if two_streams or use_graph else None,
-            "host_enqueue_ms_median": host_ms[len(host_ms) // 2], "host_enqueue_ms_max": host_ms[-1],
-            "host_enqueue_ms_median_eager_steps": host_ms_eager[len(host_ms_eager) // 2] if host_ms_eager else None,
-            "kernel_events_every": every, "ms_per_step_events": [round(v, 3) for v in step_ms_order],
-            "roofline": roof,
-            "roofline_mfma": mfma,
-            "roofline_attack": attack_roofline(timer, B, S, args.noise),
-            "step_mfma_util_pmc": pmc_traffic(args, S, B, "step_mfma_util"),
-            "step_gflop_per_frame": step_gflop,
-            "step_flops_frac_of_peak": (step_gflop * 1e9 * world * B * args.steps / dt) / (peak * 1e12 * world),
-            "pmc_stale": bool(_pmc.get("stale", True)),
-            "kernel_sources_sha": kernel_sources_sha(), "library": os.path.relpath(_wm_lib.loaded_path(), ROOT), "library_sha16": file_sha16(_wm_lib.loaded_path()),
-            "grad_sync": sync_rep,
-            "last_losses": {k.strip(): v for k, v in losses.items()},
-        }
-        out.update(extra)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(S, args.cpu_frames, args.cpu_steps)
-        print(json.dumps(out))
-    if world > 1:
-        dist.destroy_process_group()
+    if rank != 0:
+        return {}
+    esz = 2 if dtype == torch.bfloat16 else 4
+    tensor_bytes = float(B * S * S * 64 * esz)
+    flops_per_launch = 2.0 * B * S * S * 64 * 9 * 64
+    avg_ms = sum(kms) / max(1, len(kms))
+    achieved = flops_per_launch / (avg_ms * 1e-3) / 1e12
+    peak = 2500.0 if dtype == torch.bfloat16 else 157.3
+    mfma = {"bound": "mfma",
+            "kernel": ("conv3x3_ws_kernel<64,64,XFORM,STATS,M16>" if dtype == torch.bfloat16 else "conv3x3_kernel<float,64,true>") + " (forward 64->64 implicit GEMM, fused BN+ReLU input, BN statistics)",
+            "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+            "traffic": pmc_traffic(args, S, B, "fwd_hbm_bytes_per_launch"), "mfma_util_pmc": pmc_traffic(args, S, B, "fwd.mfma_util"),
+            "launches_timed": len(kms), "avg_launch_ms": avg_ms,
+            "flops_per_launch": flops_per_launch, "hbm_algorithmic_bytes_per_launch": 2.0 * tensor_bytes}
+    if dms:   # bf16: the one-pass backward kernel is the dominant one; 288 FLOP/B sits just under the ridge: HBM-bound
+        davg = sum(dms) / len(dms)
+        dbytes = 4.0 * tensor_bytes   # reads g, y, y of the layer below; writes dx
+        dflops = 2.0 * flops_per_launch   # the input gradient and the weight gradient
+        roof = {"bound": "hbm",
+                "kernel": "bwd_ws8_kernel (64->64 body layer, one pass: input gradient + BatchNorm-backward apply + the feeding layer's BatchNorm sums + weight gradient; the two GEMMs on different waves)",
+                "achieved": dbytes / (davg * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s", "frac": dbytes / (davg * 1e-3) / 1e9 / 8000.0,
+                "traffic": pmc_traffic(args, S, B), "mfma_util_pmc": pmc_traffic(args, S, B, "bwd_fused.mfma_util"),
+                "launches_timed": len(dms), "avg_launch_ms": davg,
+                "algorithmic_bytes_per_launch": dbytes, "flops_per_launch": dflops,
+                "flops_frac_of_mfma_peak": dflops / (davg * 1e-3) / 1e12 / peak}
+    else:
+        roof = mfma
+    out = {
+        "ms_per_step_median_events": step_ms[len(step_ms) // 2], "ms_per_step_min_events": step_ms[0], "ms_per_step_max_events": step_ms[-1],
+        "kernel_events_note": "the steps whose kernels are bracketed with events run on one stream, eagerly (every kernel alone on the chip): avg_launch_ms is the kernel's own duration; the other steps run as two chains" + (" replayed from a hipGraph" if use_graph else "") if two_streams or use_graph else None,
+        "host_enqueue_ms_median": host_ms[len(host_ms) // 2], "host_enqueue_ms_max": host_ms[-1],
+        "host_enqueue_ms_median_eager_steps": host_ms_eager[len(host_ms_eager) // 2] if host_ms_eager else None,
+        "kernel_events_every": every, "ms_per_step_events": [round(v, 3) for v in step_ms_order],
+        "roofline": roof,
+        "roofline_mfma": mfma,
+        "roofline_attack": attack_roofline(timer, B, S, args.noise),
+        "step_mfma_util_pmc": pmc_traffic(args, S, B, "step_mfma_util"),
+        "pmc_stale": bool(_pmc.get("stale", True)),
+        "grad_sync": sync_rep,
+    }
+    out.update(extra)
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(S, args.cpu_frames, args.cpu_steps)
+    return out
 
 
 if __name__ == "__main__":

@@ -6,6 +6,6 @@
 ROUNDS=${AB_ROUNDS:-3}
 for r in $(seq 1 $ROUNDS); do
   for v in "$@"; do
-    WM_LIB_VARIANT=$v python bench.py --no-cpu-baseline --no-extra ${AB_ARGS} 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', round(d['ms_per_step'],4), round(d['ms_per_step_median_events'],4), round(d['roofline']['avg_launch_ms']*1000,1), round(d['roofline_mfma']['avg_launch_ms']*1000,1))"
+    WM_LIB_VARIANT=$v python bench.py --full --no-cpu-baseline --no-extra ${AB_ARGS} 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', round(d['ms_per_step'],4), round(d['ms_per_step_median_events'],4), round(d['roofline']['avg_launch_ms']*1000,1), round(d['roofline_mfma']['avg_launch_ms']*1000,1))"
   done
 done

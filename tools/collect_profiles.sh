@@ -11,7 +11,7 @@ PART=${1:-a}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 set -e
-ONE="--no-cpu-baseline --no-extra --one-stream --no-graph"
+ONE="--full --no-cpu-baseline --no-extra --one-stream --no-graph"
 if [ "$PART" = "a" ]; then
 # Round 4: bench.py's default runs the step as two chains on two streams, replayed from a hipGraph: beside a launch of the other chain a
 # kernel's traced duration includes the time it shares the chip.  The per-kernel numbers (durations, counters) are therefore taken from
@@ -19,7 +19,7 @@ if [ "$PART" = "a" ]; then
 # brackets time); the default mode's trace is kept beside it ("stats2").  --no-extra: the headline workload only (no 512 x 512 / keep-dead region).
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python3 $ROOT/bench.py $ONE --steps 10 --warmup 3 > $OUT/stats.log 2>&1
 echo "stats done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats2 -o s2 -- python3 $ROOT/bench.py --no-cpu-baseline --no-extra --steps 10 --warmup 3 > $OUT/stats2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats2 -o s2 -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-extra --steps 10 --warmup 3 > $OUT/stats2.log 2>&1
 echo "stats (two chains + graph) done"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o f -- python3 $ROOT/bench.py $ONE --steps 3 --warmup 1 > $OUT/pmc_fetch.log 2>&1
 echo "fetch done"
@@ -34,12 +34,12 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/att_fetch -o af -- python
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/att_write -o aw -- python3 $ROOT/tools/attack_bench.py 5 > $OUT/att_write.log 2>&1
 python3 $ROOT/tools/attack_bench.py 50 > $OUT/attack_bench.json 2> $OUT/attack_bench.err
 echo "attacks done"
-python3 $ROOT/bench.py --no-cpu-baseline --no-extra --size 512 --batch 8 2> $OUT/b512.err | tail -1 > $OUT/bench_512_b8.json
-python3 $ROOT/bench.py --no-cpu-baseline --no-extra --keep-dead-grads 2> /dev/null | tail -1 > $OUT/bench_c2_keep_dead_grads.json
-python3 $ROOT/bench.py --no-cpu-baseline 2> /dev/null | tail -1 > $OUT/bench_c2.json
+python3 $ROOT/bench.py --full --no-cpu-baseline --no-extra --size 512 --batch 8 2> $OUT/b512.err | tail -1 > $OUT/bench_512_b8.json
+python3 $ROOT/bench.py --full --no-cpu-baseline --no-extra --keep-dead-grads 2> /dev/null | tail -1 > $OUT/bench_c2_keep_dead_grads.json
+python3 $ROOT/bench.py --full --no-cpu-baseline 2> /dev/null | tail -1 > $OUT/bench_c2.json
 # the step's four modes, interleaved, two rounds (one GPU): one stream / two chains x enqueued / replayed
 (for r in 1 2; do for m in "--one-stream --no-graph" "--two-streams --no-graph" "--two-streams --graph" "--one-stream --graph"; do
-  python3 $ROOT/bench.py --no-cpu-baseline --no-extra $m 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$m: ms_per_step', round(d['ms_per_step'],4), 'median of the step events', round(d['ms_per_step_median_events'],4), 'min', round(d['ms_per_step_min_events'],4), 'host enqueue ms', round(d['host_enqueue_ms_median'],3), 'bwd_ws8 us', round(d['roofline']['avg_launch_ms']*1000,1), 'fwd 64->64 us', round(d['roofline_mfma']['avg_launch_ms']*1000,1))"
+  python3 $ROOT/bench.py --full --no-cpu-baseline --no-extra $m 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$m: ms_per_step', round(d['ms_per_step'],4), 'median of the step events', round(d['ms_per_step_median_events'],4), 'min', round(d['ms_per_step_min_events'],4), 'host enqueue ms', round(d['host_enqueue_ms_median'],3), 'bwd_ws8 us', round(d['roofline']['avg_launch_ms']*1000,1), 'fwd 64->64 us', round(d['roofline_mfma']['avg_launch_ms']*1000,1))"
 done; done) > $OUT/step_modes.txt 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s512_stats -o q -- python3 $ROOT/bench.py $ONE --size 512 --batch 8 --steps 10 --warmup 3 > $OUT/s512_stats.log 2>&1
 echo "part a done"

@@ -52,9 +52,9 @@ def traffic_tables(fetch_sub, write_sub, base):
     return out
 
 
-avg_ns = stats_summary("stats", f"{tag}_bench_c2_kernel_stats", 13.0, "python3 bench.py --no-cpu-baseline --no-extra --one-stream --no-graph --steps 10 --warmup 3   (the step's launches one after the other: every kernel alone on the chip)")
+avg_ns = stats_summary("stats", f"{tag}_bench_c2_kernel_stats", 13.0, "python3 bench.py --full --no-cpu-baseline --no-extra --one-stream --no-graph --steps 10 --warmup 3   (the step's launches one after the other: every kernel alone on the chip)")
 try:
-    stats_summary("stats2", f"{tag}_bench_c2_two_chains_graph_kernel_stats", 13.0, "python3 bench.py --no-cpu-baseline --no-extra --steps 10 --warmup 3   (bench.py's default: two chains on two streams, replayed from a hipGraph -- a kernel's duration here includes the time it shares the chip with a launch of the other chain)")
+    stats_summary("stats2", f"{tag}_bench_c2_two_chains_graph_kernel_stats", 13.0, "python3 bench.py --full --no-cpu-baseline --no-extra --steps 10 --warmup 3   (bench.py's default mode: two chains on two streams, replayed from a hipGraph -- a kernel's duration here includes the time it shares the chip with a launch of the other chain)")
     os.remove(os.path.join(dst, f"{tag}_bench_c2_two_chains_graph_kernel_stats.csv"))
 except (ValueError, IndexError, OSError) as e:
     print("missing: stats2", e)
@@ -75,7 +75,7 @@ for k, v in m.items():
 rows.sort(reverse=True)
 step_util = tot_busy / (tot_act / NXCD * NCU * NSIMD)
 with open(os.path.join(dst, f"{tag}_bench_c2_pmc_mfma.csv"), "w") as g:
-    g.write("# rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -- python3 bench.py --no-cpu-baseline --no-extra --one-stream --no-graph --steps 3 --warmup 1\n")
+    g.write("# rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -- python3 bench.py --full --no-cpu-baseline --no-extra --one-stream --no-graph --steps 3 --warmup 1\n")
     g.write(f"# whole run (every kernel of 4 training steps): MFMA utilisation {step_util:.4f}\n")
     g.write("kernel,dispatches,mean_SQ_VALU_MFMA_BUSY_CYCLES,mean_GRBM_GUI_ACTIVE,mfma_util\n")
     for busy, k, n, mb, ma, u in rows:
@@ -156,7 +156,7 @@ if os.path.exists(_sq) and os.path.exists(_sq1):
     with open(_sq, "a") as g:
         g.write("\n" + open(_sq1).read())
 for sub, base, steps, cmd in (("lit_stats", f"{tag}_literal_step_kernel_stats", 8.0, "python3 tools/bench_literal.py 4 bf16 6   (8 steps: the reference's literal IRNrhi step, 24 frames 256x256, bf16)"),
-                              ("s512_stats", f"{tag}_bench_512_b8_kernel_stats", 13.0, "python3 bench.py --no-cpu-baseline --no-extra --one-stream --no-graph --size 512 --batch 8 --steps 10 --warmup 3   (13 steps of 8 frames 512x512, one stream)"),
+                              ("s512_stats", f"{tag}_bench_512_b8_kernel_stats", 13.0, "python3 bench.py --full --no-cpu-baseline --no-extra --one-stream --no-graph --size 512 --batch 8 --steps 10 --warmup 3   (13 steps of 8 frames 512x512, one stream)"),
                               ("inn_stats", f"{tag}_inn_step_kernel_stats", 7.0, "INN_PAR=0 python3 tools/bench_inn.py 8 bf16 4   (7 steps enqueued on one stream -- every kernel alone: the invertible embedder, 8 frames 4x256x256, embed + extract + backward + AdamW, bf16)"),
                               ("c5_stats", f"{tag}_c5_fp16_kernel_stats", 42.0, "python3 tools/bench_c5.py train_hidden_c5_fp16.yml f16 44   (42 steps with work, 16 frames 256x256 each, UNet head, f16 + device GradScaler)")):
     try:
@@ -186,7 +186,7 @@ def emit_measurements_md():
     A(f"<!-- generated by tools/summarise_profiles.py {tag} from profiles/{tag}_*: do not edit by hand -->")
     A("| quantity | value (files under `profiles/`) |")
     A("|---|---|")
-    A(f"| step time / throughput, C2 as `bench.py` runs it by default (two chains on two streams, replayed from a hipGraph; every {b.get('kernel_events_every')}th step enqueued on one stream with its kernels bracketed by events) | **{b['ms_per_step']:.3f} ms → {b['value']:.0f} frames/s** (`{tag}_bench_c2.json`; step events: median {b['ms_per_step_median_events']:.3f} ms, fastest {b['ms_per_step_min_events']:.3f} ms); host enqueue per replayed step {b['host_enqueue_ms_median']:.2f} ms" + " |")
+    A(f"| step time / throughput, C2 as `bench.py --full` runs it (two chains on two streams, replayed from a hipGraph; every {b.get('kernel_events_every')}th step enqueued on one stream with its kernels bracketed by events) | **{b['ms_per_step']:.3f} ms → {b['value']:.0f} frames/s** (`{tag}_bench_c2.json`; step events: median {b['ms_per_step_median_events']:.3f} ms, fastest {b['ms_per_step_min_events']:.3f} ms); host enqueue per replayed step {b['host_enqueue_ms_median']:.2f} ms" + " |")
     try:
         modes = open(os.path.join(dst, f"{tag}_step_modes.txt")).read().strip().splitlines()
         A("| the step's four modes, same box, interleaved, two rounds (`" + f"{tag}_step_modes.txt" + "`) | " + "<br>".join(m.replace("|", "/") for m in modes) + " |")
