@@ -15,7 +15,8 @@
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*), re-entrant, and the library
  *     holds no mutable state between calls (no knobs, no environment variables, no set-then-call hints; the
  *     only per-thread datum is the text of the last error); safe under hipGraph capture.  The A/B switches
- *     (wm_debug_*, WM_NO_* variables) of tools/ exist only in the -DWM_DEBUG build lib/libwm_hip_dbg.so;
+ *     (wm_debug_* setters) of tools/ and the tests exist only in the -DWM_DEBUG build lib/libwm_hip_dbg.so;
+ *     neither build reads an environment variable;
  *   - return value: 0 = ok, <0 = error (WM_E_*); wm_last_error_string() gives the text of
  *     the last error on the calling thread.  No C++ exception crosses the boundary;
  *   - activations are NHWC ("pixel-major"): element (b,h,w,c) lives at
@@ -375,7 +376,6 @@ int wm_pooled_bn_bwd_rows(const float* gvec, const float* npos, const float* ysu
 int wm_bn_bwd_finalize_pooled(const float* gvec, const float* npos, const float* ysum, int B, int C, int CP, double count,
                               const float* gamma, const float* mean, const float* invstd, float* dgamma, float* dbeta,
                               int accumulate, float* coef, void* stream);
-int wm_pool_stats_enabled(void);
 /* 1x1 conv Cin->Cout (Cout <= 4) on relu(scale*y+shift): replaces nn.Conv2d(64,3,1) at
  * hidden_models/encoder.py:28,42 and the sigmoid head of network/UNet.py:41-43,65.
  * w f32[Cout,Cin], bias f32[Cout]; out f32 NCHW [B,Cout,H,W]; act 0 = none, 1 = sigmoid. */

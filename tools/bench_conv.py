@@ -35,7 +35,8 @@ flops = 2.0 * B * H * W * C * 9 * C
 import ctypes
 from video_watermarking_forgery_detection_amd import _lib
 _lib._lib = _lib.debug_lib()   # the wm_debug_* switches exist only in the -DWM_DEBUG build (lib/libwm_hip_dbg.so)
-for variant in [int(v) for v in os.environ.get('VARIANTS', '0').split(',')]:
+for variant in [int(v) for v in os.environ.get('VARIANTS', '0').split(',')]:   # VARIANTS=0,1: 16x16x32 / 32x32x16 MFMA consumers
+  assert variant in (0, 1), f"wm_debug_ws_variant {variant}: this tool compares the consumer forms 0 and 1"
   _lib.lib().wm_debug_ws_variant(ctypes.c_int(variant))
   for name, x in xs.items():
     t1 = timeit(lambda: ops.conv3x3_fwd(x, wp, bias, sc, sh, True))

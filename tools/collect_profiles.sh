@@ -46,13 +46,12 @@ echo "part a done"
 ls -R $OUT | head -40
 exit 0
 fi
-# ---- part b: the widened configurations through the model surface, the literal IRNrhi step, the one-pass backward kernel's phases, the co-issue micro
+# ---- part b: the widened configurations through the model surface, the literal IRNrhi step, the co-issue micro
 cd $ROOT
 (python3 tools/bench_c5.py train_hidden_c3.yml bf16 130 && python3 tools/bench_c5.py train_hidden_c3.yml bf16 130 deferred && python3 tools/bench_c5.py train_hidden_c3.yml f16 130 && python3 tools/bench_c5.py train_hidden_c5.yml bf16 130 &&
  python3 tools/bench_c5.py train_hidden_c5_fp16.yml f16 130) 2> $OUT/c3_c5.err | grep '^{' > $OUT/c3_c5_steps.jsonl
 (python3 tools/bench_literal.py 4 bf16 12 && python3 tools/bench_literal.py 4 f16 12) 2> $OUT/literal.err | grep '^{' > $OUT/literal_steps.jsonl
 (python3 tools/bench_inn.py 8 bf16 6 && python3 tools/bench_inn.py 8 bf16 6 graph && python3 tools/bench_inn.py 8 f16 6 graph && INN_PAR=0 python3 tools/bench_inn.py 8 bf16 6 graph) 2> $OUT/inn.err | grep '^{' > $OUT/inn_steps.jsonl
-(python3 tools/phase_bwd.py 0 && python3 tools/phase_bwd.py 256 && python3 tools/phase_bwd.py 8 && python3 tools/phase_bwd.py 1048832) 2>&1 | grep -v amdgpu.ids > $OUT/bwd_phase_cycles.txt
 if [ -x tools/micro/mfma_rate ]; then tools/micro/mfma_rate > $OUT/mfma_coissue_micro.txt 2>&1; fi
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/lit_stats -o l -- python3 $ROOT/tools/bench_literal.py 4 bf16 6 > $OUT/lit_stats.log 2>&1
@@ -62,8 +61,6 @@ bash $ROOT/tools/pmc_bwd.sh > $OUT/bwd_sq_counters.txt 2>&1
 bash $ROOT/tools/pmc_fwd.sh > $OUT/fwd_sq_counters.txt 2>&1
 bash $ROOT/tools/trace_step.sh > $OUT/trace_step.log 2>&1; cp $ROOT/gpurun_out/trace_step/step.txt $OUT/step_trace_one_stream.txt
 cd $ROOT
-python3 tools/phase_ws.py 2>&1 | grep -v amdgpu.ids > $OUT/fwd_phase_cycles.txt
 if [ -f tools/micro/ab/libwm_hip_half.so ]; then python3 tools/bench_two_chains.py half 5 2>&1 | grep -v amdgpu.ids > $OUT/two_chains.txt; fi
-(python3 tools/phase_bwd8.py && python3 tools/phase_bwd8.py gvec) 2>&1 | grep -v amdgpu.ids > $OUT/bwd8_phase_cycles.txt
 echo "widened done"
 ls -R $OUT | head -40

@@ -1,14 +1,11 @@
 """run the fused backward kernel (csrc/bwd_ws.hip) N times on random operands of the benchmark shape: a target for rocprofv3
-usage: python3 tools/run_bwd_fused.py [N] [variant]   (variant: wm_debug_bwd_variant of the debug library)"""
-import ctypes, os, sys
+usage: python3 tools/run_bwd_fused.py [N]"""
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from video_watermarking_forgery_detection_amd import _lib, ops
+from video_watermarking_forgery_detection_amd import ops
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-if len(sys.argv) > 2:
-    _lib._lib = _lib.debug_lib()
-    _lib.lib().wm_debug_bwd_variant(ctypes.c_int(int(sys.argv[2])))
 B, H, W, C, dt = 16, 256, 256, 64, torch.bfloat16
 torch.manual_seed(0)
 g = torch.randn(B, H, W, C, device="cuda").to(dt); y = torch.randn(B, H, W, C, device="cuda").to(dt); xr = torch.randn(B, H, W, C, device="cuda").to(dt)

@@ -393,8 +393,6 @@ extern "C" int wm_bn_finalize(const float* partials, int nparts, int C, int CP, 
 }
 
 constexpr int BWD_BT = 1024;
-WM_KNOB_INT(g_bn_reverse, "WM_BN_REVERSE", 1);   // bit 0: reduce pass sweeps backwards (it follows a forward-sweeping dgrad), bit 1: apply pass
-WM_KNOB_SETTER(wm_debug_bn_reverse, g_bn_reverse)
 extern "C" int wm_bn_bwd_nparts(size_t npix) {
     const size_t n = (npix + BWD_BT - 1) / BWD_BT;
     return (int)(n < 1 ? 1 : (n > 256 ? 256 : n));
@@ -409,13 +407,14 @@ extern "C" int wm_bn_bwd_reduce(const void* g, int ldg, const float* gvec, const
     const size_t npix = (size_t)B * hw;
     const int nparts = wm_bn_bwd_nparts(npix);
     hipStream_t s = (hipStream_t)stream;
+    // (the reduce pass sweeps backwards: it follows a forward-sweeping dgrad; the apply pass below sweeps forwards)
     WM_DISPATCH_DTYPE(dtype, "wm_bn_bwd_reduce",
         if (g) hipLaunchKernelGGL((bn_bwd_kernel<T, false, BWD_BT, false>), dim3(nparts), dim3(BWD_BT), 0, s, (const T*)g, ldg, gvec,
                            (const T*)y, ldy, scale, shift, mean, invstd, (const float*)nullptr, (T*)nullptr, 0, partials,
-                           npix, hw, CP, g_bn_reverse & 1);
+                           npix, hw, CP, 1);
         else hipLaunchKernelGGL((bn_bwd_kernel<T, false, BWD_BT, true>), dim3(nparts), dim3(BWD_BT), 0, s, (const T*)g, ldg, gvec,
                            (const T*)y, ldy, scale, shift, mean, invstd, (const float*)nullptr, (T*)nullptr, 0, partials,
-                           npix, hw, CP, g_bn_reverse & 1));
+                           npix, hw, CP, 1));
     WM_LAUNCH_CHECK("wm_bn_bwd_reduce");
     return WM_OK;
 }
@@ -454,17 +453,17 @@ extern "C" int wm_bn_bwd_apply(const void* g, int ldg, const float* gvec, const 
     if (dbias_partials) {   // rows for wm_colsum_finalize: same grid as the reduce pass
         WM_DISPATCH_DTYPE(dtype, "wm_bn_bwd_apply",
             if (g) hipLaunchKernelGGL((bn_bwd_kernel<T, true, BWD_BT, false>), dim3(nparts), dim3(BWD_BT), 0, s, (const T*)g, ldg, gvec,
-                               (const T*)y, ldy, scale, shift, mean, invstd, coef, (T*)dy, lddy, dbias_partials, npix, hw, CP, (g_bn_reverse >> 1) & 1);
+                               (const T*)y, ldy, scale, shift, mean, invstd, coef, (T*)dy, lddy, dbias_partials, npix, hw, CP, 0);
             else hipLaunchKernelGGL((bn_bwd_kernel<T, true, BWD_BT, true>), dim3(nparts), dim3(BWD_BT), 0, s, (const T*)g, ldg, gvec,
-                               (const T*)y, ldy, scale, shift, mean, invstd, coef, (T*)dy, lddy, dbias_partials, npix, hw, CP, (g_bn_reverse >> 1) & 1));
+                               (const T*)y, ldy, scale, shift, mean, invstd, coef, (T*)dy, lddy, dbias_partials, npix, hw, CP, 0));
     } else {
         const size_t nb = (npix + 255) / 256;
         const int grid = (int)(nb < 1 ? 1 : (nb > 2048 ? 2048 : nb));
         WM_DISPATCH_DTYPE(dtype, "wm_bn_bwd_apply",
             if (g) hipLaunchKernelGGL((bn_bwd_kernel<T, true, 256, false>), dim3(grid), dim3(256), 0, s, (const T*)g, ldg, gvec,
-                               (const T*)y, ldy, scale, shift, mean, invstd, coef, (T*)dy, lddy, dbias_partials, npix, hw, CP, (g_bn_reverse >> 1) & 1);
+                               (const T*)y, ldy, scale, shift, mean, invstd, coef, (T*)dy, lddy, dbias_partials, npix, hw, CP, 0);
             else hipLaunchKernelGGL((bn_bwd_kernel<T, true, 256, true>), dim3(grid), dim3(256), 0, s, (const T*)g, ldg, gvec,
-                               (const T*)y, ldy, scale, shift, mean, invstd, coef, (T*)dy, lddy, dbias_partials, npix, hw, CP, (g_bn_reverse >> 1) & 1));
+                               (const T*)y, ldy, scale, shift, mean, invstd, coef, (T*)dy, lddy, dbias_partials, npix, hw, CP, 0));
     }
     WM_LAUNCH_CHECK("wm_bn_bwd_apply");
     return WM_OK;
@@ -500,10 +499,6 @@ extern "C" int wm_bnrelu_avgpool(const void* y, int ldy, const float* scale, con
     WM_LAUNCH_CHECK("wm_bnrelu_avgpool(finalize)");
     return WM_OK;
 }
-
-WM_KNOB_ON(g_pool_stats, "WM_NO_POOL_STATS");
-WM_KNOB_SETTER(wm_debug_pool_stats, g_pool_stats)   // A/B knob (tools/ab_step.py, debug build only)
-extern "C" int wm_pool_stats_enabled(void) { return g_pool_stats; }
 
 extern "C" int wm_bnrelu_avgpool_stats(const void* y, int ldy, const float* scale, const float* shift, float* out3, float* ws, int B,
                                        size_t hw, int CP, int dtype, void* stream) {

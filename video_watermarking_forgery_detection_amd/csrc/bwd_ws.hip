@@ -32,8 +32,6 @@ typedef h16<hx_t> HX;
 typedef HX::x8 hx8;
 typedef HX::x2 hx2;
 
-int wm_sweep_dir(int reverse);   // conv3x3_ws.hip
-
 namespace {
 
 constexpr int TH = 8, TW = 16, HH = 10, HW = 18, NPX = HH * HW, C = 64;
@@ -72,10 +70,6 @@ __device__ __forceinline__ hx8 tr_frag(const char* p0, const char* p1) {
     return __builtin_bit_cast(hx8, v);
 }
 
-// DBG (debug build only, tools/ab_step.py wm_debug_bwd_variant): phase ablations -- 1 skip the input-gradient MFMAs, 2 the weight-gradient
-// MFMAs, 4 the epilogue, 8 the staging of the next tile, 16 stage the same tile again and again (results are then meaningless; compile-
-// time so the real kernel is untouched), 512 no dx stores, 1024 / 2048 half the filter / dy fragment reads of the input- / weight-gradient loop,
-// 4096 phase stamps (with 512: the sums land where dx would)
 // PREMASKED: g arrives already multiplied by its layer's ReLU mask (this kernel's own dx is written that way, see the epilogue), so the
 // staging's compare + select + the z fma disappear; masking twice is the identity, so results do not depend on the flag
 // GVEC: the layer's output was globally pooled, so its gradient is one value per (sample, channel): the staging reads y only and takes
@@ -86,7 +80,7 @@ __device__ __forceinline__ hx8 tr_frag(const char* p0, const char* p1) {
 // left or right of the image reads its neighbour in memory (a valid address; the value is zeroed when it is published), one above the first
 // or below the last image falls outside the buffer descriptor's range and reads zeros; which slots lie outside the image is a wave-uniform
 // choice among four per-thread bit masks (top / bottom / left / right edge), and the a tile needs no masking at all.
-template <int DBG, bool PREMASKED, bool GVEC = false, bool ALIGNED = false>
+template <bool PREMASKED, bool GVEC = false, bool ALIGNED = false>
 __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[SW_BYTES + 2 * BUF_BYTES + 4 * 2 * C * 4 + 2 * C * 4 + (C * 8 + 32) * 4 + (GVEC ? GV_MAXB * C * 4 : 0)];
     hx_t* sW = reinterpret_cast<hx_t*>(smem);
@@ -383,7 +377,6 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
         const bool is_dy = j < 3;
         const int k = is_dy ? grp * 3 + j : grp * 2 + (j - 3);
         if (v < 20) {
-            if constexpr ((DBG & 32) != 0) return;   // DBG 32: no transform arithmetic (raw operands are published)
             const int pq = v / 5;
             if (is_dy) {
                 u32x4 w = __builtin_bit_cast(u32x4, GVEC ? dY[k] : dG[k]);
@@ -392,7 +385,7 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
                 if constexpr (GVEC) {
                     d0 = wm_bn_fold_dy(HX::lo(wy[pq]), pka[0], pka[1], pka[3], pka2[0], pkg[0]);
                     d1 = wm_bn_fold_dy(HX::hi(wy[pq]), pkb[0], pkb[1], pkb[3], pkb2[0], pkg[1]);
-                } else if constexpr (PREMASKED || (DBG & 256) != 0) {   // (DBG 256: timing probe of the same on unmasked data)
+                } else if constexpr (PREMASKED) {
                     d0 = __builtin_fmaf(pka[2], HX::lo(w[pq]), __builtin_fmaf(-pka[3], HX::lo(wy[pq]), pka2[0]));
                     d1 = __builtin_fmaf(pkb[2], HX::hi(w[pq]), __builtin_fmaf(-pkb[3], HX::hi(wy[pq]), pkb2[0]));
                 } else {
@@ -417,7 +410,7 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
 #pragma unroll
             for (int q4 = 0; q4 < 4; ++q4) w[q4] &= keep;
             if (k + 1 < XV || last_live) *reinterpret_cast<u32x4*>(buf + hlds[k]) = w;
-            if (refill && !(DBG & 64)) {   // DBG 64: no refill loads
+            if (refill) {
                 load_dy_slot(g2, k);
                 if constexpr (ALIGNED) okh = (okh & ~(1u << k)) | (okn & (1u << k));   // the slot now holds tile + 2's pixel (one v_bfi)
             }
@@ -429,24 +422,18 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
                 for (int q4 = 0; q4 < 4; ++q4) w[q4] &= keep;
             }
             *reinterpret_cast<u32x4*>(buf + (alds0 + k * 32 * 128)) = w;
-            if (refill && !(DBG & 64)) load_a_slot(g2, k);
+            if (refill) load_a_slot(g2, k);
         }
     };
-    constexpr int NUNIT = 50;
     static_assert(XV == 6 && AV == 4, "the staging schedule is written for 6 + 4 slots");
     // the second tile of the run is requested before the loop; from then on every slot is re-requested as soon as it has been published
-    if (t_begin + 1 < t_end && !(DBG & 8)) { const TileGeo g1 = geo(t_begin + 1); load_halo(g1); load_atile(g1); }
+    if (t_begin + 1 < t_end) { const TileGeo g1 = geo(t_begin + 1); load_halo(g1); load_atile(g1); }
 
     // one tile; STAGE: tile + 1 exists (its operands are in the registers: publish them); REFILL: tile + 2 exists (request it).  Compile-
     // time, so the body is straight-line code the scheduler can interleave; the last two tiles of a run use the reduced bodies
-    // DBG 4096: s_memtime stamps at the phase boundaries, summed per workgroup and written over the start of dx (tools/phase_bwd.py)
-    unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, t_run0 = 0, r_run0 = 0;
-    if constexpr ((DBG & 4096) != 0) { t_run0 = __builtin_amdgcn_s_memtime(); r_run0 = __builtin_amdgcn_s_memrealtime(); }
     auto tile_body = [&](int tile, auto stage_c, auto refill_c) {
-        unsigned long long ts[7];
-        if constexpr ((DBG & 4096) != 0) ts[0] = __builtin_amdgcn_s_memtime();
-        constexpr bool stage = decltype(stage_c)::value && !(DBG & 8);
-        constexpr bool refill = decltype(refill_c)::value && !(DBG & 8);
+        constexpr bool stage = decltype(stage_c)::value;
+        constexpr bool refill = decltype(refill_c)::value;
         const unsigned char* cur = sBuf + ((tile - t_begin) & 1) * BUF_BYTES;
         unsigned char* nxt = sBuf + (((tile - t_begin) & 1) ^ 1) * BUF_BYTES;
         // the tile's scalar bookkeeping and the request of its epilogue operand (the feeding layer's y at this lane's two output pixels:
@@ -461,7 +448,7 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
         auto head_work = [&]() __attribute__((always_inline)) {
             g = geo(tile);
             if constexpr (GVEC && decltype(stage_c)::value) bpub = geo(tile + 1).b;
-            g2 = (DBG & 16) ? geo(t_begin) : geo(refill ? tile + 2 : tile);   // DBG 16: every refill re-reads the run's first tile (L2 hits)
+            g2 = geo(refill ? tile + 2 : tile);
             if constexpr (ALIGNED && refill) okn = inside_bits(g2);
 #pragma unroll
             for (int ml = 0; ml < 2; ++ml) {
@@ -481,10 +468,9 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
                 ryv[ml][4] = t1[0]; ryv[ml][5] = t1[1]; ryv[ml][6] = t1[2]; ryv[ml][7] = t1[3];
             }
         };
-        if constexpr ((DBG & 2) != 0) { head_work(); if constexpr ((DBG & 4096) != 0) ts[1] = __builtin_amdgcn_s_memtime(); }
         // ---------------- weight gradient: 4 K-steps x 9 taps x (2 x 2 fragments); the dy fragments of the next tap are requested while
         // this tap's four MFMAs run (fenced: an unfenced schedule hoists dozens of fragment reads and spills)
-        if constexpr (!(DBG & 2)) {
+        {
             const char* curc = reinterpret_cast<const char*>(cur);
             // one wave per SIMD has nobody to hide its LDS latency behind: the dy fragments are requested WR - 1 taps ahead (a ring of WR),
             // the a fragments of the next K-step half a K-step ahead
@@ -505,11 +491,10 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
             for (int i = 0; i < WR - 1; ++i) load_a(i, i);
             head_work();
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr ((DBG & 4096) != 0) { ts[1] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
 #pragma unroll
             for (int st = 0; st < 36; ++st) {
                 const int ks = st / 9, tap = st - ks * 9;
-                if (st + WR - 1 < 36 && !((DBG & 2048) && ((st + WR - 1) & 1))) load_a(st + WR - 1, (st + WR - 1) % WR);   // DBG 2048: half the dy fragment reads
+                if (st + WR - 1 < 36) load_a(st + WR - 1, (st + WR - 1) % WR);
                 if (tap == 4 && ks + 1 < TH / 2) load_b(ks + 1, (ks + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -523,10 +508,8 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
         // gfx9 counts loads and stores in ONE counter and only loads return in order: with the previous tile's dx stores possibly pending,
         // every wait on a staged slot would become vmcnt(0) -- also for the slots just re-requested.  So ONE full wait here, where it is
         // free (everything outstanding was issued at least a weight-gradient phase ago and is needed now), and none after the refills
-        if constexpr ((DBG & 4096) != 0) { ts[2] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr ((DBG & 4096) != 0) { ts[3] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
         // ---------------- input gradient: 18 K-steps x (2 pixel + 4 filter fragments, 8 MFMAs), the next tile's staging in their shadow
         f32x4 acc[2][4];
 #pragma unroll
@@ -543,8 +526,7 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
                 rhv[jj] = *reinterpret_cast<const f32x4*>(sTab + C + 16 * q + 4 * jj);
             }
         };
-        if constexpr ((DBG & 1) != 0) load_rsrh(0, 2);
-        if constexpr (!(DBG & 1)) {
+        {
             // fragment schedule: every fragment of K-step sidx + 1 is requested at the top of K-step sidx (8 MFMAs + the staging units ahead
             // of its use: one wave per SIMD has to cover the LDS latency itself); 48 registers of operands
             hx8 pix[2][2], filA[2][2], filB[2][2];
@@ -563,7 +545,7 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
             };
             // the region's schedule: MFMA, up to IV VALU instructions, MFMA, ... (whatever is left follows the fourth group)
             auto interleave4 = [] {
-                constexpr int IV = (DBG & 8192) ? 3 : 5;
+                constexpr int IV = 5;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, IV, 0); }
             };
@@ -573,52 +555,43 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
 #pragma unroll
             for (int sidx = 0; sidx < 18; ++sidx) {
                 const int cb = sidx & 1;
-                constexpr bool inter = stage && !(DBG & 128);
-                if constexpr (inter) { if ((2 * sidx) % 18 < 16 && ((2 * sidx) % 18) % 4 == 0) pub_consts(((2 * sidx) % 18) / 4); }
+                if constexpr (stage) { if ((2 * sidx) % 18 < 16 && ((2 * sidx) % 18) % 4 == 0) pub_consts(((2 * sidx) % 18) / 4); }
                 if (sidx == 17 && (PREMASKED || GVEC)) load_rsrh(0, 2);   // (all four vectors here cost the unmasked-g variant 2 spilled registers; its f16 twin has no room for any)
                 if (sidx + 1 < 18) {
                     load_pix(sidx + 1, cb ^ 1);
-                    if (!((DBG & 1024) && (sidx & 1))) { load_fil(sidx + 1, 0, filA[cb ^ 1]); load_fil(sidx + 1, 1, filB[cb ^ 1]); }   // DBG 1024: half the filter fragment reads
+                    load_fil(sidx + 1, 0, filA[cb ^ 1]);
+                    load_fil(sidx + 1, 1, filB[cb ^ 1]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int ml = 0; ml < 2; ++ml)
 #pragma unroll
                     for (int n = 0; n < 2; ++n) acc[ml][n] = HX::mfma16(filA[cb][n], pix[cb][ml], acc[ml][n]);
-                if constexpr (inter) {
+                if constexpr (stage) {
 #pragma unroll
                     for (int u = hs_first(2 * sidx); u < hs_first(2 * sidx) + hs_count(2 * sidx); ++u) pub_unit(u, nxt, refill, g2, okn);
                     interleave4();
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (inter) { if ((2 * sidx + 1) % 18 < 16 && ((2 * sidx + 1) % 18) % 4 == 0) pub_consts(((2 * sidx + 1) % 18) / 4); }
+                if constexpr (stage) { if ((2 * sidx + 1) % 18 < 16 && ((2 * sidx + 1) % 18) % 4 == 0) pub_consts(((2 * sidx + 1) % 18) / 4); }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int ml = 0; ml < 2; ++ml)
 #pragma unroll
                     for (int n = 0; n < 2; ++n) acc[ml][2 + n] = HX::mfma16(filB[cb][n], pix[cb][ml], acc[ml][2 + n]);
-                if constexpr (inter) {
+                if constexpr (stage) {
 #pragma unroll
                     for (int u = hs_first(2 * sidx + 1); u < hs_first(2 * sidx + 1) + hs_count(2 * sidx + 1); ++u) pub_unit(u, nxt, refill, g2, okn);
                     interleave4();
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (stage && (DBG & 128) != 0) {   // DBG 128: the staging as one block after the MFMAs instead of between them
-#pragma unroll
-                for (int u = 0; u < NUNIT; ++u) { if (u % 25 < 20 && u % 5 == 0) pub_consts((u % 25) / 5); pub_unit(u, nxt, refill, g2, okn); __builtin_amdgcn_sched_barrier(0); }
-            }
-        } else if constexpr (stage) {
-#pragma unroll
-            for (int u = 0; u < NUNIT; ++u) { if (u % 25 < 20 && u % 5 == 0) pub_consts((u % 25) / 5); pub_unit(u, nxt, refill, g2, okn); }
         }
-        if constexpr ((DBG & 4096) != 0) { __builtin_amdgcn_sched_barrier(0); ts[4] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
         // ---------------- input-gradient epilogue: layer L-1's BatchNorm-backward sums (gz = dx * [z > 0], dx rounded as stored), pack, store
         // (one wave per SIMD pays an issue slot for every instruction: 15 VALU instructions per channel pair; branch-free, so both pixel rows
         // schedule as one block)
-        if constexpr (!(PREMASKED || GVEC) && !(DBG & 1)) load_rsrh(0, 2);
+        if constexpr (!(PREMASKED || GVEC)) load_rsrh(0, 2);
         load_rsrh(2, 4);
-        if constexpr (!(DBG & 4))
 #pragma unroll
         for (int ml = 0; ml < 2; ++ml) {
             unsigned pk[8];
@@ -639,22 +612,14 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
                 s2[2 * j + 1] = __builtin_fmaf(gz1, y1, s2[2 * j + 1]);
             }
             if constexpr (ALIGNED) {
-                if (!(DBG & 512)) {   // DBG 512: no dx stores
-                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk[0], pk[1], pk[2], pk[3]}, rsD, eo[ml], 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk[4], pk[5], pk[6], pk[7]}, rsD, eo[ml] + 16u, 0, 0);
-                }
-            } else if (inb[ml] && !(DBG & 512)) {
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk[0], pk[1], pk[2], pk[3]}, rsD, eo[ml], 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk[4], pk[5], pk[6], pk[7]}, rsD, eo[ml] + 16u, 0, 0);
+            } else if (inb[ml]) {
                 *reinterpret_cast<u32x4*>(outp[ml]) = u32x4{pk[0], pk[1], pk[2], pk[3]};
                 *reinterpret_cast<u32x4*>(outp[ml] + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
             }
         }
-        if constexpr ((DBG & 4096) != 0) { __builtin_amdgcn_sched_barrier(0); ts[5] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
         __syncthreads();
-        if constexpr ((DBG & 4096) != 0) {
-            ts[6] = __builtin_amdgcn_s_memtime();
-#pragma unroll
-            for (int i = 0; i < 6; ++i) ph[i] += ts[i + 1] - ts[i];
-        }
     };
     {
         typedef std::integral_constant<bool, true> yes;
@@ -665,15 +630,6 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
         if (tile < t_end) tile_body(tile, no{}, no{});
     }
 
-    if constexpr ((DBG & 4096) != 0) {
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (tid == 0) {
-            unsigned long long* o = reinterpret_cast<unsigned long long*>(a.dx) + (size_t)blockIdx.x * 8;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) o[i] = ph[i];
-            o[6] = t1 - t_run0; o[7] = r1 - r_run0;
-        }
-    }
     // ---- weight-gradient slab: wacc[tap][fi][fj][i] = sum_q dy[q + (kh-1, kw-1)][co] * a[q][ci], co = 32mi + 16fi + 4kq + i,
     // ci = 32ni + 16fj + r: that is dW of filter tap 8 - tap; slab layout [tap][ci][co] (wgrad.hip's reduction)
     float* slab = a.ws + (size_t)blockIdx.x * 9 * C * C;
@@ -712,7 +668,7 @@ int WM_HSYM(wm_bwd_ws_gvec_max_batch)() { return GV_MAXB; }
 // nwg workgroups (= slabs = partial rows), each a run of 8x16-pixel tiles
 void WM_HSYM(wm_launch_bwd_ws)(const void* g, const void* y, const float* stats4, int st_ld, const float* coef, const void* wpt, const void* xr,
                                const float* in_scale, const float* in_shift, void* dx, float* stat, float* ws, int B, int H, int W, int nwg,
-                               int reverse, hipStream_t s, int dbg, int premasked, const float* gvec, int gv_ld) {
+                               int reverse, hipStream_t s, int premasked, const float* gvec, int gv_ld) {
     BwdArgs a;
     a.g = (const hx_t*)g; a.y = (const hx_t*)y; a.stats4 = stats4; a.st_ld = st_ld; a.coef = coef; a.wpt = (const hx_t*)wpt;
     a.gvec = gvec; a.gv_ld = gv_ld;
@@ -720,46 +676,15 @@ void WM_HSYM(wm_launch_bwd_ws)(const void* g, const void* y, const float* stats4
     a.B = B; a.H = H; a.W = W; a.tilesX = wm_cdiv(W, TW); a.tilesY = wm_cdiv(H, TH); a.ntiles = B * a.tilesX * a.tilesY;
     auto magic = [](int d) { return d == 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); };
     a.mX = magic(a.tilesX); a.mY = magic(a.tilesY); a.m2X = magic(2 * a.tilesX);
-    a.reverse = wm_sweep_dir(reverse);
-    const bool aligned = H % TH == 0 && W % TW == 0 && !(dbg & (1 << 20));   // (debug bit 20: the general addressing on a whole-tile shape, for A/B)
-#ifdef WM_DEBUG
-    if (!gvec && aligned)   // phase stamps of the whole-tile (buffer-addressed) form: tools/phase_bwd.py
-    switch (dbg) {
-        case 4608: hipLaunchKernelGGL((bwd_ws_kernel<4608, false, false, true>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 4864: hipLaunchKernelGGL((bwd_ws_kernel<4864, false, false, true>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 4616: hipLaunchKernelGGL((bwd_ws_kernel<4616, false, false, true>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        default: break;
-    }
-    if (!gvec)   // (the ablation variants exist for the tensor-gradient form only; a gvec launch has no g to read)
-    switch (dbg & ~(1 << 20)) {
-        case 1: hipLaunchKernelGGL((bwd_ws_kernel<1, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 2: hipLaunchKernelGGL((bwd_ws_kernel<2, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 3: hipLaunchKernelGGL((bwd_ws_kernel<3, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 4: hipLaunchKernelGGL((bwd_ws_kernel<4, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 8: hipLaunchKernelGGL((bwd_ws_kernel<8, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 32: hipLaunchKernelGGL((bwd_ws_kernel<32, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 64: hipLaunchKernelGGL((bwd_ws_kernel<64, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 512: hipLaunchKernelGGL((bwd_ws_kernel<512, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 1024: hipLaunchKernelGGL((bwd_ws_kernel<1024, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 2048: hipLaunchKernelGGL((bwd_ws_kernel<2048, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 3072: hipLaunchKernelGGL((bwd_ws_kernel<3072, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 4608: hipLaunchKernelGGL((bwd_ws_kernel<4608, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 4616: hipLaunchKernelGGL((bwd_ws_kernel<4616, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 4640: hipLaunchKernelGGL((bwd_ws_kernel<4640, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 4672: hipLaunchKernelGGL((bwd_ws_kernel<4672, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 4864: hipLaunchKernelGGL((bwd_ws_kernel<4864, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        case 15: hipLaunchKernelGGL((bwd_ws_kernel<15, false>), dim3((unsigned)nwg), dim3(256), 0, s, a); return;
-        default: break;
-    }
-#endif
-    (void)dbg;
+    a.reverse = reverse ? 1 : 0;
+    const bool aligned = H % TH == 0 && W % TW == 0;
     if (aligned) {
-        if (gvec) hipLaunchKernelGGL((bwd_ws_kernel<0, false, true, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
-        else if (premasked) hipLaunchKernelGGL((bwd_ws_kernel<0, true, false, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((bwd_ws_kernel<0, false, false, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
+        if (gvec) hipLaunchKernelGGL((bwd_ws_kernel<false, true, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
+        else if (premasked) hipLaunchKernelGGL((bwd_ws_kernel<true, false, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((bwd_ws_kernel<false, false, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
         return;
     }
-    if (gvec) hipLaunchKernelGGL((bwd_ws_kernel<0, false, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
-    else if (premasked) hipLaunchKernelGGL((bwd_ws_kernel<0, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((bwd_ws_kernel<0, false>), dim3((unsigned)nwg), dim3(256), 0, s, a);
+    if (gvec) hipLaunchKernelGGL((bwd_ws_kernel<false, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
+    else if (premasked) hipLaunchKernelGGL((bwd_ws_kernel<true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((bwd_ws_kernel<false>), dim3((unsigned)nwg), dim3(256), 0, s, a);
 }

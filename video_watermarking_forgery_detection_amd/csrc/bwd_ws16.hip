@@ -28,8 +28,6 @@ typedef h16<hx_t> HX;
 typedef HX::x8 hx8;
 typedef HX::x2 hx2;
 
-int wm_sweep_dir(int reverse);   // conv3x3_ws.hip
-
 namespace {
 
 constexpr int TH = 8, TW = 16, HH = 10, HW = 18, NPX = HH * HW, C = 64, CX = 16;
@@ -289,7 +287,7 @@ void WM_HSYM(wm_launch_bwd_ws16)(const void* g, const void* y, const float* stat
     a.g = (const hx_t*)g; a.y = (const hx_t*)y; a.stats4 = stats4; a.st_ld = st_ld; a.coef = coef; a.wpt = (const hx_t*)wpt;
     a.x = (const hx_t*)x; a.dx = (hx_t*)dx; a.ws = ws;
     a.B = B; a.H = H; a.W = W; a.tilesX = W / TW; a.tilesY = H / TH; a.ntiles = B * a.tilesX * a.tilesY;
-    a.reverse = wm_sweep_dir(reverse);
+    a.reverse = reverse ? 1 : 0;
     // (dynamic LDS for the allocation's size alone: see wgrad_ws.hip WM_LDS_PAD16 -- a workgroup of the JPEG kernels must not fit beside this
     //  kernel on a CU.  It costs this kernel its second workgroup per CU.)
     constexpr int PAD = 137472 - (SW_BYTES + 2 * BUF_BYTES + (C * 8 + 32) * 4);

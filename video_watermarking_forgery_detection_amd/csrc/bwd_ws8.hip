@@ -29,8 +29,6 @@ typedef h16<hx_t> HX;
 typedef HX::x8 hx8;
 typedef HX::x2 hx2;
 
-int wm_sweep_dir(int reverse);   // conv3x3_ws.hip
-
 namespace {
 
 constexpr int TH = 8, TW = 16, HH = 10, HW = 18, NPX = HH * HW, C = 64;
@@ -55,16 +53,7 @@ struct Bwd8Args {
     int B, H, W, tilesX, tilesY, ntiles, reverse;
     int tq, trem;                                          // ntiles / gridDim.x, ntiles % gridDim.x
     unsigned mX, mY, m2X;
-    int stamps;                                            // debug build: per-wave phase cycle sums instead of the partial rows
 };
-
-// debug build (tools/phase_bwd8.py): s_memtime sums per wave -- [0] the MFMA loop (+ the units between its MFMAs), [1] W: staging of the
-// a tile / D: the wait at the tile's barrier, [2] W: the wait at the barrier / D: the epilogue; written over the workgroup's partial rows
-#ifdef WM_DEBUG
-#define WM_STAMP(i) if (a.stamps) { const long long now_ = (long long)__builtin_amdgcn_s_memtime(); tacc[i] += now_ - tprev; tprev = now_; }
-#else
-#define WM_STAMP(i)
-#endif
 
 __device__ __forceinline__ int fsw(int px) { return ((px >> 2) & 1) | (((px >> 1) & 1) << 1) | (((px >> 3) & 1) << 2); }
 __device__ __forceinline__ int swz16(int col) { return (((col >> 1) & 1) << 5) | (((col >> 3) & 1) << 6); }
@@ -91,9 +80,6 @@ __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const bool wrole = tid >= 256;           // waves 4..7: the weight gradient
     const int rt = tid & 255, wave = rt >> 6;   // index inside the role
-#ifdef WM_DEBUG
-    long long tacc[4] = {0, 0, 0, 0}, tprev = a.stamps ? (long long)__builtin_amdgcn_s_memtime() : 0;   // [3]: everything outside the tile loop
-#endif
     // ---- prologue (round 4): EVERY global load of the prologue is issued before anything waits -- the constants (wave 0), the filter
     // (9 vectors per thread; round 3's loop `load, wait, write` ran its 9 trips one L2 round trip after the other: ~4 us of every launch)
     // and, further down, the role's first tile; the LDS commits follow in issue order (vmcnt retires in order), one barrier for all
@@ -275,7 +261,6 @@ __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
                     for (int fj = 0; fj < 2; ++fj) wacc[tap][fi][fj] = HX::mfma16(afrag[st % WR][fi], bfrag[ks & 1][fj], wacc[tap][fi][fj]);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            WM_STAMP(0)
             // the a tile of tile + 1 AFTER the loop: a W wave is done long before its D partner (144 MFMAs against 144 + the dy staging + the
             // epilogue), the fragment registers are free now, and nothing of it sits on the tile's critical path
             if constexpr (stage) {
@@ -293,11 +278,8 @@ __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
                     for (int k = 0; k < AV; ++k) load_a_slot(g2, k);
                 }
             }
-            WM_STAMP(1)
             __syncthreads();
-            WM_STAMP(2)
         };
-        WM_STAMP(3)
         {
             int tile = t_begin;
             for (; tile + 2 < t_end; ++tile) w_tile(tile, yes{}, yes{});
@@ -315,16 +297,6 @@ __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
                     const int ci = ni * 32 + fj * 16 + r, co = mi * 32 + fi * 16 + 4 * kq;
                     *reinterpret_cast<f32x4*>(slab + ((size_t)(8 - tap) * C + ci) * C + co) = wacc[tap][fi][fj];
                 }
-#ifdef WM_DEBUG
-        if (a.stamps) {
-            __builtin_amdgcn_s_waitcnt(0);
-            WM_STAMP(3)
-            if (lane == 0) {
-                long long* o = reinterpret_cast<long long*>(a.stat + (size_t)blockIdx.x * 2 * C) + (tid >> 6) * 4;
-                o[0] = tacc[0]; o[1] = tacc[1]; o[2] = tacc[2]; o[3] = tacc[3];
-            }
-        }
-#endif
         __syncthreads();   // (the D role's final barrier: its partial sums)
         return;
     }
@@ -516,12 +488,10 @@ __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
             units(2 * sidx + 1);
             __builtin_amdgcn_sched_barrier(0);
         }
-        WM_STAMP(0)
         // The tile's barrier sits HERE, in front of the epilogue: every read of this tile's LDS buffer and every staging write into the next
         // one is done, and the epilogue touches neither (accumulators, its operand registers, the constant table) -- so the W waves start
         // the next tile's weight-gradient MFMAs while this role still masks, packs and sums: VALU work beside the partner's matrix work
         __syncthreads();
-        WM_STAMP(1)
         // epilogue: the feeding layer's BatchNorm-backward sums (gz = dx * [z > 0], dx rounded as stored), pack, store
         f32x4 rsv[4], rhv[4];
 #pragma unroll
@@ -547,9 +517,7 @@ __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk[0], pk[1], pk[2], pk[3]}, rsD, eo[ml], 0, 0);
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk[4], pk[5], pk[6], pk[7]}, rsD, eo[ml] + 16u, 0, 0);
         }
-        WM_STAMP(2)
     };
-    WM_STAMP(3)
     {
         int tile = t_begin;
         for (; tile + 2 < t_end; ++tile) d_tile(tile, yes{}, yes{});
@@ -568,16 +536,6 @@ __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
         }
     }
     __syncthreads();
-#ifdef WM_DEBUG
-    if (a.stamps) {
-        WM_STAMP(3)
-        if (lane == 0) {
-            long long* o = reinterpret_cast<long long*>(a.stat + (size_t)blockIdx.x * 2 * C) + (tid >> 6) * 4;
-            o[0] = tacc[0]; o[1] = tacc[1]; o[2] = tacc[2]; o[3] = tacc[3];
-        }
-        return;
-    }
-#endif
     if (tid < 2 * C) {
         const int which = tid / C, n = tid - which * C;
         a.stat[((size_t)blockIdx.x * 2 + which) * C + n] =
@@ -589,9 +547,8 @@ __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
 
 int WM_HSYM(wm_launch_bwd_ws8)(const void* g, const void* y, const float* stats4, int st_ld, const float* coef, const void* wpt, const void* xr,
                                 const float* in_scale, const float* in_shift, void* dx, float* stat, float* ws, int B, int H, int W, int nwg,
-                                int reverse, hipStream_t s, int premasked, const float* gvec, int gv_ld, int stamps) {
+                                int reverse, hipStream_t s, int premasked, const float* gvec, int gv_ld) {
     Bwd8Args a;
-    a.stamps = stamps;
     a.g = (const hx_t*)g; a.y = (const hx_t*)y; a.stats4 = stats4; a.st_ld = st_ld; a.coef = coef; a.wpt = (const hx_t*)wpt;
     a.gvec = gvec; a.gv_ld = gv_ld;
     a.xr = (const hx_t*)xr; a.in_scale = in_scale; a.in_shift = in_shift; a.dx = (hx_t*)dx; a.stat = stat; a.ws = ws;
@@ -599,7 +556,7 @@ int WM_HSYM(wm_launch_bwd_ws8)(const void* g, const void* y, const float* stats4
     auto magic = [](int d) { return d == 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); };
     a.mX = magic(a.tilesX); a.mY = magic(a.tilesY); a.m2X = magic(2 * a.tilesX);
     a.tq = a.ntiles / nwg; a.trem = a.ntiles % nwg;
-    a.reverse = wm_sweep_dir(reverse);
+    a.reverse = reverse ? 1 : 0;
     // (the unmasked-gradient form is not instantiated: it needs ~15 registers more than a two-waves-per-SIMD kernel has and stays on
     // bwd_ws.hip -- wgrad.hip dispatches.  Both instantiated forms: 250 registers, no scratch.)  An unmasked tensor gradient handed to
     // this launcher would be staged WITHOUT its ReLU mask: refused here, whatever the caller's dispatch condition says

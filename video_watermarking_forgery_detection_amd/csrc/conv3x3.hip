@@ -265,12 +265,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs<T> a) {
 constexpr int WS_MAX_WGS = WM_MAX_WGS;  // one persistent workgroup per CU
 inline bool is16(int dtype) { return dtype == WM_BF16 || dtype == WM_F16; }   // the two 16-bit activation dtypes share every MFMA kernel
 inline bool use_ws(int Cin, int CoutP, int dtype) {
-    static const bool off = WM_ENV_FLAG("WM_NO_WS");  // diagnostic knob (debug build): force the generic kernel
-    return !off && is16(dtype) && (((Cin == 64 || Cin == 32 || Cin == 16) && CoutP == 64) || (Cin == 64 && CoutP == 32));
+    return is16(dtype) && (((Cin == 64 || Cin == 32 || Cin == 16) && CoutP == 64) || (Cin == 64 && CoutP == 32));
 }  // + ldy == CoutP (a dense output tensor)
 inline bool use_stream(int Cin, int CoutP, int dtype) {
-    static const bool off = WM_ENV_FLAG("WM_NO_STREAM");  // diagnostic knob (debug build): force the generic kernel
-    return !off && is16(dtype) && !use_ws(Cin, CoutP, dtype) && wm_conv3x3_stream_supported(Cin, CoutP);
+    return is16(dtype) && !use_ws(Cin, CoutP, dtype) && wm_conv3x3_stream_supported(Cin, CoutP);
 }
 inline int ws_tiles_per_wg(int ntiles) { return (ntiles + WS_MAX_WGS - 1) / WS_MAX_WGS; }
 inline int ws_wgs(int ntiles) { const int per = ws_tiles_per_wg(ntiles); return (ntiles + per - 1) / per; }
@@ -438,8 +436,7 @@ extern "C" int wm_conv3x3_dgrad_gvfused(const void* y, int ldy, int CoutY, const
 
 // input gradient whose epilogue also reduces the BatchNorm-backward sums of the layer it feeds.  src: dy [B,H,W,lds] of this
 // layer, or (gvec != NULL) this layer's raw output y with the apply pass fused as in wm_conv3x3_dgrad_gvfused.
-WM_KNOB_ON(g_bwdst, "WM_NO_BWDST");
-WM_KNOB_SETTER(wm_debug_bwdst, g_bwdst)   // A/B knob (tools/ab_step.py, debug build only)
+WM_KNOB(g_bwdst, wm_debug_bwdst, 1);   // A/B knob (tools/ab_step.py, debug build only)
 extern "C" int wm_conv3x3_dgrad_bwdstats_supported(int CoutY, int CinP, int dtype) {
     return (g_bwdst && is16(dtype) && (CoutY == 64 || CoutY == 32) && CinP == 64 && use_ws(CoutY, CinP, dtype)) ? 1 : 0;
 }
@@ -464,8 +461,7 @@ extern "C" int wm_conv3x3_dgrad_bwdstats(const void* src, int lds, int CoutY, co
 
 // input gradient of an ordinary 64 -> 64 ConvBNRelu with the BatchNorm-backward APPLY pass fused: reads g and the layer's raw
 // output y, writes dy (for the weight gradient that follows) and dx; optionally reduces the feeding layer's sums as above.
-WM_KNOB_ON(g_applyfuse, "WM_NO_APPLY_FUSE");
-WM_KNOB_SETTER(wm_debug_apply_fuse, g_applyfuse)   // A/B knob (tools/ab_step.py, debug build only)
+WM_KNOB(g_applyfuse, wm_debug_apply_fuse, 1);   // A/B knob (tools/ab_step.py, debug build only)
 extern "C" int wm_conv3x3_dgrad_applyfused_supported(int CoutY, int CinP, int dtype) {
     return (g_applyfuse && is16(dtype) && CoutY == 64 && (CinP == 64 || CinP == 32) && use_ws(CoutY, CinP, dtype)) ? 1 : 0;
 }

@@ -47,8 +47,6 @@ struct WsArgs {
     int ldy;                   // NARROW (the 32-channel consumers only): the output's pixel stride when it is below COUT -- channels >= ldy are not stored
     float* stat;                 // [gridDim.x][2][64] or null
     int B, H, W, tilesX, tilesY, ntiles, tiles_per_wg;
-    int dbg;      // STAMPS build only: 1 = skip the MFMA loop, 2 = skip the stores, 4 = skip the halo loads
-    int xcd_map;
     const float* bw_stats4; int bw_ld; const float* bw_coef; const float* bw_gvec;   // BNBWD: [scale|shift|mean|invstd][bw_ld], coef [3][bw_ld], gvec [B][bw_ld]
     const hx_t* ry; const float* r_scale; const float* r_shift;   // BWDST: raw output [B,H,W,COUT] and scale / shift of the layer whose output gradient this kernel writes
     const hx_t* ay; hx_t* dy_out;   // BNBWD == 2: x is g [B,H,W,64]; ay the layer's raw output, dy_out where dy is written (both dense)
@@ -74,7 +72,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
 
-// STAMPS: diagnostic build only (tools/phase_ws.py) -- per-role cycle totals of the phases of the tile loop
 // M16: consumers use v_mfma_f32_16x16x32_bf16 (needs CIN % 32 == 0) instead of 32x32x16: same FLOPs per cycle, but the
 // chip holds a higher clock on it under load (MI355X_MICROARCH.md, DVFS give-back item 7); A/B: tools/ab_step.py
 // BNBWD (dgrad of a layer whose output was globally pooled): the input tensor is that layer's raw conv output y, and the
@@ -105,9 +102,9 @@ __device__ __forceinline__ float ws_elu(float z) {
     return z > 0.f ? z : neg;
 }
 
-template <int CIN, int COUT, bool XFORM, bool STATS, bool M16 = false, bool STAMPS = false, int BNBWD = 0, bool BWDST = false, bool PIN = true,
-          bool ADDIN = false, bool WHOLE = false, int ACT = 0, bool NARROW = false>
-__global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned long long* __restrict__ stamps = nullptr) {
+template <int CIN, int COUT, bool XFORM, bool STATS, bool M16 = false, int BNBWD = 0, bool BWDST = false, bool ADDIN = false, bool WHOLE = false,
+          int ACT = 0, bool NARROW = false>
+__global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a) {
     static_assert(!NARROW || (M16 && COUT == 32 && !BWDST && !ADDIN && !STATS), "NARROW: an input gradient towards a 16-channel (stride) tensor");
     static_assert(ACT == 0 || (!STATS && !BWDST && BNBWD == 0 && !ADDIN), "ACT: plain forward form");
     static_assert(BNBWD != 3 || (!STATS && !BWDST && M16), "BNBWD == 3: no other reduction in the same launch");
@@ -119,23 +116,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
     constexpr int KS = CIN / 16;                       // MFMA k-steps per filter tap
     constexpr int NSTEP = 9 * KS;
     constexpr int XVP = (NPIX * VPP + 255) / 256;      // halo vectors per PRODUCER thread (256 producer threads)
-    unsigned long long ph[4] = {0, 0, 0, 0}, tlast = 0, t_start = 0, rt_start = 0;
-    auto now = [&]() {
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        return t;
-    };
-    auto stamp = [&](int which) {
-        if (STAMPS) {
-            const unsigned long long t = now();
-            if (which >= 0) ph[which] += t - tlast;
-            tlast = t;
-        }
-    };
-    if (STAMPS) {
-        t_start = now();
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_start)::"memory");
-    }
     constexpr int SW_BYTES = 9 * COUT * CIN * 2, SX_BYTES = NPIX * CIN * 2;
     __shared__ __attribute__((aligned(16))) unsigned char smem[SW_BYTES + 2 * SX_BYTES + 4 * 2 * C64 * 4 + C64 * 4];
     hx_t* sW = reinterpret_cast<hx_t*>(smem);
@@ -175,14 +155,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
             if (i < NV) *reinterpret_cast<hx8*>(sW + lrow * CIN + swz<CIN>(lrow, i % VPP) * 8) = wv[k];
         }
     };
-    const bool early_filter = (a.dbg & 128) != 0;   // A/B knob (variant 10): the filter committed before anything else is issued
-    if (early_filter) commit_filter();
 
     // XCD-aware run assignment: workgroups b and b+8 share an XCD (round-robin dispatch), so give XCD x the
     // consecutive runs [x*G/8, (x+1)*G/8): vertically adjacent tile rows then meet in ONE L2 at about the same time
     // and the halo rows they share are fetched from HBM once
     const int G = gridDim.x;
-    const int run = (a.xcd_map && (G & 7) == 0) ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int run = (G & 7) == 0 ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
     const int t_begin = run * a.tiles_per_wg;
     const int t_end = min(a.ntiles, t_begin + a.tiles_per_wg);
     struct TileGeo { int b, ty0, tx0; };
@@ -199,7 +177,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
 
     if (producer) {
         // ================================================================== PRODUCER waves
-        if (a.dbg & 8) __builtin_amdgcn_s_setprio(3);   // A/B knob (variant 3): raising the producers measured 1 % slower
         const int ptid = tid - 256;
         const int vec = ptid % VPP;
         f32x2 sc2[4], sh2[4];
@@ -261,7 +238,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
         const bool last_live = EDGE ? (((ptid + 256 * (XVP - 1 - KMAIN)) >> 3) < 36) : (((ptid + 256 * (XVP - 1)) / VPP) < NPIX);
         // does tile T start with the two columns its predecessor in the run ended with?
         auto reuse_of = [&](int T) {
-            if (!(EDGE && BNBWD < 2 && !(a.dbg & 64) && T > t_begin)) return false;
+            if (!(EDGE && BNBWD < 2 && T > t_begin)) return false;
             const int tt = a.reverse ? t_begin + (t_end - 1 - T) : T;
             const int col = tt - fdiv(tt, a.tilesX, a.mX) * a.tilesX;
             return a.reverse ? col != a.tilesX - 1 : col != 0;
@@ -280,7 +257,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
         auto tile_ptr = [&](const TileGeo& g) { return a.x + ((size_t)(g.b * a.H + g.ty0 - 1) * a.W + (g.tx0 - 1)) * a.ldx; };
         auto image_ptr = [&](const TileGeo& g) { return a.x + (size_t)g.b * a.H * a.W * a.ldx; };
         auto load_tile = [&](const TileGeo& g, hx8 (&d)[XVP], unsigned& okbits, bool reuse) {
-            if (STAMPS && (a.dbg & 4)) { okbits = 0xffffffffu; return; }
             if (is_interior(g)) {
                 const hx_t* xt = tile_ptr(g);
 #pragma unroll
@@ -396,20 +372,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
                 }
             };
             if (t_begin < t_end) load_both(geo(t_begin));
-            if (!early_filter) commit_filter();
+            commit_filter();
             if (t_begin < t_end) put_both(sX0, geo(t_begin));
             __syncthreads();  // filter + first halo tile visible
-            stamp(-1);
             for (int tile = t_begin; tile < t_end; ++tile) {
                 if (tile + 1 < t_end) {
                     const TileGeo g1 = geo(tile + 1);
                     load_both(g1);
                     put_both(sX0 + (((tile - t_begin) & 1) ^ 1) * (NPIX * CIN), g1);
                 }
-                stamp(0);
-                stamp(1);
                 __syncthreads();
-                stamp(2);
             }
             if (BNBWD == 3) {   // lanes l, l + 8, ... of a wave stage the same 8 channels: fold them, one row of 64 sums per producer wave
 #pragma unroll
@@ -427,21 +399,20 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
         unsigned okA = 0, okB = 0;
         if (t_begin < t_end) load_tile(geo(t_begin), dA, okA, false);
         if (t_begin + 1 < t_end) load_tile(geo(t_begin + 1), dB, okB, reuse_of(t_begin + 1));
-        if (!early_filter) commit_filter();
+        commit_filter();
         if (t_begin < t_end) {
             load_gvec(geo(t_begin).b);
 #pragma unroll
             for (int k = 0; k < XVP; ++k) put_one(sX0, k, dA[k], okA);
         }
         __syncthreads();  // filter + first halo tile visible
-        stamp(-1);
         // iteration `tile`: `cur` holds tile+1 (loaded one iteration ago) and is published (transform + LDS write) while
         // the loads of tile+2 go into `nxt`; one load, one vector of VALU work, alternating, so the memory queue is fed
         // at an even pace and never holds the whole burst
         auto iter = [&](int tile, hx8 (&nxt)[XVP], unsigned& oknxt, const hx8 (&cur)[XVP], unsigned okcur) {
             hx_t* sXn = sX0 + (((tile - t_begin) & 1) ^ 1) * (NPIX * CIN);
             const hx_t* sXc = sX0 + ((tile - t_begin) & 1) * (NPIX * CIN);   // the tile the consumers are on: left neighbour of tile+1
-            const bool have_next = tile + 2 < t_end && !(STAMPS && (a.dbg & 4));
+            const bool have_next = tile + 2 < t_end;
             const bool reuse_cur = reuse_of(tile + 1), reuse_nxt = reuse_of(tile + 2);
             if (BNBWD == 1 && tile + 1 < t_end) load_gvec(geo(tile + 1).b);
             if (have_next) {
@@ -486,24 +457,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
                     for (int k = KMAIN; k < XVP; ++k) put_one(sXn, k, cur[k], okcur);
                 }
             }
-            stamp(0);  // loads of tile+2 interleaved with transform + LDS writes of tile+1
-            if (STAMPS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            stamp(1);
             __syncthreads();
-            stamp(2);  // barrier
         };
         for (int tile = t_begin; tile < t_end; tile += 2) {
             iter(tile, dA, okA, dB, okB);
             if (tile + 1 < t_end) iter(tile + 1, dB, okB, dA, okA);
         }
         if (STATS || BWDST) __syncthreads();
-        if (STAMPS && stamps && tid == 256) {
-            unsigned long long rt_end;
-            asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_end)::"memory");
-            unsigned long long* o = stamps + (size_t)blockIdx.x * 16 + 8;
-            o[0] = ph[0]; o[1] = ph[1]; o[2] = ph[2]; o[3] = ph[3];
-            o[4] = now() - t_start; o[5] = rt_end - rt_start;
-        }
         return;
     }
 
@@ -514,7 +474,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
     // fragment mf = 0 then mf = 1 (2 MFMAs per step; the filter fragments are read twice -- the LDS has the room), and
     // while one half accumulates, the finished other half is drained (BatchNorm sums, bf16 pack, stores) in the
     // shadow of the MFMAs, a few instructions per step, so the matrix pipe never waits for an epilogue.
-    if (!early_filter) commit_filter();
+    commit_filter();
     if constexpr (M16) {
         // lane (p, q): pixel column p of the tile row wave*4 + mf; accumulator [mf][nf] register i = channel 16q + 4nf + i
         constexpr int KS2 = CIN / 32, NSTEP2 = 9 * KS2;
@@ -586,7 +546,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
                     // are pure arithmetic, the sched_barriers do not hold them), out of the matrix pipe's shadow
                     // (WHOLE: the sched_group_barrier pairing in pass() does it instead -- the asm's tied operands cost 4 v_mov per channel pair;
                     // measured both ways on both forms: A/B table in DESIGN section 9)
-                    if (PIN && !WHOLE) asm volatile("" : "+v"(s1[2 * j]), "+v"(s1[2 * j + 1]), "+v"(s2[2 * j]), "+v"(s2[2 * j + 1]));
+                    if (!WHOLE) asm volatile("" : "+v"(s1[2 * j]), "+v"(s1[2 * j + 1]), "+v"(s2[2 * j]), "+v"(s2[2 * j + 1]));
                 }
                 float y0 = 0.f, y1 = 0.f;
                 if (BWDST) {   // The gradient LEAVES multiplied by the ReLU mask of the layer it belongs to (gz, not g: every consumer applies
@@ -605,7 +565,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
                     s2[2 * j + 1] = __builtin_fmaf(gz1, y1, s2[2 * j + 1]);
                     // (no pin here: measured 0.4 % slower on the step than the compiler's placement after the pass)
                 }
-            } else if (d[ml].inb && !(STAMPS && (a.dbg & 2))) {
+            } else if (d[ml].inb) {
 #pragma unroll
                 for (int v = 0; v < NPAIR / 4; ++v)
                     *reinterpret_cast<u32x4*>(d[ml].yp + 8 * v) = u32x4{pk[4 * v], pk[4 * v + 1], pk[4 * v + 2], pk[4 * v + 3]};
@@ -617,14 +577,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
             for (int ml = 0; ml < 2; ++ml)
 #pragma unroll
                 for (int nf = 0; nf < NFR; ++nf) acc[2 * half + ml][nf] = *reinterpret_cast<const f32x4*>(sBias + CPL * q + 4 * nf);
-            if (STAMPS && (a.dbg & 1)) {
-                if (drain) {
-                    load_ry(d);
-#pragma unroll
-                    for (int m = 0; m < NDR; ++m) drain_step(m, dh, d);
-                }
-                return;
-            }
             // BWDST: the y values of the half being drained are requested here and first used DS0 K-steps later
             constexpr int DS0 = (BWDST || ADDIN) ? 6 : 0;
             if (drain) load_ry(d);
@@ -655,7 +607,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
                 if (drain) {
 #pragma unroll
                     for (int m = max(sidx - DS0, 0) * NDR / (NSTEP2 - DS0); m < max(sidx + 1 - DS0, 0) * NDR / (NSTEP2 - DS0); ++m) drain_step(m, dh, d);
-                    if (PIN && STATS && WHOLE) {   // one drain instruction behind each of the step's MFMAs
+                    if (STATS && WHOLE) {   // one drain instruction behind each of the step's MFMAs
 #pragma unroll
                         for (int i = 0; i < 2 * NFR; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 1, 0); }
                     }
@@ -664,20 +616,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
             }
         };
         __syncthreads();  // filter + first halo tile visible
-        stamp(-1);
         if (t_begin < t_end) {
             Drain dnone[2];
             dnone[0].yp = a.y; dnone[0].mk = 0.f; dnone[0].inb = false; dnone[1] = dnone[0];
             pass(sX0, 0, false, 0, dnone);
-            stamp(0);
             for (int tile = t_begin; tile < t_end; ++tile) {
                 const TileGeo g = geo(tile);
                 const hx_t* sX = sX0 + ((tile - t_begin) & 1) * (NPIX * CIN);
                 const Drain d0[2] = {drain_of(g, 0), drain_of(g, 1)};
                 pass(sX, 1, true, 0, d0);
-                stamp(1);
                 __syncthreads();  // X[t&1] is free for the producers, X[(t+1)&1] is ready
-                stamp(2);
                 const Drain d1[2] = {drain_of(g, 2), drain_of(g, 3)};
                 if (tile + 1 < t_end) {
                     pass(sX0 + (((tile - t_begin) & 1) ^ 1) * (NPIX * CIN), 0, true, 1, d1);
@@ -686,15 +634,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
 #pragma unroll
                     for (int m = 0; m < NDR; ++m) drain_step(m, 1, d1);
                 }
-                stamp(0);
             }
-        }
-        if (STAMPS && stamps && tid == 0) {
-            unsigned long long rt_end;
-            asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_end)::"memory");
-            unsigned long long* o = stamps + (size_t)blockIdx.x * 16;
-            o[0] = ph[0]; o[1] = ph[1]; o[2] = ph[2]; o[3] = ph[3];
-            o[4] = now() - t_start; o[5] = rt_end - rt_start;
         }
         if (BNBWD == 3) {
             __syncthreads();  // matched by the producers' final barrier: their four rows of channel sums are in sRed
@@ -769,7 +709,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
             }
             const hx2 p2 = HX::pack2(v0, v1);
             pk[j] = __builtin_bit_cast(unsigned, p2);
-        } else if (d.inb && !(STAMPS && (a.dbg & 2))) {
+        } else if (d.inb) {
             *reinterpret_cast<u32x4*>(d.yp + nf * 32) = u32x4{pk[0], pk[1], pk[2], pk[3]};
             *reinterpret_cast<u32x4*>(d.yp + nf * 32 + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
         }
@@ -778,13 +718,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
     auto pass = [&](const hx_t* sX, int mf, bool drain, int dmf, const Drain& d) {
 #pragma unroll
         for (int nf = 0; nf < 2; ++nf) acc[mf][nf] = *reinterpret_cast<const f32x16*>(sBias + nf * 32 + 16 * h);
-        if (STAMPS && (a.dbg & 1)) {
-            if (drain) {
-#pragma unroll
-                for (int m = 0; m < 18; ++m) drain_step(m, dmf, d);
-            }
-            return;
-        }
         constexpr int PF = STATS ? 2 : 3;   // fragment ring: fetched PF-1 steps ahead of use (the statistics take the registers)
         hx8 af[PF], bfr[PF][2];
         auto load_frags = [&](int sidx, int buf) {
@@ -813,19 +746,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
         }
     };
     __syncthreads();  // filter + first halo tile visible
-    stamp(-1);
 
     if (t_begin < t_end) {
         Drain dnone; dnone.yp = a.y; dnone.mk = 0.f; dnone.inb = false;
         pass(sX0, 0, false, 0, dnone);                       // prologue: first half of the first tile
-        stamp(0);
         for (int tile = t_begin; tile < t_end; ++tile) {
             const TileGeo g = geo(tile);
             const hx_t* sX = sX0 + ((tile - t_begin) & 1) * (NPIX * CIN);
             pass(sX, 1, true, 0, drain_of(g, 0));            // second half; drain the first
-            stamp(1);
             __syncthreads();  // X[t&1] is free for the producers, X[(t+1)&1] is ready
-            stamp(2);
             const Drain d1 = drain_of(g, 1);
             if (tile + 1 < t_end) {
                 pass(sX0 + (((tile - t_begin) & 1) ^ 1) * (NPIX * CIN), 0, true, 1, d1);   // next tile's first half; drain the second
@@ -833,15 +762,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
 #pragma unroll
                 for (int m = 0; m < 18; ++m) drain_step(m, 1, d1);
             }
-            stamp(0);
         }
-    }
-    if (STAMPS && stamps && tid == 0) {
-        unsigned long long rt_end;
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_end)::"memory");
-        unsigned long long* o = stamps + (size_t)blockIdx.x * 16;
-        o[0] = ph[0]; o[1] = ph[1]; o[2] = ph[2]; o[3] = ph[3];
-        o[4] = now() - t_start; o[5] = rt_end - rt_start;
     }
     if (STATS) {
         // per-lane partial sums -> per-wave sums over the 32 pixel lanes of each half (xor 1..16 stays inside a half)
@@ -872,40 +793,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a, unsigned l
 
 }  // namespace
 
-#if defined(WM_DEBUG) && !defined(WM_H16_F16)
-// diagnostic entry of the debug build (tools/phase_ws.py): stamps [wgs][16] u64 = consumer {mfma, epilogue, barrier, -, cycles, realtime} at +0,
-// producer {load issue, transform + LDS write, barrier, -, cycles, realtime} at +8
-extern "C" int wm_debug_conv3x3_ws64_phases(const void* x, const void* wp, const float* in_scale, const float* in_shift,
-                                            void* y, float* stat, int B, int H, int W, unsigned long long* stamps, int dbg, void* stream) {
-    WsArgs a;
-    a.dbg = dbg; a.xcd_map = 1;
-    a.x = (const hx_t*)x; a.ldx = 64; a.wp = (const hx_t*)wp; a.bias = nullptr; a.nbias = 0; a.in_scale = in_scale;
-    a.in_shift = in_shift; a.y = (hx_t*)y; a.stat = stat; a.B = B; a.H = H; a.W = W;
-    a.tilesX = wm_cdiv(W, TW); a.tilesY = wm_cdiv(H, TH); a.ntiles = B * a.tilesX * a.tilesY; ws_magic(a);
-    const int wgs = a.ntiles < 256 ? a.ntiles : 256;
-    a.ldy = 64; a.tiles_per_wg = wm_cdiv(a.ntiles, wgs); a.reverse = 0; a.bw_stats4 = nullptr; a.bw_ld = 0; a.bw_coef = nullptr; a.bw_gvec = nullptr; a.ry = nullptr; a.r_scale = nullptr; a.r_shift = nullptr; a.ay = nullptr; a.dy_out = nullptr;
-    const dim3 grid((unsigned)wm_cdiv(a.ntiles, a.tiles_per_wg)), block(512);
-    if (in_scale && stat) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, true, true, false, true>), grid, block, 0, (hipStream_t)stream, a, stamps);
-    else hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, false, true>), grid, block, 0, (hipStream_t)stream, a, stamps);
-    return (int)grid.x;
-}
-#endif
-
 // `sweep_reverse` of the conv / dgrad / wgrad entry points: sweep the tiles backwards.  A kernel that starts where its input's
 // producer stopped finds the freshest part of that tensor in the Infinity Cache (256 MB; a layer's tensor is 134 MB): the host
 // alternates the direction along a chain of layers (engine.py).  Results do not depend on it except for the summation order
 // inside the per-workgroup statistics rows.  (A per-call argument: the library keeps no state between calls.)
+
+// debug build A/B knob -- 1: 32x32x16 MFMA consumers, 11: the masked form for whole-tile shapes too
 #ifndef WM_H16_F16
-WM_KNOB_INT(g_ws_reverse, "WM_WS_REVERSE", -1);   // debug build: -1 follow the caller (default), 0 / 1 force forward / backward sweeps
-WM_KNOB_SETTER(wm_debug_ws_direction, g_ws_reverse)
-int wm_sweep_dir(int reverse) { return (g_ws_reverse == 0 || g_ws_reverse == 1) ? g_ws_reverse : (reverse ? 1 : 0); }
-#else
-int wm_sweep_dir(int reverse);
-#endif
-// debug build A/B knobs -- 1: 32x32x16 MFMA consumers, 2: no XCD-aware run assignment, 3: producers at s_setprio 3, 8: no halo-edge reuse, 9: statistics sums not pinned, 10: filter committed to LDS before the first tile loads are issued, 11: the masked form for whole-tile shapes too
-#ifndef WM_H16_F16
-WM_KNOB_INT(g_ws_variant, "WM_WS_VARIANT", 0);
-WM_KNOB_SETTER(wm_debug_ws_variant, g_ws_variant)
+WM_KNOB(g_ws_variant, wm_debug_ws_variant, 0);
 #else
 static constexpr int g_ws_variant = 0;
 #endif
@@ -919,12 +814,11 @@ int WM_HSYM(wm_launch_conv3x3_ws)(const void* x, int ldx, int Cin, int CoutP, co
                            int act = 0, int ldy = 0) {
     WsArgs a;
     a.ldy = ldy > 0 ? ldy : CoutP;
-    a.dbg = g_ws_variant == 3 ? 8 : (g_ws_variant == 8 ? 64 : (g_ws_variant == 10 ? 128 : 0)); a.xcd_map = g_ws_variant != 2;
     a.x = (const hx_t*)x; a.ldx = ldx; a.wp = (const hx_t*)wp; a.bias = bias; a.nbias = nbias; a.in_scale = in_scale;
     a.in_shift = in_shift; a.y = (hx_t*)y; a.stat = stat; a.B = B; a.H = H; a.W = W;
     a.tilesX = wm_cdiv(W, TW); a.tilesY = wm_cdiv(H, TH); a.ntiles = B * a.tilesX * a.tilesY; ws_magic(a); a.tiles_per_wg = tiles_per_wg;
     if ((long long)a.ntiles * (a.tilesX > a.tilesY ? a.tilesX : a.tilesY) >= (1LL << 32)) return WM_E_SHAPE;   // (the mulhi tile geometry's range)
-    a.reverse = wm_sweep_dir(reverse);
+    a.reverse = reverse ? 1 : 0;
     a.bw_stats4 = bw_stats4; a.bw_ld = bw_ld; a.bw_coef = bw_coef; a.bw_gvec = bw_gvec;
     a.ry = (const hx_t*)ry; a.r_scale = r_scale; a.r_shift = r_shift;
     a.ay = (const hx_t*)ay; a.dy_out = (hx_t*)dy_out;
@@ -932,23 +826,23 @@ int WM_HSYM(wm_launch_conv3x3_ws)(const void* x, int ldx, int Cin, int CoutP, co
     if (addend) {   // forward 64 -> 64 with a second tensor added before the statistics (the encoder's after-concat layer)
         if (Cin != 64 || CoutP != 64 || !in_scale || !stat || ay || ry || bw_stats4) return WM_E_SHAPE;
         a.ry = (const hx_t*)addend;
-        hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, true, true, true, false, 0, false, true, true>), grid, block, 0, s, a, nullptr);
+        hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, true, true, true, 0, false, true>), grid, block, 0, s, a);
         return WM_OK;
     }
     if (act && ay) {   // backward of a conv + ELU layer: x = g, ay = the layer's output, dy_out = gz for the weight gradient, stat = the bias gradient's partial rows
         if (Cin != 64 || (CoutP != 64 && CoutP != 32) || ldx != 64 || in_scale || bw_stats4 || ry || !stat || addend) return WM_E_SHAPE;
         if (CoutP == 32 && a.ldy == 16)   // towards a 16-channel (stride) tensor: the 32-channel consumers, channels 16..31 (zero filter rows) not stored
-            hipLaunchKernelGGL((conv3x3_ws_kernel<64, 32, false, false, true, false, 3, false, true, false, false, 0, true>), grid, block, 0, s, a, nullptr);
+            hipLaunchKernelGGL((conv3x3_ws_kernel<64, 32, false, false, true, 3, false, false, false, 0, true>), grid, block, 0, s, a);
         else if (a.ldy != CoutP) return WM_E_SHAPE;
-        else if (CoutP == 32) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 32, false, false, true, false, 3, false>), grid, block, 0, s, a, nullptr);
-        else hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, false, 3, false>), grid, block, 0, s, a, nullptr);
+        else if (CoutP == 32) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 32, false, false, true, 3, false>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, 3, false>), grid, block, 0, s, a);
         return WM_OK;
     }
     if (act) {   // forward conv + bias + ELU (the pre-activation is not stored)
         if (CoutP != 64 || in_scale || stat || bw_stats4 || ry || addend) return WM_E_SHAPE;
-        if (Cin == 64) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, false, 0, false, true, false, false, 1>), grid, block, 0, s, a, nullptr);
-        else if (Cin == 32) hipLaunchKernelGGL((conv3x3_ws_kernel<32, 64, false, false, true, false, 0, false, true, false, false, 1>), grid, block, 0, s, a, nullptr);
-        else if (Cin == 16) hipLaunchKernelGGL((conv3x3_ws_kernel<16, 64, false, false, false, false, 0, false, true, false, false, 1>), grid, block, 0, s, a, nullptr);
+        if (Cin == 64) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, 0, false, false, false, 1>), grid, block, 0, s, a);
+        else if (Cin == 32) hipLaunchKernelGGL((conv3x3_ws_kernel<32, 64, false, false, true, 0, false, false, false, 1>), grid, block, 0, s, a);
+        else if (Cin == 16) hipLaunchKernelGGL((conv3x3_ws_kernel<16, 64, false, false, false, 0, false, false, false, 1>), grid, block, 0, s, a);
         else return WM_E_SHAPE;
         return WM_OK;
     }
@@ -956,49 +850,45 @@ int WM_HSYM(wm_launch_conv3x3_ws)(const void* x, int ldx, int Cin, int CoutP, co
         if (Cin != 64 || (CoutP != 64 && CoutP != 32) || ldx != 64 || in_scale || !bw_stats4 || !bw_coef || bw_gvec ||
             (ry != nullptr) != (stat != nullptr) || (ry && CoutP != 64))
             return WM_E_SHAPE;
-        if (CoutP == 32) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 32, false, false, true, false, 2, false>), grid, block, 0, s, a, nullptr);   // image-fed layer: dx has 3 (-> 32) channels
-        else if (ry) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, false, 2, true>), grid, block, 0, s, a, nullptr);
-        else hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, false, 2, false>), grid, block, 0, s, a, nullptr);
+        if (CoutP == 32) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 32, false, false, true, 2, false>), grid, block, 0, s, a);   // image-fed layer: dx has 3 (-> 32) channels
+        else if (ry) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, 2, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, 2, false>), grid, block, 0, s, a);
         return WM_OK;
     }
     if (ry) {   // dgrad that also reduces the BatchNorm-backward sums of the layer it feeds
         if (CoutP != 64 || in_scale || !stat || (Cin != 64 && Cin != 32)) return WM_E_SHAPE;
         if (bw_stats4) {
-            if (Cin == 64) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, false, 1, true>), grid, block, 0, s, a, nullptr);
-            else hipLaunchKernelGGL((conv3x3_ws_kernel<32, 64, false, false, true, false, 1, true>), grid, block, 0, s, a, nullptr);
+            if (Cin == 64) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, 1, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((conv3x3_ws_kernel<32, 64, false, false, true, 1, true>), grid, block, 0, s, a);
         } else {
-            if (Cin == 64) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, false, 0, true>), grid, block, 0, s, a, nullptr);
-            else hipLaunchKernelGGL((conv3x3_ws_kernel<32, 64, false, false, true, false, 0, true>), grid, block, 0, s, a, nullptr);
+            if (Cin == 64) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, 0, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((conv3x3_ws_kernel<32, 64, false, false, true, 0, true>), grid, block, 0, s, a);
         }
         return WM_OK;
     }
     if (bw_stats4) {   // dgrad with the BatchNorm-backward apply (per-sample gradient rows) fused: 64 or 32 -> 64
         if ((Cin != 64 && Cin != 32) || CoutP != 64 || in_scale || stat) return WM_E_SHAPE;
-        if (Cin == 64) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, false, 1>), grid, block, 0, s, a, nullptr);
-        else hipLaunchKernelGGL((conv3x3_ws_kernel<32, 64, false, false, true, false, 1>), grid, block, 0, s, a, nullptr);
+        if (Cin == 64) hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, false, false, true, 1>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((conv3x3_ws_kernel<32, 64, false, false, true, 1>), grid, block, 0, s, a);
         return WM_OK;
     }
     const bool xf = in_scale != nullptr, st = stat != nullptr;
-#define WM_WS_LAUNCH2(CIN_, COUT_, M16_)                                                                                     \
-    do {                                                                                                                     \
-        if (xf && st) hipLaunchKernelGGL((conv3x3_ws_kernel<CIN_, COUT_, true, true, M16_>), grid, block, 0, s, a, nullptr);   \
-        else if (xf) hipLaunchKernelGGL((conv3x3_ws_kernel<CIN_, COUT_, true, false, M16_>), grid, block, 0, s, a, nullptr);   \
-        else if (st) hipLaunchKernelGGL((conv3x3_ws_kernel<CIN_, COUT_, false, true, M16_>), grid, block, 0, s, a, nullptr);   \
-        else hipLaunchKernelGGL((conv3x3_ws_kernel<CIN_, COUT_, false, false, M16_>), grid, block, 0, s, a, nullptr);          \
+#define WM_WS_LAUNCH2(CIN_, COUT_, M16_)                                                                          \
+    do {                                                                                                          \
+        if (xf && st) hipLaunchKernelGGL((conv3x3_ws_kernel<CIN_, COUT_, true, true, M16_>), grid, block, 0, s, a); \
+        else if (xf) hipLaunchKernelGGL((conv3x3_ws_kernel<CIN_, COUT_, true, false, M16_>), grid, block, 0, s, a); \
+        else if (st) hipLaunchKernelGGL((conv3x3_ws_kernel<CIN_, COUT_, false, true, M16_>), grid, block, 0, s, a); \
+        else hipLaunchKernelGGL((conv3x3_ws_kernel<CIN_, COUT_, false, false, M16_>), grid, block, 0, s, a);      \
     } while (0)
 #define WM_WS_LAUNCH(CIN_, M16_) WM_WS_LAUNCH2(CIN_, 64, M16_)
     // 16x16x32 consumers by default where Cin allows (-4.5 % on the 64->64 conv in the training step, tools/ab_step.py)
     // whole 16 x 16 tiles (every shape of the benchmarked step): the form without the inside-the-image mask (-1.0 % step time; variant 11 = off)
     if (Cin == 64 && CoutP == 64 && xf && st && g_ws_variant == 0 && H % TH == 0 && W % TW == 0) {
-        hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, true, true, true, false, 0, false, true, false, true>), grid, block, 0, s, a, nullptr);
+        hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, true, true, true, 0, false, false, true>), grid, block, 0, s, a);
         return WM_OK;
     }
     if (Cin == 16 && CoutP == 64 && !xf && st && g_ws_variant == 0 && H % TH == 0 && W % TW == 0) {   // the image-fed first layers' forward
-        hipLaunchKernelGGL((conv3x3_ws_kernel<16, 64, false, true, false, false, 0, false, true, false, true>), grid, block, 0, s, a, nullptr);
-        return WM_OK;
-    }
-    if (g_ws_variant == 9 && Cin == 64 && CoutP == 64 && xf && st) {   // knob 9: the statistics sums left to the compiler's placement
-        hipLaunchKernelGGL((conv3x3_ws_kernel<64, 64, true, true, true, false, 0, false, false>), grid, block, 0, s, a, nullptr);
+        hipLaunchKernelGGL((conv3x3_ws_kernel<16, 64, false, true, false, 0, false, false, true>), grid, block, 0, s, a);
         return WM_OK;
     }
     if (CoutP == 32) WM_WS_LAUNCH2(64, 32, true);

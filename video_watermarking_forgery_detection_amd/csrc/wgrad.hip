@@ -6,20 +6,18 @@
 // network/UNet.py:67-97), with a = x or the fused relu(in_scale*x+in_shift) of the producer.
 //
 // GEMM view per tap: M = Cin, N = Cout, K = B*H*W pixels -- the reduction runs over pixels, the
-// slow index of both NHWC operands, so both MFMA operands need an [k = pixel][row/col = channel]
-// -> k-contiguous transpose.  On gfx950 that is free: ds_read_b64_tr_b16 reads a 4 pixel x 16
-// channel LDS block and hands each lane 4 consecutive pixels of one channel, which is exactly
-// the v_mfma_f32_32x32x16_bf16 operand layout (two reads per 8-deep fragment).
+// slow index of both NHWC operands.  The 16-bit dtypes run on the wave-specialised kernel of
+// wgrad_ws.hip; wgrad_kernel below is the f32 parity path.
 //
-//   workgroup  = 256 threads, loops over 16x16-pixel tiles (grid-stride), one (64 ci x 64 co)
-//                channel block per blockIdx.y; stages the 18x18x64 input halo tile and the
-//                16x16x64 dy tile in LDS per tile
+//   workgroup  = 256 threads, loops over 8x16-pixel tiles (grid-stride), one (64 ci x 64 co)
+//                channel block per blockIdx.y; stages the 10x18x64 input halo tile and the
+//                8x16x64 dy tile in LDS per tile
 //   wave (mi,ni) owns the 32 ci x 32 co block for all 9 taps: 9 accumulators (144 VGPRs) that
-//                live across the whole tile loop; per K step (16 pixels of a tile row) it reads
-//                the dy fragment once and 9 shifted x fragments
+//                live across the whole tile loop; per K step (2 pixels of a tile row) it reads
+//                the dy fragment once and 9 shifted x fragments (v_mfma_f32_32x32x2_f32, plain
+//                ds_read_b32 operands)
 //   epilogue   = f32 slab [9][CinP][CoutP] per workgroup; a second kernel sums the slabs in a
 //                fixed order (deterministic, no float atomics) into the PyTorch-layout gradient.
-//   f32 path   : v_mfma_f32_32x32x2_f32 on 8x16 tiles (parity path; plain ds_read_b32 operands).
 #include <stdlib.h>
 #include <type_traits>
 #include "wm_common.h"
@@ -42,7 +40,7 @@ static inline bool is16(int dtype) { return dtype == WM_BF16 || dtype == WM_F16;
 #define WM_DECL_BWDWS8(sfx)                                                                                                            \
     int wm_launch_bwd_ws8##sfx(const void* g, const void* y, const float* stats4, int st_ld, const float* coef, const void* wpt,     \
                                 const void* xr, const float* in_scale, const float* in_shift, void* dx, float* stat, float* ws, int B, \
-                                int H, int W, int nwg, int reverse, hipStream_t s, int premasked, const float* gvec, int gv_ld, int stamps)
+                                int H, int W, int nwg, int reverse, hipStream_t s, int premasked, const float* gvec, int gv_ld)
 WM_DECL_BWDWS8(_bf16);
 WM_DECL_BWDWS8(_f16);
 // fused input + weight gradient of an image-fed first layer (bwd_ws16.hip), compiled twice
@@ -54,7 +52,7 @@ void wm_launch_bwd_ws16_f16(const void* g, const void* y, const float* stats4, i
 #define WM_DECL_BWDWS(sfx)                                                                                                             \
     void wm_launch_bwd_ws##sfx(const void* g, const void* y, const float* stats4, int st_ld, const float* coef, const void* wpt,      \
                                const void* xr, const float* in_scale, const float* in_shift, void* dx, float* stat, float* ws, int B,  \
-                               int H, int W, int nwg, int reverse, hipStream_t s, int dbg, int premasked, const float* gvec, int gv_ld); \
+                               int H, int W, int nwg, int reverse, hipStream_t s, int premasked, const float* gvec, int gv_ld);      \
     int wm_bwd_ws_gvec_max_batch##sfx()
 WM_DECL_BWDWS(_bf16);
 WM_DECL_BWDWS(_f16);
@@ -67,8 +65,6 @@ constexpr int HW_ = TW + 2;
 constexpr int CB = 64;  // channel block (both ci and co)
 
 template <typename T> struct WCfg;
-template <> struct WCfg<bf16_t> { static constexpr int TH = 16, VE = 8, PS = 72; };   // 144-byte pixel rows
-template <> struct WCfg<f16_t> : WCfg<bf16_t> {};
 template <> struct WCfg<float>  { static constexpr int TH = 8,  VE = 4, PS = 68; };   // 272-byte pixel rows
 
 template <typename T>
@@ -81,16 +77,6 @@ struct WgArgs {
     int tilesX, tilesY, ntiles;
     int ciBlocks, coBlocks;
 };
-
-template <typename T>
-__device__ __forceinline__ typename h16<T>::x8 tr_frag(const T* p0, const T* p1) {
-    typedef short s4 __attribute__((ext_vector_type(4)));
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p0));
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p1));
-    typedef short s8 __attribute__((ext_vector_type(8)));
-    s8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(typename h16<T>::x8, v);
-}
 
 template <typename T, bool XFORM>
 __global__ __launch_bounds__(256, 1) void wgrad_kernel(WgArgs<T> a) {
@@ -225,40 +211,19 @@ __global__ __launch_bounds__(256, 1) void wgrad_kernel(WgArgs<T> a) {
         };
 
         auto mfma_loop = [&](auto steady_tag) {
-            if constexpr (sizeof(T) == 2) {
-                // transposing-read lane geometry: 16-lane group g = lane>>4; lane i = 4q+p of the group
-                const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-                const int chan = 16 * (g & 1) + 4 * p;  // channel offset inside the 32-channel block
-                const int pk = 8 * (g >> 1) + q;        // pixel offset inside the 16-pixel K step (+4 for the 2nd read)
+            // f32 parity path: the loads of the next tile go out as one burst ahead of the loop (a fully
+            // unrolled loop with in-loop slots spills next to 144 accumulator registers)
 #pragma unroll
-                for (int kr = 0; kr < TH; ++kr) {
-                    const T* pd = sD + (kr * TW + pk) * PS + ni * 32 + chan;
-                    const auto bfrag = tr_frag(pd, pd + 4 * PS);
+            for (int sl = 0; sl < NXV + NDV; ++sl) slot(sl, steady_tag);
+            for (int kr = 0; kr < TH; ++kr) {
+                for (int kp = 0; kp < TW / 2; ++kp) {
+                    const int px = 2 * kp + h;
+                    const float bfrag = sD[(kr * TW + px) * PS + ni * 32 + r];
 #pragma unroll
                     for (int tap = 0; tap < 9; ++tap) {
                         const int kh = tap / 3, kw = tap % 3;
-                        const T* px_ = sX + ((kr + kh) * HW_ + pk + kw) * PS + mi * 32 + chan;
-                        const auto afrag = tr_frag(px_, px_ + 4 * PS);
-                        if (tap == 2) slot(2 * kr, steady_tag);
-                        if (tap == 6) slot(2 * kr + 1, steady_tag);
-                        acc[tap] = h16<T>::mfma32(afrag, bfrag, acc[tap]);
-                    }
-                }
-            } else {
-                // f32 parity path: the loads of the next tile go out as one burst ahead of the loop (a fully
-                // unrolled loop with in-loop slots spills next to 144 accumulator registers)
-#pragma unroll
-                for (int sl = 0; sl < NXV + NDV; ++sl) slot(sl, steady_tag);
-                for (int kr = 0; kr < TH; ++kr) {
-                    for (int kp = 0; kp < TW / 2; ++kp) {
-                        const int px = 2 * kp + h;
-                        const float bfrag = sD[(kr * TW + px) * PS + ni * 32 + r];
-#pragma unroll
-                        for (int tap = 0; tap < 9; ++tap) {
-                            const int kh = tap / 3, kw = tap % 3;
-                            const float afrag = sX[((kr + kh) * HW_ + px + kw) * PS + mi * 32 + r];
-                            acc[tap] = __builtin_amdgcn_mfma_f32_32x32x2f32(afrag, bfrag, acc[tap], 0, 0, 0);
-                        }
+                        const float afrag = sX[((kr + kh) * HW_ + px + kw) * PS + mi * 32 + r];
+                        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x2f32(afrag, bfrag, acc[tap], 0, 0, 0);
                     }
                 }
             }
@@ -455,8 +420,7 @@ extern "C" size_t wm_conv3x3_wgrad_ws_bytes(int B, int H, int W, int CinX, int C
 // never materialised -- it is formed from g (gradient wrt the ReLU output), y (raw conv output), the BatchNorm constants
 // stats4 = [scale | shift | mean | invstd] (4 rows of CP) and coef = wm_bn_bwd_finalize's [3][CP] while the tile is staged
 extern "C" int wm_conv3x3_wgrad_bnfused_supported(int CinX, int CoutY, int dtype) {
-    static const bool off = WM_ENV_FLAG("WM_NO_WGRAD_FUSE");
-    return (!off && is16(dtype) && CinX <= 16 && CoutY % 64 == 0) ? 1 : 0;
+    return (is16(dtype) && CinX <= 16 && CoutY % 64 == 0) ? 1 : 0;
 }
 
 extern "C" int wm_conv3x3_wgrad_bnfused(const void* x, int ldx, int CinX, const void* g, int ldg, const void* y, int ldy, int CoutY,
@@ -475,12 +439,10 @@ extern "C" int wm_conv3x3_wgrad_bnfused(const void* x, int ldx, int CinX, const 
     return WM_OK;
 }
 
-WM_KNOB_ON(g_fin_rider, "WM_NO_FIN_RIDER");
-WM_KNOB_SETTER(wm_debug_fin_rider, g_fin_rider)   // A/B knob (tools/ab_step.py, debug build only)
+WM_KNOB(g_fin_rider, wm_debug_fin_rider, 1);   // A/B knob (tools/ab_step.py, debug build only)
 extern "C" int wm_fin_rider_enabled(void) { return g_fin_rider; }
 
-WM_KNOB_ON(g_gv_fuse, "WM_NO_GV_FUSE");
-WM_KNOB_SETTER(wm_debug_gv_fuse, g_gv_fuse)   // A/B knob (tools/ab_step.py, debug build only)
+WM_KNOB(g_gv_fuse, wm_debug_gv_fuse, 1);   // A/B knob (tools/ab_step.py, debug build only)
 
 extern "C" int wm_conv3x3_gvfused_supported(int CinX, int CoutY, int dtype) {
     return (g_gv_fuse && is16(dtype) && CinX == 64 && (CoutY == 64 || CoutY == 32)) ? 1 : 0;
@@ -526,11 +488,8 @@ extern "C" int wm_conv3x3_wgrad_fin(const void* x, int ldx, int CinX, const floa
                "wm_conv3x3_wgrad: bad pixel strides ldx=%d lddy=%d", ldx, lddy);
     WM_REQUIRE(perm_dev || CinX >= Cin, WM_E_BADARG, "wm_conv3x3_wgrad: x has fewer channels than the weight");
     hipStream_t s = (hipStream_t)stream;
-    static const bool v1 = WM_ENV_FLAG("WM_WGRAD_V1");  // diagnostic knob (debug build): single-role kernel
     const int nsl = nslabs_ch(B, H, W, CinX, CoutY);
-    if (is16(dtype) && !v1) wm_launch_wgrad_ws(dtype, x, ldx, CinX, in_scale, in_shift, dy, lddy, CoutY, ws, B, H, W, nsl, s, sweep_reverse ? 1 : 0);
-    else if (dtype == WM_BF16) launch_wgrad<bf16_t>(x, ldx, CinX, in_scale, in_shift, dy, lddy, CoutY, ws, B, H, W, s);
-    else if (dtype == WM_F16) launch_wgrad<f16_t>(x, ldx, CinX, in_scale, in_shift, dy, lddy, CoutY, ws, B, H, W, s);
+    if (is16(dtype)) wm_launch_wgrad_ws(dtype, x, ldx, CinX, in_scale, in_shift, dy, lddy, CoutY, ws, B, H, W, nsl, s, sweep_reverse ? 1 : 0);
     else launch_wgrad<float>(x, ldx, CinX, in_scale, in_shift, dy, lddy, CoutY, ws, B, H, W, s);
     WM_LAUNCH_CHECK("wm_conv3x3_wgrad");
     const int CinP = wm_cdiv(CinX, CB) * CB, CoutP = wm_cdiv(CoutY, CB) * CB;
@@ -569,12 +528,7 @@ extern "C" int wm_conv3x3_wgrad(const void* x, int ldx, int CinX, const float* i
 
 // ---- fused backward of a 64 -> 64 ConvBNRelu body layer (bwd_ws.hip): dx, the feeding layer's BatchNorm-backward partial rows and
 // the weight gradient from one pass over (g, y, the feeding layer's raw output); then the slab reduction (+ an optional rider).
-WM_KNOB_ON(g_bwdfuse, "WM_NO_BWD_FUSE");
-WM_KNOB_SETTER(wm_debug_bwd_fuse, g_bwdfuse)   // A/B knob (tools/ab_step.py, debug build only)
-WM_KNOB_INT(g_bwd_dbg, "WM_BWD_DBG", 0);
-WM_KNOB_SETTER(wm_debug_bwd_variant, g_bwd_dbg)   // phase ablations of bwd_ws.hip (debug build only; results are then meaningless)
-WM_KNOB_ON(g_bwd_split, "WM_NO_BWD_SPLIT");
-WM_KNOB_SETTER(wm_debug_bwd_split, g_bwd_split)   // A/B knob (debug build only): 0 = every form on bwd_ws.hip
+WM_KNOB(g_bwdfuse, wm_debug_bwd_fuse, 1);   // A/B knob (tools/ab_step.py, debug build only)
 extern "C" int wm_conv3x3_bwd_fused_supported(int dtype) { return (g_bwdfuse && is16(dtype)) ? 1 : 0; }
 // ... and the tensor fits the kernel's 32-bit element offsets / 24-bit row and column counts
 // (byte offsets are 32-bit, and the last MB of the range stays free so that a "negative" (wrapped) halo offset lies outside the buffer
@@ -594,7 +548,7 @@ extern "C" int wm_conv3x3_bwd_fused_nwg(int B, int H, int W) {
 extern "C" int wm_conv3x3_bwd_fused_gvec_max_batch(void) { return wm_bwd_ws_gvec_max_batch_bf16(); }
 // whole-tile shapes with a premasked tensor gradient or a per-sample gradient (all 13 launches of the step): the role-split 8-wave form
 static bool bwd_split(int H, int W, int g_premasked, bool has_gvec) {
-    return g_bwd_split && (has_gvec || g_premasked) && H % 8 == 0 && W % 16 == 0 && (g_bwd_dbg == 0 || g_bwd_dbg == (1 << 21));
+    return (has_gvec || g_premasked) && H % 8 == 0 && W % 16 == 0;
 }
 extern "C" int wm_conv3x3_bwd_fused_kernel(int H, int W, int g_premasked, int has_gvec) { return bwd_split(H, W, g_premasked, has_gvec != 0) ? 8 : 1; }
 extern "C" int wm_conv3x3_bwd_fused(const void* g, const float* gvec, const void* y, const float* stats4, const float* coef, const void* wpt,
@@ -612,22 +566,19 @@ extern "C" int wm_conv3x3_bwd_fused(const void* g, const float* gvec, const void
     hipStream_t s = (hipStream_t)stream;
     const int nwg = wm_conv3x3_bwd_fused_nwg(B, H, W);
     const bool split = bwd_split(H, W, g_premasked, gvec != nullptr);
-    const int stamps = g_bwd_dbg == (1 << 21);   // debug build: tools/phase_bwd8.py
     if (split) {
         const int rc8 = dtype == WM_F16
-            ? wm_launch_bwd_ws8_f16(g, y, stats4, 64, coef, wpt, xr, in_scale, in_shift, dx, partials, ws, B, H, W, nwg, sweep_reverse ? 1 : 0, s, g_premasked, gvec, 64, stamps)
-            : wm_launch_bwd_ws8_bf16(g, y, stats4, 64, coef, wpt, xr, in_scale, in_shift, dx, partials, ws, B, H, W, nwg, sweep_reverse ? 1 : 0, s, g_premasked, gvec, 64, stamps);
+            ? wm_launch_bwd_ws8_f16(g, y, stats4, 64, coef, wpt, xr, in_scale, in_shift, dx, partials, ws, B, H, W, nwg, sweep_reverse ? 1 : 0, s, g_premasked, gvec, 64)
+            : wm_launch_bwd_ws8_bf16(g, y, stats4, 64, coef, wpt, xr, in_scale, in_shift, dx, partials, ws, B, H, W, nwg, sweep_reverse ? 1 : 0, s, g_premasked, gvec, 64);
         WM_REQUIRE(rc8 == WM_OK, rc8, "wm_conv3x3_bwd_fused: the role-split kernel takes a premasked tensor gradient or a per-sample gradient only");
-    } else if (dtype == WM_F16) wm_launch_bwd_ws_f16(g, y, stats4, 64, coef, wpt, xr, in_scale, in_shift, dx, partials, ws, B, H, W, nwg, sweep_reverse ? 1 : 0, s, g_bwd_dbg, g_premasked, gvec, 64);
-    else wm_launch_bwd_ws_bf16(g, y, stats4, 64, coef, wpt, xr, in_scale, in_shift, dx, partials, ws, B, H, W, nwg, sweep_reverse ? 1 : 0, s, g_bwd_dbg, g_premasked, gvec, 64);
+    } else if (dtype == WM_F16) wm_launch_bwd_ws_f16(g, y, stats4, 64, coef, wpt, xr, in_scale, in_shift, dx, partials, ws, B, H, W, nwg, sweep_reverse ? 1 : 0, s, g_premasked, gvec, 64);
+    else wm_launch_bwd_ws_bf16(g, y, stats4, 64, coef, wpt, xr, in_scale, in_shift, dx, partials, ws, B, H, W, nwg, sweep_reverse ? 1 : 0, s, g_premasked, gvec, 64);
     WM_LAUNCH_CHECK("wm_conv3x3_bwd_fused");
     return WM_OK;
 }
 // ---- the image-fed first layer in one pass (bwd_ws16.hip): input gradient wrt the 16-channel image tensor + weight gradient
-WM_KNOB_ON(g_bwdfuse16, "WM_NO_BWD_FUSE16");
-WM_KNOB_SETTER(wm_debug_bwd_fuse16, g_bwdfuse16)   // A/B knob (debug build only)
 extern "C" int wm_conv3x3_bwd_fused16_supported(int B, int H, int W, int dtype) {
-    return (g_bwdfuse16 && is16(dtype) && B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 16 == 0 &&
+    return (is16(dtype) && B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 16 == 0 &&
             (long long)B * H * W * 64 <= (1LL << 31) - (1LL << 19)) ? 1 : 0;
 }
 extern "C" int wm_conv3x3_bwd_fused16_nwg(int B, int H, int W) {

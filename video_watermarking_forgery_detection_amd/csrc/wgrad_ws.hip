@@ -22,8 +22,6 @@ typedef h16<hx_t> HX;
 typedef HX::x8 hx8;
 typedef HX::x2 hx2;
 
-int wm_sweep_dir(int reverse);   // conv3x3_ws.hip
-
 namespace {
 
 constexpr int TH = 16, TW = 16, HH = 18, HW = 18, CB = 64;
@@ -366,7 +364,7 @@ void WM_HSYM(wm_launch_wgrad_ws)(const void* x, int ldx, int CinX, const float* 
     a.bscale = bstats4; a.bshift = bstats4 ? bstats4 + bstats_ld : nullptr; a.bmean = bstats4 ? bstats4 + 2 * bstats_ld : nullptr;
     a.binvstd = bstats4 ? bstats4 + 3 * bstats_ld : nullptr; a.bcoef = bcoef; a.gvec = gvec; a.ldgv = bstats_ld;
     a.tilesX = wm_cdiv(W, TW); a.tilesY = wm_cdiv(H, TH); a.ntiles = B * a.tilesX * a.tilesY;
-    a.reverse = wm_sweep_dir(reverse);
+    a.reverse = reverse ? 1 : 0;
     a.ciBlocks = wm_cdiv(CinX, CB); a.coBlocks = wm_cdiv(CoutY, CB);
     const dim3 block(512);
     if (CinX <= 16) {   // one 16-channel input block; the slab keeps its 64-row pitch (rows >= 16 are never read back)

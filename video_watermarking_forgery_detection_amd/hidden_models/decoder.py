@@ -21,7 +21,7 @@ def stack_fwd(blocks, image, dt, training):
     for blk in blocks:
         a, cx = engine.cbr_forward(blk.layers[0], blk.layers[1], a, dt, training=training)
         ctx.layers.append(cx)
-    if training and ops.pool_stats_enabled():
+    if training:
         ctx.pooled, ctx.pool_stats = ops.bnrelu_avgpool_stats(a.t, a.scale, a.shift)
     else:
         ctx.pooled, ctx.pool_stats = ops.bnrelu_avgpool(a.t, a.scale, a.shift), None

@@ -749,10 +749,6 @@ def conv3x3_wgrad_bias(x, gz, dw, accumulate, bias_partials, db, db_accumulate):
 
 
 # ----------------------------------------------------------------------------- heads
-def pool_stats_enabled():
-    return bool(_lib.lib().wm_pool_stats_enabled())
-
-
 def bnrelu_avgpool_stats(y, scale, shift):
     """global average pool of relu(scale*y+shift) plus, per (sample, channel), the active-pixel count N+ and the sum S+ of y over
     the active pixels.  Returns (pooled [B,CP], (N+ [B,CP], S+ [B,CP]))."""
