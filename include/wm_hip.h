@@ -461,13 +461,16 @@ int wm_adam_step(float* p, const float* g, float* m, float* v, size_t n, float l
                  float beta2, float eps, float weight_decay, int decoupled, int step, float grad_scale,
                  void* stream);
 /* The same step for a hipGraph-captured training step (a Python step per batch per rank, /root/reference/train.py:99-109, replayed
- * instead of re-enqueued): the two step-count-dependent constants come from DEVICE memory instead of the argument list.
- * wm_adam_hyper (host, no launch): out2 = {lr / (1 - beta1^step), sqrt(1 - beta2^step)} -- exactly the values wm_adam_step derives;
- * wm_adam_step_dev reads them from hyper_dev (device float[2]), which the caller refreshes before each replay: bit-identical
- * to wm_adam_step(step). */
-int wm_adam_hyper(float lr, float beta1, float beta2, int step, float* out2);
-int wm_adam_step_dev(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
-                     float weight_decay, int decoupled, const float* hyper_dev, float grad_scale, void* stream);
+ * instead of re-enqueued): every number that may change between replays -- the step-count-dependent constants and the hyperparameters
+ * a scheduler or a loaded state_dict changes -- comes from DEVICE memory instead of the argument list.
+ * wm_adam_hyper (host, no launch): out[WM_ADAM_HYPER] = {lr / (1 - beta1^step), sqrt(1 - beta2^step), lr, beta1, beta2, eps,
+ * weight_decay, 0} -- the first two exactly the values wm_adam_step derives; wm_adam_step_dev reads the block from hyper_dev
+ * (device float[WM_ADAM_HYPER]), which the caller refreshes before each replay: bit-identical to wm_adam_step(step).  Only
+ * `decoupled`, which selects a code path, stays a launch argument. */
+#define WM_ADAM_HYPER 8
+int wm_adam_hyper(float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* out);
+int wm_adam_step_dev(float* p, const float* g, float* m, float* v, size_t n, int decoupled, const float* hyper_dev, float grad_scale,
+                     void* stream);
 /* sum of squares partials (clip_grad_norm_) */
 /* nn.Linear after the global average pool (hidden_models/decoder.py:26,32-34, discriminator.py:18,24-26), B ~ 16, I,O <= 64:
  * fwd: out[B,O] = pooled[:, :I] @ w[O,I]^T + bias.
@@ -508,15 +511,21 @@ int wm_sumsq(const float* x, size_t n, float* partials, int nparts, void* stream
  * state: f32[WM_AMP_STATE] device array = [0] loss scale, [1] growth tracker, [2] growth_factor, [3] backoff_factor,
  * [4] growth_interval, [8+k] found_inf of optimiser k, [12+k] step count of optimiser k (k < 4).  The loss kernels take &state[0]
  * as gscale_dev, so every gradient of the backward is multiplied by the scale; then, per optimiser,
- *   wm_amp_found_inf : found_inf[k] = !isfinite(sum of its wm_sumsq rows)       (GradScaler.unscale_'s inf check)
+ *   wm_nonfinite     : partials[nparts] = per block, 1 if any of its elements of x is inf / nan, else 0
+ *   wm_amp_found_inf : found_inf[k] = any of its wm_nonfinite rows != 0         (GradScaler.unscale_'s per-element inf check; a finite
+ *                      gradient whose square overflows f32 is stepped, as torch steps it)
  *   wm_adam_step_amp : the Adam step on g / scale, skipped when found_inf[k]; bias corrections from the device step count,
- *                      which a skipped step does not advance (like torch's per-parameter `step`)
+ *                      which a skipped step does not advance (like torch's per-parameter `step`).  hyper_dev (may be NULL: the
+ *                      arguments hold): a wm_adam_hyper block whose lr, beta1, beta2, eps and weight_decay replace the arguments
+ *                      (a captured step); its two step-count-dependent entries are not read
  * and once per iteration wm_amp_update: GradScaler.update() (backoff on any inf, growth after growth_interval clean iterations),
  * advances the step counts of the optimisers that stepped and clears the flags.  No host synchronisation anywhere. */
 #define WM_AMP_STATE 16
-int wm_amp_found_inf(const float* const* sumsq_partials, const int* nparts, int ngroups, float* state, int k, void* stream);
+int wm_nonfinite(const float* x, size_t n, float* partials, int nparts, void* stream);
+int wm_amp_found_inf(const float* const* nonfinite_partials, const int* nparts, int ngroups, float* state, int k, void* stream);
 int wm_adam_step_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
-                     float weight_decay, int decoupled, float grad_scale, const float* amp_state, int k, void* stream);
+                     float weight_decay, int decoupled, float grad_scale, const float* amp_state, int k, const float* hyper_dev,
+                     void* stream);
 int wm_amp_update(float* state, int noptimizers, void* stream);
 
 /* ------------------------------------------------------------------ tamper-localisation branch (elementwise, f32 NCHW planes)
@@ -535,7 +544,7 @@ int wm_amp_update(float* state, int noptimizers, void* stream);
  * wm_masked_axpy: a += g * (1 - mask) (the splice's backward onto the gradient of the encoded image).
  * wm_mask_threshold: out[i] = p[i] > threshold (uint8 tamper mask).
  * wm_clip_coef: partials[k][nparts[k]] = wm_sumsq rows of up to 4 flat gradient buffers clipped TOGETHER;
- *   out2[0] = min(1, max_norm / (total_norm + 1e-6)), out2[1] = total_norm.   wm_scale_dev: x *= scale_dev[0]. */
+ *   out2[0] = min(1, max_norm / (total_norm + 1e-6)), out2[1] = total_norm; a nan norm gives a nan coefficient, as torch.clamp does.   wm_scale_dev: x *= scale_dev[0]. */
 int wm_clamp_quant_fwd(const float* x, float* y, size_t n, void* stream);
 int wm_splice_nparts(size_t n);
 int wm_splice_fwd(const float* enc, const float* real, const float* prev, const float* mask, float* fwd_q, float* tampered,

@@ -378,3 +378,112 @@ def test_two_chain_training_under_a_differentiable_jpeg_is_the_one_stream_run():
         got = run(True)
         for k in ref:
             assert torch.equal(ref[k], got[k]), (r, k)
+
+
+def _change(kind, i, models, decoupled):
+    """step i's change of one optimiser setting, made on both models the same way (the eager one first: its state is the one loaded)"""
+    opts = [(h.optimizer_discrim, h.optimizer_enc_dec) for h in models]
+    if kind == "lr":                 # BaseModel.update_learning_rate under a warm-up: a new lr every step
+        for pair in opts:
+            for o in pair:
+                o.param_groups[0]["lr"] = o.param_groups[0]["initial_lr"] / 8 * (i + 1)
+        return
+    if i < 3:                        # the others change between replays only: the capture is at call 3 (i == 2)
+        return
+    new = {"betas": [(0.8, 0.99), (0.85, 0.995), (0.5, 0.9)], "eps": [1e-3, 1e-6, 1e-4], "weight_decay": [0.0, 0.02, 0.1]}
+    if kind in new:
+        for pair in opts:
+            for o in pair:
+                o.param_groups[0][kind] = new[kind][i - 3]
+        return
+    # a torch.optim.AdamW (Adam for the coupled case) state_dict with other hyperparameters, loaded on resume
+    cls = torch.optim.AdamW if decoupled else torch.optim.Adam
+    for j in range(2):
+        src = opts[0][j]
+        params = [p.detach().cpu().clone().requires_grad_(True) for p in src._params()]
+        t = cls(params, lr=2e-3 * i, betas=(0.7, 0.98), eps=1e-5 * i, weight_decay=0.01 * i)
+        t.load_state_dict({**src.state_dict(), "param_groups": [{**t.state_dict()["param_groups"][0]}]})
+        sd = t.state_dict()
+        assert sd["param_groups"][0]["decoupled_weight_decay"] == decoupled and sd["state"]
+        for pair in opts:
+            pair[j].load_state_dict(sd)
+
+
+@pytest.mark.parametrize("change", ["lr", "betas", "eps", "weight_decay", "state_dict"])
+@pytest.mark.parametrize("decoupled", [False, True], ids=["Adam", "AdamW"])
+@pytest.mark.parametrize("dt", ["f32", "bf16", "f16-amp"])
+def test_replayed_steps_follow_optimiser_changes_bit_for_bit(dt, decoupled, change):
+    """A captured step reads every optimiser number that may change between replays from device memory: the learning rate of a warm-up
+    (every step), new betas, eps or weight decay, a loaded torch state_dict -- on both models between the replays, and every weight, flat
+    gradient, moment and step count stays equal to the eagerly enqueued model's after every step.  (The decoupled decay once used the
+    capture-time lr; betas, eps and weight decay were frozen at capture.)  Under the scaler the graph count does not grow with the number of
+    learning rates."""
+    from video_watermarking_forgery_detection_amd import noise_layers as NL, ops
+    dtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16-amp": torch.float16}[dt]
+    S, B = (32, 2) if dt == "f32" else (64, 2)
+
+    def make():
+        from video_watermarking_forgery_detection_amd.hidden_models import Hidden
+        from video_watermarking_forgery_detection_amd.options import HiDDenConfiguration
+        amp = ops.AmpState(torch.device("cuda")) if dt == "f16-amp" else None
+        h = Hidden(HiDDenConfiguration(H=S, W=S), torch.device("cuda"), NL.JpegSS(50), None, compute_dtype=dtype, amp=amp)
+        for m in (h.encoder_decoder.encoder, h.encoder_decoder.decoder, h.discriminator):
+            detgen.fill_module(m)
+        for o in (h.optimizer_discrim, h.optimizer_enc_dec):
+            o.param_groups[0].update(lr=2e-3, initial_lr=2e-3, weight_decay=0.05)
+            o.decoupled = decoupled
+        return h
+
+    eager, graph = make(), make().enable_graph()
+    NSTEP = 6
+    for i in range(NSTEP):
+        _change(change, i, (eager, graph), decoupled)
+        images = detgen.uniform((B, 3, S, S), 8000 + i).cuda()
+        messages = detgen.bits((B, 30), 8100 + i).cuda()
+        le, _ = eager.train_on_batch([images, messages])
+        lg, _ = graph.train_on_batch([images, messages])
+        assert dict(le) == dict(lg), (i, dict(le), dict(lg))
+        se, sg = _state(eager), _state(graph)
+        for k in se:
+            assert torch.equal(se[k], sg[k]), (i, k)
+        if eager.amp is not None:
+            assert torch.equal(eager.amp.state, graph.amp.state), i
+    (g,) = graph._graphs.values()                      # one graph for every lr / beta / eps / weight decay the run went through
+    assert g.graph is not None and g.calls == NSTEP
+
+
+def test_model_surface_adamw_warmup_replayed_equals_eager(tmp_path):
+    """IRNrhiModel with train.adamw and weight_decay_G, update_learning_rate(step, warmup_iter) every step (the reference's loop,
+    train.py:99-109): train.graph against train.graph false, every logged scalar and all optimiser state equal"""
+    from video_watermarking_forgery_detection_amd.models.IRNrhi_model import IRNrhiModel
+    from video_watermarking_forgery_detection_amd.options.options import dict_to_nonedict
+
+    def make(graph):
+        opt = dict_to_nonedict({"gpu_ids": [0], "dist": False, "is_train": True, "datasets": {"train": {"GT_size": 64, "batch_size": 4}},
+                                "train": {"compute_dtype": "bf16", "attacks": ["Jpeg50", "GaussianBlur"], "lr_G": 1e-3, "manual_seed": 10,
+                                          "save_interval": 3000, "localizer": False, "graph": graph, "adamw": True, "weight_decay_G": 0.01},
+                                "path": {"models": str(tmp_path / "models"), "training_state": str(tmp_path / "state")}})
+        m = IRNrhiModel(opt)
+        for net in (m.netG.encoder, m.netG.decoder, m.discriminator):
+            detgen.fill_module(net)
+        return m
+
+    eager, graph = make(False), make(True)
+    assert graph.hidden._graphs is not None and graph.hidden.optimizer_enc_dec.decoupled
+    for step in range(1, 13):
+        x = detgen.uniform((4, 3, 64, 64), 300 + step)
+        msg = (detgen.uniform((4, 30), 700 + step) > 0.5).float().cuda()
+        out = []
+        for m in (eager, graph):
+            m.update_learning_rate(step, warmup_iter=50)
+            m.feed_data(x)
+            m.messages = msg
+            logs, _ = m.optimize_parameters(step, None)
+            out.append(logs)
+        assert out[0] == out[1], (step, out[0], out[1])
+    assert eager.get_current_learning_rate() == graph.get_current_learning_rate() == 1e-3 / 50 * 12
+    g = graph.hidden._graphs
+    assert len(g) == 2 and all(v.graph is not None for v in g.values())
+    a, b = _state(eager.hidden), _state(graph.hidden)
+    for k in a:
+        assert torch.equal(a[k], b[k]), k

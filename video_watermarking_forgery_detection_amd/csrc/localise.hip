@@ -130,7 +130,8 @@ __global__ __launch_bounds__(256) void mask_threshold_kernel(const float* __rest
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = p[i] > thr ? 1 : 0;
 }
 
-// clip_grad_norm_(params, max_norm): total = sqrt(sum of all squares); coef = min(1, max_norm / (total + 1e-6))
+// clip_grad_norm_(params, max_norm): total = sqrt(sum of all squares); coef = min(1, max_norm / (total + 1e-6)) as torch.clamp(max=1) takes it:
+// an inf total gives 0, a nan total a nan coefficient (which then turns every gradient into nan, as torch's clipping does)
 struct ClipGroups { const float* parts[4]; int n[4]; };
 __global__ void clip_coef_kernel(ClipGroups g, int ngroups, float max_norm, float* __restrict__ out) {
     __shared__ double s[256];
@@ -146,7 +147,7 @@ __global__ void clip_coef_kernel(ClipGroups g, int ngroups, float max_norm, floa
     if (threadIdx.x == 0) {
         const float total = sqrtf((float)s[0]);
         const float coef = max_norm / (total + 1e-6f);
-        out[0] = coef < 1.f ? coef : 1.f;
+        out[0] = coef > 1.f ? 1.f : coef;
         out[1] = total;
     }
 }

@@ -117,54 +117,60 @@ __global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ a, const 
 //   g += wd*p (coupled)  |  p *= 1 - lr*wd (decoupled)
 //   m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g
 //   denom = sqrt(v)/sqrt(1-b2^t) + eps ; p -= (lr/(1-b1^t)) * m/denom
+// The numbers of one step; step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t)
+struct AdamHyper { float lr, b1, b2, eps, wd, step_size, bc2_sqrt; };
+
+// the step over a flat buffer (grid-stride: elements i0, i0 + stride, ...), shared by the three kernels below: eager, replayed and scaled
+// steps run the same arithmetic.  (The kernels pass i0 / stride: blockDim read inside a non-kernel function costs an extra load.)
+__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                          size_t n, size_t i0, size_t stride, const AdamHyper h, int decoupled, float grad_scale) {
+    for (size_t i = i0; i < n; i += stride) {
+        float gg = g[i] * grad_scale;
+        float pp = p[i];
+        if (h.wd != 0.f) {
+            if (decoupled) pp *= 1.f - h.lr * h.wd;
+            else gg += h.wd * pp;
+        }
+        const float mm = h.b1 * m[i] + (1.f - h.b1) * gg;
+        const float vv = h.b2 * v[i] + (1.f - h.b2) * gg * gg;
+        m[i] = mm;
+        v[i] = vv;
+        const float denom = sqrtf(vv) / h.bc2_sqrt + h.eps;
+        p[i] = pp - h.step_size * (mm / denom);
+    }
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
                                                    float wd, int decoupled, float step_size, float bc2_sqrt,
                                                    float grad_scale) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float gg = g[i] * grad_scale;
-        float pp = p[i];
-        if (wd != 0.f) {
-            if (decoupled) pp *= 1.f - lr * wd;
-            else gg += wd * pp;
-        }
-        const float mm = b1 * m[i] + (1.f - b1) * gg;
-        const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-        m[i] = mm;
-        v[i] = vv;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        p[i] = pp - step_size * (mm / denom);
-    }
+    adam_body(p, g, m, v, n, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x,
+              AdamHyper{lr, b1, b2, eps, wd, step_size, bc2_sqrt}, decoupled, grad_scale);
 }
 
-// the same step with its two step-count-dependent constants read from DEVICE memory (hyper = {lr / (1 - b1^t), sqrt(1 - b2^t)}, the values
-// wm_adam_hyper computes on the host): a step captured into a hipGraph replays with the constants of the CURRENT step count -- the host
-// refreshes the two floats before each replay -- and is bit-identical to wm_adam_step
+// the same step with every number that may change between the replays of a captured step read from DEVICE memory (hyper: the
+// WM_ADAM_HYPER floats wm_adam_hyper writes on the host, which the graph's owner refreshes before each replay): bit-identical to wm_adam_step
 __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
-                                                       float wd, int decoupled, const float* __restrict__ hyper, float grad_scale) {
-    const float step_size = hyper[0], bc2_sqrt = hyper[1];
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float gg = g[i] * grad_scale;
-        float pp = p[i];
-        if (wd != 0.f) {
-            if (decoupled) pp *= 1.f - lr * wd;
-            else gg += wd * pp;
-        }
-        const float mm = b1 * m[i] + (1.f - b1) * gg;
-        const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-        m[i] = mm;
-        v[i] = vv;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        p[i] = pp - step_size * (mm / denom);
-    }
+                                                       float* __restrict__ v, size_t n, int decoupled, const float* __restrict__ hyper,
+                                                       float grad_scale) {
+    adam_body(p, g, m, v, n, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x,
+              AdamHyper{hyper[2], hyper[3], hyper[4], hyper[5], hyper[6], hyper[0], hyper[1]}, decoupled, grad_scale);
 }
 
 // ---- torch.cuda.amp.GradScaler (models/IRNcrop_model.py:143,407-416) kept on the device.  state (f32[WM_AMP_STATE]):
 //   [0] scale  [1] growth tracker  [2] growth_factor  [3] backoff_factor  [4] growth_interval
 //   [8 + k] found_inf of optimiser k (k < 4)   [12 + k] step count of optimiser k (torch's `step`: not advanced by a skipped step)
-// found_inf[k] = !isfinite(sum of squares of optimiser k's gradients) -- the rows wm_sumsq wrote (shared with clip_grad_norm_)
+// found_inf[k] = any element of optimiser k's gradients is inf / nan: the rows wm_nonfinite wrote (per block: 1 if it saw one, else 0).
+// (Not the sum of squares: a finite gradient beyond 1.8e19 squares to inf, and GradScaler checks elements, not their squares.)
 struct AmpGroups { const float* parts[4]; int n[4]; };
+
+__global__ __launch_bounds__(256) void nonfinite_kernel(const float* __restrict__ x, float* __restrict__ partials, size_t n) {
+    int bad = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) bad |= !isfinite(x[i]);
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) partials[blockIdx.x] = bad ? 1.f : 0.f;
+}
+
 __global__ void amp_found_inf_kernel(AmpGroups g, int ngroups, float* __restrict__ state, int k) {
     __shared__ float s[256];
     float a = 0.f;
@@ -176,7 +182,7 @@ __global__ void amp_found_inf_kernel(AmpGroups g, int ngroups, float* __restrict
         if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) state[8 + k] = isfinite(s[0]) ? 0.f : 1.f;
+    if (threadIdx.x == 0) state[8 + k] = s[0] != 0.f ? 1.f : 0.f;
 }
 
 // GradScaler.update(): any found_inf -> scale *= backoff, tracker = 0; else tracker += 1 and at growth_interval scale *= growth.
@@ -196,29 +202,20 @@ __global__ void amp_update_kernel(float* __restrict__ state, int nopt) {
     }
 }
 
-// Adam / AdamW under the scaler: the gradients in g are still multiplied by state[0]; skipped entirely when found_inf[k]
+// Adam / AdamW under the scaler: the gradients in g are still multiplied by state[0]; skipped entirely when found_inf[k].  hyper (may be NULL:
+// then the launch arguments hold) = wm_adam_hyper's block, of which the kernel reads lr, beta1, beta2, eps and weight_decay: a captured
+// step takes the values of the current replay from there (the bias corrections come from the device step count, not from hyper[0..1])
 __global__ __launch_bounds__(256) void adam_amp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps, float wd,
-                                                       int decoupled, float grad_scale, const float* __restrict__ state, int k) {
+                                                       int decoupled, float grad_scale, const float* __restrict__ state, int k,
+                                                       const float* __restrict__ hyper) {
     if (state[8 + k] != 0.f) return;
+    if (hyper) { lr = hyper[2]; b1 = hyper[3]; b2 = hyper[4]; eps = hyper[5]; wd = hyper[6]; }
     const float t = state[12 + k] + 1.f;
     const float bc1 = 1.f - powf(b1, t), bc2_sqrt = sqrtf(1.f - powf(b2, t));
     const float step_size = lr / bc1;
-    const float gs = grad_scale / state[0];
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float gg = g[i] * gs;
-        float pp = p[i];
-        if (wd != 0.f) {
-            if (decoupled) pp *= 1.f - lr * wd;
-            else gg += wd * pp;
-        }
-        const float mm = b1 * m[i] + (1.f - b1) * gg;
-        const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-        m[i] = mm;
-        v[i] = vv;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        p[i] = pp - step_size * (mm / denom);
-    }
+    adam_body(p, g, m, v, n, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x,
+              AdamHyper{lr, b1, b2, eps, wd, step_size, bc2_sqrt}, decoupled, grad_scale / state[0]);
 }
 
 inline int grid_for(size_t n, int cap = 2048) {
@@ -311,40 +308,46 @@ extern "C" int wm_axpy(float* a, const float* b, float s, size_t n, void* stream
     return WM_OK;
 }
 
-extern "C" int wm_adam_hyper(float lr, float beta1, float beta2, int step, float* out2) {
-    WM_REQUIRE(out2 && step >= 1, WM_E_BADARG, "wm_adam_hyper: bad arguments");
+extern "C" int wm_adam_hyper(float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* out) {
+    WM_REQUIRE(out && step >= 1, WM_E_BADARG, "wm_adam_hyper: bad arguments");
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    out2[0] = (float)((double)lr / bc1);
-    out2[1] = (float)sqrt(bc2);
+    out[0] = (float)((double)lr / bc1);
+    out[1] = (float)sqrt(bc2);
+    out[2] = lr; out[3] = beta1; out[4] = beta2; out[5] = eps; out[6] = weight_decay; out[7] = 0.f;
     return WM_OK;
 }
 
 extern "C" int wm_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                             float eps, float weight_decay, int decoupled, int step, float grad_scale, void* stream) {
     WM_REQUIRE(p && g && m && v && n > 0 && step >= 1, WM_E_BADARG, "wm_adam_step: bad arguments");
-    float hy[2];
-    wm_adam_hyper(lr, beta1, beta2, step, hy);
+    float hy[WM_ADAM_HYPER];
+    wm_adam_hyper(lr, beta1, beta2, eps, weight_decay, step, hy);
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
                        weight_decay, decoupled, hy[0], hy[1], grad_scale);
     WM_LAUNCH_CHECK("wm_adam_step");
     return WM_OK;
 }
 
-extern "C" int wm_adam_step_dev(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
-                                float weight_decay, int decoupled, const float* hyper_dev, float grad_scale, void* stream) {
+extern "C" int wm_adam_step_dev(float* p, const float* g, float* m, float* v, size_t n, int decoupled, const float* hyper_dev, float grad_scale,
+                                void* stream) {
     WM_REQUIRE(p && g && m && v && hyper_dev && n > 0, WM_E_BADARG, "wm_adam_step_dev: bad arguments");
-    hipLaunchKernelGGL(adam_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
-                       weight_decay, decoupled, hyper_dev, grad_scale);
+    hipLaunchKernelGGL(adam_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, decoupled, hyper_dev, grad_scale);
     WM_LAUNCH_CHECK("wm_adam_step_dev");
     return WM_OK;
 }
 
+extern "C" int wm_nonfinite(const float* x, size_t n, float* partials, int nparts, void* stream) {
+    WM_REQUIRE(x && partials && n > 0 && nparts > 0 && nparts <= 2048, WM_E_BADARG, "wm_nonfinite: bad arguments");
+    hipLaunchKernelGGL(nonfinite_kernel, dim3(nparts), dim3(256), 0, (hipStream_t)stream, x, partials, n);
+    WM_LAUNCH_CHECK("wm_nonfinite");
+    return WM_OK;
+}
 
-extern "C" int wm_amp_found_inf(const float* const* sumsq_partials, const int* nparts, int ngroups, float* state, int k, void* stream) {
-    WM_REQUIRE(sumsq_partials && nparts && state && ngroups >= 1 && ngroups <= 4 && k >= 0 && k < 4, WM_E_BADARG, "wm_amp_found_inf: bad arguments");
+extern "C" int wm_amp_found_inf(const float* const* nonfinite_partials, const int* nparts, int ngroups, float* state, int k, void* stream) {
+    WM_REQUIRE(nonfinite_partials && nparts && state && ngroups >= 1 && ngroups <= 4 && k >= 0 && k < 4, WM_E_BADARG, "wm_amp_found_inf: bad arguments");
     AmpGroups g;
-    for (int q = 0; q < 4; ++q) { g.parts[q] = q < ngroups ? sumsq_partials[q] : nullptr; g.n[q] = q < ngroups ? nparts[q] : 0; }
+    for (int q = 0; q < 4; ++q) { g.parts[q] = q < ngroups ? nonfinite_partials[q] : nullptr; g.n[q] = q < ngroups ? nparts[q] : 0; }
     for (int q = 0; q < ngroups; ++q) WM_REQUIRE(g.parts[q] && g.n[q] > 0, WM_E_BADARG, "wm_amp_found_inf: null group");
     hipLaunchKernelGGL(amp_found_inf_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, g, ngroups, state, k);
     WM_LAUNCH_CHECK("wm_amp_found_inf");
@@ -359,10 +362,11 @@ extern "C" int wm_amp_update(float* state, int noptimizers, void* stream) {
 }
 
 extern "C" int wm_adam_step_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
-                                float weight_decay, int decoupled, float grad_scale, const float* amp_state, int k, void* stream) {
+                                float weight_decay, int decoupled, float grad_scale, const float* amp_state, int k, const float* hyper_dev,
+                                void* stream) {
     WM_REQUIRE(p && g && m && v && amp_state && n > 0 && k >= 0 && k < 4, WM_E_BADARG, "wm_adam_step_amp: bad arguments");
     hipLaunchKernelGGL(adam_amp_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
-                       decoupled, grad_scale, amp_state, k);
+                       decoupled, grad_scale, amp_state, k, hyper_dev);
     WM_LAUNCH_CHECK("wm_adam_step_amp");
     return WM_OK;
 }

@@ -86,8 +86,8 @@ class _FlatAdam:
         self._m = None
         self._v = None
         self.capturing = False  # True while a step is being CAPTURED into a hipGraph (_StepGraph): step() leaves step_count to the graph's owner,
-        self.hyper_dev = None   # and (without a scaler) launches the kernel that reads its step-count-dependent constants from this [2] f32
-                                # device tensor, which the owner refreshes before each replay
+        self.hyper_dev = None   # and launches the kernel that reads lr, betas, eps, weight_decay (and, without a scaler, the step-count-dependent
+                                # constants) from this [ops.ADAM_HYPER] f32 device tensor, which the owner refreshes before each replay
 
     def _ensure(self):
         if self._m is None:
@@ -110,24 +110,24 @@ class _FlatAdam:
         g = self.param_groups[0]
         amp = getattr(self, "amp", None)
         if amp is not None:   # scaler.step(optimizer), IRNcrop_model.py:413-414
-            amp.found_inf(self.amp_slot, [ops.sumsq(mod.flat_grads) for mod in self.modules])
+            amp.found_inf(self.amp_slot, [mod.flat_grads for mod in self.modules])
             for mod, m, v in zip(self.modules, self._m, self._v):
                 ops.adam_step_amp(mod.flat_params, mod.flat_grads, m, v, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
-                                  amp, self.amp_slot, decoupled=self.decoupled, grad_scale=grad_scale)
+                                  amp, self.amp_slot, decoupled=self.decoupled, grad_scale=grad_scale, hyper_dev=self.hyper_dev)
             return
-        if self.hyper_dev is not None:   # being captured: the constants of step t come from device memory at replay time
+        if self.hyper_dev is not None:   # being captured: the numbers of step t come from device memory at replay time
             for mod, m, v in zip(self.modules, self._m, self._v):
-                ops.adam_step_dev(mod.flat_params, mod.flat_grads, m, v, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
-                                  g["weight_decay"], self.hyper_dev, decoupled=self.decoupled, grad_scale=grad_scale)
+                ops.adam_step_dev(mod.flat_params, mod.flat_grads, m, v, self.hyper_dev, decoupled=self.decoupled, grad_scale=grad_scale)
             return
         for mod, m, v in zip(self.modules, self._m, self._v):
             ops.adam_step(mod.flat_params, mod.flat_grads, m, v, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
                           g["weight_decay"], self.step_count, decoupled=self.decoupled, grad_scale=grad_scale)
 
     def hyper(self, step):
-        """the pair adam_step derives from the step count (host arithmetic): what a captured step's replay needs in hyper_dev"""
+        """the current param group and the constants adam_step derives from the step count (host arithmetic): what a captured step's
+        replay needs in hyper_dev"""
         g = self.param_groups[0]
-        return ops.adam_hyper(g["lr"], g["betas"][0], g["betas"][1], step)
+        return ops.adam_hyper(g["lr"], g["betas"][0], g["betas"][1], step, g["eps"], g["weight_decay"])
 
     def _params(self):
         return [p for mod in self.modules for p in mod.parameters()]
@@ -166,6 +166,9 @@ class _FlatAdam:
         groups = sd["param_groups"]
         if len(groups) != 1:
             raise ValueError("expected one param group (torch.optim.Adam over one parameter list)")
+        for k in ("amsgrad", "maximize"):   # variants the kernel does not run: refused rather than continued as plain Adam
+            if groups[0].get(k, False):
+                raise ValueError(f"optimizer state uses {k}=True; the flat Adam step implements neither amsgrad nor maximize")
         params = self._params()
         ids = list(groups[0].get("params", range(len(params))))
         if len(ids) != len(params):
@@ -261,8 +264,10 @@ class _StepGraph:
     """One training step of `Hidden` as a hipGraph (the reference runs one Python step per batch per rank, train.py:99-109; here the host's
     ~190 launches per step are enqueued once and replayed).  Exact by construction: the graph holds the very launches of the eager step --
     the step has no autograd and no host synchronisation (engine.py) --, its inputs are static tensors refreshed by copy_, and the only
-    host-side number a step depends on, Adam's step count, reaches the kernels through device memory (wm_adam_step_dev) that is refreshed
-    before each replay.  Call k of a shape: k < WARMUP eager (real steps; they build the weight-pack plans and settle the allocator),
+    host-side numbers a step depends on -- Adam's step count and the param group's lr, betas, eps and weight_decay, which a scheduler or a
+    loaded state_dict may change between replays -- reach the kernels through device memory (wm_adam_step_dev / wm_adam_step_amp) that is
+    refreshed before each replay; `decoupled`, which selects a code path, is part of the graph's key.  Call k of a shape: k < WARMUP eager
+    (real steps; they build the weight-pack plans and settle the allocator),
     k == WARMUP capture + replay, later calls replay.  The tensors a replay returns (encoded, noised, decoded) are the graph's own and are
     overwritten by the next replay of the same graph, as torch.cuda.CUDAGraph documents; the losses are copied out per step."""
     WARMUP = 2
@@ -282,8 +287,7 @@ class _StepGraph:
 
     def _hyper_refresh(self):
         opts = (self.h.optimizer_discrim, self.h.optimizer_enc_dec)
-        if self.h.amp is not None:
-            return   # under the scaler the step counts live on the device already (wm_adam_step_amp)
+        # (under the scaler the kernel takes the step count from the device and reads only the hyperparameters of the block)
         vals = [v for o in opts for v in o.hyper(o.step_count + 1)]
         # a FRESH pinned tensor per replay: the copy below is asynchronous, and a host that runs ahead of the GPU (a loop that does not read
         # the losses every step: bench.py) would overwrite a reused staging buffer with the NEXT step's constants before this step's copy
@@ -300,15 +304,14 @@ class _StepGraph:
         if self.graph is None:
             dev = images.device
             self.img, self.msg = torch.empty_like(images), torch.empty_like(messages)
-            self.hyper = torch.zeros(4, device=dev, dtype=torch.float32)
+            self.hyper = torch.zeros(2 * ops.ADAM_HYPER, device=dev, dtype=torch.float32)
             self.img.copy_(images); self.msg.copy_(messages)
             self._seen = {"img": (images, images._version), "msg": (messages, messages._version)}
             opts = (h.optimizer_discrim, h.optimizer_enc_dec)
             for i, o in enumerate(opts):
                 o._ensure()
                 o.capturing = True
-                if h.amp is None:
-                    o.hyper_dev = self.hyper[2 * i:2 * i + 2]
+                o.hyper_dev = self.hyper[ops.ADAM_HYPER * i:ops.ADAM_HYPER * (i + 1)]
             graph = torch.cuda.CUDAGraph()
             # Python's cyclic collector must not run inside the capture: whatever dead cycle it finds may own device memory, events or
             # another hipGraph, and releasing those calls HIP functions that are illegal while a stream captures (the process aborts --
@@ -467,10 +470,10 @@ class Hidden:
         else:
             ck = None
         if ck is not None:
+            # (the optimisers' numbers are read from device memory at each replay, _StepGraph._hyper_refresh: only `decoupled`, a code path,
+            # needs a graph of its own)
             key = (tuple(images.shape), tuple(messages.shape), self.noise_id, self.keep_dead_discriminator_grads, self.lazy_losses, self.two_streams, self.skip_zero_attack_gradient,
-                   self.encoder_decoder.encoder.compute_dtype, ck)
-            if self.amp is not None:   # under the scaler the learning rate reaches wm_adam_step_amp as a launch argument: a scheduler's new value needs its own graph
-                key += tuple(o.param_groups[0]["lr"] for o in (self.optimizer_discrim, self.optimizer_enc_dec))
+                   self.encoder_decoder.encoder.compute_dtype, ck, self.optimizer_discrim.decoupled, self.optimizer_enc_dec.decoupled)
             g = self._graphs.get(key)
             if g is None and len(self._graphs) < self.MAX_GRAPHS:
                 g = self._graphs[key] = _StepGraph(self)

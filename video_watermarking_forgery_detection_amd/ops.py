@@ -881,20 +881,23 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, decoupled=F
     _wrote(p, m, v)
 
 
-def adam_hyper(lr, beta1, beta2, step):
-    """(lr / (1 - beta1^step), sqrt(1 - beta2^step)) as wm_adam_step derives them (host arithmetic, no launch)"""
-    out = (c_float * 2)()
-    rc = _lib.lib().wm_adam_hyper(c_float(lr), c_float(beta1), c_float(beta2), c_int(step), out)
+ADAM_HYPER = 8   # WM_ADAM_HYPER
+
+
+def adam_hyper(lr, beta1, beta2, step, eps, weight_decay):
+    """the WM_ADAM_HYPER floats a replayed step reads (host arithmetic, no launch): (lr / (1 - beta1^step), sqrt(1 - beta2^step), lr, beta1,
+    beta2, eps, weight_decay, 0) -- the first two exactly as wm_adam_step derives them, the rest rounded to f32 as its arguments are"""
+    out = (c_float * ADAM_HYPER)()
+    rc = _lib.lib().wm_adam_hyper(c_float(lr), c_float(beta1), c_float(beta2), c_float(eps), c_float(weight_decay), c_int(step), out)
     _lib.check(rc, "wm_adam_hyper")
-    return float(out[0]), float(out[1])
+    return tuple(float(x) for x in out)
 
 
-def adam_step_dev(p, g, m, v, lr, beta1, beta2, eps, weight_decay, hyper_dev, decoupled=False, grad_scale=1.0):
-    """adam_step with the step-count-dependent constants read from the device tensor hyper_dev [2] f32 (adam_hyper's pair): what a
+def adam_step_dev(p, g, m, v, hyper_dev, decoupled=False, grad_scale=1.0):
+    """adam_step with every number but `decoupled` read from the device tensor hyper_dev [ADAM_HYPER] f32 (adam_hyper's block): what a
     captured step launches -- the caller refreshes hyper_dev before each replay"""
-    assert hyper_dev.is_cuda and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 2 and hyper_dev.is_contiguous()
-    rc = _lib.lib().wm_adam_step_dev(_p(p), _p(g), _p(m), _p(v), c_size_t(p.numel()), c_float(lr), c_float(beta1), c_float(beta2),
-                                     c_float(eps), c_float(weight_decay), c_int(1 if decoupled else 0), _p(hyper_dev),
+    assert hyper_dev.is_cuda and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= ADAM_HYPER and hyper_dev.is_contiguous()
+    rc = _lib.lib().wm_adam_step_dev(_p(p), _p(g), _p(m), _p(v), c_size_t(p.numel()), c_int(1 if decoupled else 0), _p(hyper_dev),
                                      c_float(grad_scale), _stream())
     _lib.check(rc, "wm_adam_step_dev")
     _wrote(p, m, v)
@@ -920,8 +923,9 @@ class AmpState:
         self.nopt += 1
         return k
 
-    def found_inf(self, k, parts):
-        """found_inf[k] from the wm_sumsq rows of optimiser k's gradient buffers"""
+    def found_inf(self, k, grads):
+        """found_inf[k]: does any of optimiser k's flat gradient buffers hold an inf / nan (GradScaler's per-element check)"""
+        parts = [nonfinite(g) for g in grads]
         arr = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
         ns = (ctypes.c_int * len(parts))(*[p.numel() for p in parts])
         rc = _lib.lib().wm_amp_found_inf(arr, ns, c_int(len(parts)), _p(self.state), c_int(k), _stream())
@@ -955,9 +959,14 @@ class AmpState:
         self.state.copy_(st)
 
 
-def adam_step_amp(p, g, m, v, lr, beta1, beta2, eps, weight_decay, amp, k, decoupled=False, grad_scale=1.0):
+def adam_step_amp(p, g, m, v, lr, beta1, beta2, eps, weight_decay, amp, k, decoupled=False, grad_scale=1.0, hyper_dev=None):
+    """the step under the device scaler; hyper_dev (a captured step): adam_hyper's block on the device, whose lr, betas, eps and weight_decay
+    replace the arguments at each replay"""
+    if hyper_dev is not None:
+        assert hyper_dev.is_cuda and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= ADAM_HYPER and hyper_dev.is_contiguous()
     rc = _lib.lib().wm_adam_step_amp(_p(p), _p(g), _p(m), _p(v), c_size_t(p.numel()), c_float(lr), c_float(beta1), c_float(beta2), c_float(eps),
-                                     c_float(weight_decay), c_int(1 if decoupled else 0), c_float(grad_scale), _p(amp.state), c_int(k), _stream())
+                                     c_float(weight_decay), c_int(1 if decoupled else 0), c_float(grad_scale), _p(amp.state), c_int(k),
+                                     _p(hyper_dev), _stream())
     _lib.check(rc, "wm_adam_step_amp")
     _wrote(p, m, v)
 
@@ -968,6 +977,16 @@ def sumsq(x):
     part = torch.empty(nparts, device=x.device, dtype=torch.float32)
     rc = _lib.lib().wm_sumsq(_p(x), c_size_t(n), _p(part), c_int(nparts), _stream())
     _lib.check(rc, "wm_sumsq")
+    return part
+
+
+def nonfinite(x):
+    """per-block flags (1.0: the block saw an inf / nan in x) -- the rows AmpState.found_inf reduces"""
+    n = x.numel()
+    nparts = max(1, min(1024, (n + 4095) // 4096))
+    part = torch.empty(nparts, device=x.device, dtype=torch.float32)
+    rc = _lib.lib().wm_nonfinite(_p(x), c_size_t(n), _p(part), c_int(nparts), _stream())
+    _lib.check(rc, "wm_nonfinite")
     return part
 
 
