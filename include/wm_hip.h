@@ -663,6 +663,45 @@ int wm_clamp01_fwd(const float* x, float* y, size_t n, void* stream);
 int wm_clamp01_bwd(const float* x, const float* g, float* gx, size_t n, void* stream);
 int wm_psnr255_partials(const float* a, const float* b, size_t n, double* partials, int nparts, void* stream);
 
+/* ------------------------------------------------------------------ device RNG and the stochastic attacks (csrc/noise.hip)
+ * Philox4x32-10.  The draw for element index i is a pure function of (seed, offset, i): key = seed, counter = (i / 4, offset), word i % 4.
+ * uniform = 24-bit floats in [0,1); normal = Box-Muller (u1 in (0,1], accurate logf / sincosf) on the word pairs (0,1) and (2,3).
+ * state: device array of WM_RNG_STATE_WORDS int64 {seed, offset, 0, 0} owned by the caller (a layer).  Each forward call uses the counters
+ * [offset, offset + reserve) (reserve = 1; 2 for wm_dropout_fwd: the keep ratio at offset, the mask at offset + 1): a one-thread launch copies
+ * {seed, offset} into rec[2] (device, int64) and advances the state's offset, in stream order, then the attack kernel reads rec only; the
+ * backward regenerates the same draws from rec.  Safe under hipGraph capture: every replay draws fresh numbers.
+ * wm_rng_fill (test entry point): out[i] = draw i, i < n, of the stream at (state[0], state[1]) -- exactly what a kernel consumes for element
+ * index i; the state is only read (a rec array is a valid state). */
+#define WM_RNG_STATE_WORDS 4
+#define WM_RNG_UNIFORM 0
+#define WM_RNG_NORMAL 1
+int wm_rng_fill(const void* state, float* out, size_t n, int dist, void* stream);
+/* per-element attacks on n f32 elements (u uniform, z normal of element i):
+ *   WM_NOISE_DROP  y = u > a ? cover : x            replaces noise_layers/crop.py:136-147 (Dropout, a = prob)
+ *   WM_NOISE_GAUSS y = clamp(x + fma(b, z, a), 0, 1) replaces noise_layers/gaussian.py:11-17 (a = mean, b = stddev)
+ *   WM_NOISE_GN    y = x + fma(b, z, a)              replaces noise_layers/gaussian_noise.py:12-20 (a = mean, b = sqrt(var))
+ *   WM_NOISE_SP    y = u > b ? 0 : x, then u < a ? 1  replaces noise_layers/salt_pepper_noise.py:10-19 (a = prob/2, b = 1 - prob/2)
+ * wm_noise_bwd: gx = dy/dx . g (x = the forward's input, read by WM_NOISE_GAUSS only; WM_NOISE_GN has no kernel: the identity);
+ * gcover (WM_NOISE_DROP, may be NULL) = dy/dcover . g. */
+#define WM_NOISE_DROP 0
+#define WM_NOISE_GAUSS 1
+#define WM_NOISE_GN 2
+#define WM_NOISE_SP 3
+int wm_noise_fwd(int op, const float* x, const float* cover, float* y, size_t n, float a, float b, void* state, void* rec, void* stream);
+int wm_noise_bwd(int op, const float* x, const float* g, float* gx, float* gcover, size_t n, float a, float b, const void* rec, void* stream);
+/* replaces noise_layers/dropout.py:4-27 on N = B*C planes of H x W: keep = fma(keep_span, u, keep_min) from counter block 0 at offset,
+ * one mask m = [u < keep] over H x W (element h*W + w at offset + 1) shared by every plane; y = x*m + cover*(1-m);
+ * backward gx = g*m, gcover (may be NULL) = g*(1-m). */
+int wm_dropout_fwd(const float* x, const float* cover, float* y, int N, int H, int W, float keep_min, float keep_span, void* state, void* rec,
+                   void* stream);
+int wm_dropout_bwd(const float* g, float* gx, float* gcover, int N, int H, int W, float keep_min, float keep_span, const void* rec,
+                   void* stream);
+/* JpegCompression ("JPEG-Drop", replaces noise_layers/jpeg_compression.py:65-159) on [B,3,H,W] f32: zero pad to a multiple of 8, analog
+ * rgb2yuv, unnormalised 8x8 DCT-II, zig-zag keep mask of keep[3] (host pointer: coefficients kept in Y, U, V), IDCT (scaled sqrt(1/16), -1/2
+ * on DC), yuv2rgb, un-pad.  wm_jpeg_drop_bwd is its exact transpose (rgb2yuv^T DCT^T mask IDCT^T yuv2rgb^T). */
+int wm_jpeg_drop_fwd(const float* x, float* y, int B, int H, int W, const int* keep, void* stream);
+int wm_jpeg_drop_bwd(const float* gy, float* gx, int B, int H, int W, const int* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import engine, ops
+from ..noise_layers._device_rng import accepts_cover
 from ..options import HiDDenConfiguration
 from .discriminator import Discriminator
 from .encoder_decoder import EncoderDecoder
@@ -443,10 +444,12 @@ class Hidden:
     def _run_noiser(self, enc, cover):
         n = self.encoder_decoder.noiser
         if hasattr(n, "fwd") and hasattr(n, "bwd"):
+            kw = {}
             if _accepts_id(n.fwd):   # Combined / Noiser / the attack cycle take a deterministic choice; single layers do not
-                y, c = n.fwd(enc, id=self.noise_id)
-            else:
-                y, c = n.fwd(enc)
+                kw["id"] = self.noise_id
+            if accepts_cover(n.fwd):   # a layer that mixes in the cover (the Dropouts), or a container that passes it on
+                kw["cover"] = cover
+            y, c = n.fwd(enc, **kw)
             return y, ("explicit", c)
         return _noise_fwd(n, enc, cover)
 

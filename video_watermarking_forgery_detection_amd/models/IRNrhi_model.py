@@ -29,6 +29,11 @@ from ..hidden_models import Hidden
 from ..hidden_models.hidden import _FlatAdam
 from ..network.UNet import UNet
 from ..noise_layers import Combined, Crop, GaussianBlur, Identity, Jpeg, JpegMask, JpegSS, MiddleBlur, Resize
+from ..noise_layers._device_rng import call_fwd
+from ..noise_layers.dropout import Dropout
+from ..noise_layers.gaussian import Gaussian
+from ..noise_layers.jpeg_compression import JpegCompression
+from ..noise_layers.salt_pepper_noise import SaltPepper
 from ..options import HiDDenConfiguration
 from .base_model import BaseModel
 from .modules.Quantization import Quantization
@@ -102,7 +107,7 @@ class _AttackCycle:
         i, layer = self._choose()
         return ("cycle", i, type(layer).__name__)
 
-    def fwd(self, image, id=None, exclude=()):
+    def fwd(self, image, id=None, exclude=(), cover=None):
         i, layer = self._choose(id, exclude)
         if isinstance(layer, Resize):
             y, c = layer.fwd(image, resize_ratio=0.7)
@@ -110,7 +115,7 @@ class _AttackCycle:
             H, W = image.shape[2], image.shape[3]
             y, c = layer.fwd(image, apex=(H // 8, H // 8 + int(0.75 * H), W // 8, W // 8 + int(0.75 * W)))
         else:
-            y, c = layer.fwd(image)
+            y, c = call_fwd(layer, image, cover)   # (the cover reaches the layers that mix it in: Dropout)
         self.name = getattr(layer, "name", type(layer).__name__)   # (a layer may name itself in its forward: the reference's G_Blur -> GaussianBlur)
         return y, (layer, c)
 
@@ -153,6 +158,10 @@ class IRNrhiModel(BaseModel):
             "Jpeg": lambda q: Jpeg(q), "JpegSS": lambda q: JpegSS(q), "JpegMask": lambda q: JpegMask(q),
             "GaussianBlur": lambda q: GaussianBlur(), "MiddleBlur": lambda q: MiddleBlur(q or 3),
             "Resize": lambda q: Resize(), "Crop": lambda q: Crop(), "Identity": lambda q: Identity(),
+            # the stochastic / JPEG-Drop attacks every reference trainer constructs (IRNrhi_model.py:134-136): dropout.Dropout(),
+            # Gaussian(), SaltPepper(prob=0.01), JpegCompression; their draws come from the device generator, seeded from torch's
+            "Dropout": lambda q: Dropout(), "Gaussian": lambda q: Gaussian(), "SaltPepper": lambda q: SaltPepper(prob=0.01),
+            "JpegCompression": lambda q: JpegCompression(self.device),
         }
         if attacks is None:
             attacks = ["Jpeg50"]
@@ -283,7 +292,7 @@ class IRNrhiModel(BaseModel):
             self._gate(encoded, images)
         (tampered, mask), self._loc = self._loc, None
         kind = self.attack.name                                     # the step's attack (set by the embed -> attack -> extract pass)
-        attacked, cA = self.attack.fwd(tampered, exclude=(Crop,))   # the reference's localiser sees no geometric attack (:362-366)
+        attacked, cA = self.attack.fwd(tampered, exclude=(Crop,), cover=images)   # the reference's localiser sees no geometric attack (:362-366)
         attacked_q = ops.clamp_quant(attacked)                      # clamp_with_grad + Quantization (:372-373)
         if self.keep_outputs:
             self.last_outputs.update(tampered=tampered, attacked=attacked_q)

@@ -1,5 +1,6 @@
 """Differentiable attack layers on the MI355X kernels -- mirror of the reference's noise_layers/
-package for the layers the models instantiate."""
+package: the layers the models instantiate and the stochastic / JPEG-Drop attacks the
+reference's trainers construct and its __init__ exports (Dropout = crop.py's, GN, SaltPepper)."""
 import random
 
 
@@ -17,5 +18,9 @@ from .combined import Combined  # noqa: E402
 from .gaussian_blur import GaussianBlur  # noqa: E402
 from .middle_filter import MiddleBlur  # noqa: E402
 from .resize import Resize  # noqa: E402
-from .crop import Crop  # noqa: E402
+from .crop import Crop, Dropout  # noqa: E402
+from .gaussian_noise import GN  # noqa: E402
+from .salt_pepper_noise import SaltPepper  # noqa: E402
+from .gaussian import Gaussian  # noqa: E402
+from .jpeg_compression import JpegCompression  # noqa: E402
 from .noiser import Noiser  # noqa: E402

@@ -3,6 +3,7 @@ reference's noise_layers/combined.py:6-20 (python `random.randint`, `.name` of t
 import torch.nn as nn
 
 from . import get_random_int
+from ._device_rng import call_fwd
 from .identity import Identity
 
 
@@ -18,15 +19,19 @@ class Combined(nn.Module):
         if id is None or id >= len(self.list):
             id = get_random_int([0, len(self.list) - 1])
         selected = self.list[id]
-        self.name = selected.name
+        self.name = getattr(selected, "name", type(selected).__name__)
         return selected
 
     def forward(self, image_and_cover, id=None):
-        return self._pick(id)(image_and_cover)
-
-    def fwd(self, image, id=None):
         sel = self._pick(id)
-        y, c = sel.fwd(image)
+        if hasattr(sel, "apply_attack"):   # the stochastic / JPEG-Drop layers: each takes the image (and the cover) in its own form
+            pair = isinstance(image_and_cover, (list, tuple))
+            return sel.apply_attack(image_and_cover[0] if pair else image_and_cover, image_and_cover[1] if pair else None)
+        return sel(image_and_cover)
+
+    def fwd(self, image, id=None, cover=None):
+        sel = self._pick(id)
+        y, c = call_fwd(sel, image, cover)
         return y, (sel, c)
 
     def bwd(self, ctx, g):

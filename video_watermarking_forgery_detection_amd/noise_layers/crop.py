@@ -1,11 +1,15 @@
 """Crop -- mirror of the reference's noise_layers/crop.py:8-55 (`forward`): random (numpy RNG) or
 `apex`-given rectangle, bilinear resize back to the full frame; returns (image, apex).  The slice and
-the interpolation are one gather kernel (the rectangle is an offset into the source planes)."""
+the interpolation are one gather kernel (the rectangle is an offset into the source planes).
+
+Dropout -- mirror of crop.py:136-147 (the Dropout the reference's noise_layers package exports):
+per-element u ~ U[0,1), where(u > prob, cover, image), from the layer's device generator (csrc/noise.hip)."""
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
+from ._device_rng import DeviceRng, need_cuda
 
 
 class _CropFn(torch.autograd.Function):
@@ -65,3 +69,44 @@ class Crop(nn.Module):
     def bwd(self, ctx, g):
         rect, hw = ctx
         return ops.resample_bwd(g, None, hw, rect, ops.BILINEAR)
+
+
+class _DropFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, cover, layer):
+        y, rec = ops.noise_fwd(ops.NOISE_DROP, image, layer._prob, 0.0, layer._rng.state_on(image.device), cover=cover)
+        ctx.layer, ctx.rec = layer, rec
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, gc = ops.noise_bwd(ops.NOISE_DROP, g, ctx.layer._prob, 0.0, ctx.rec, want_cover=ctx.needs_input_grad[1])
+        return gx, gc, None
+
+
+class Dropout(nn.Module):
+    capturable = True    # the draws come from device state: a step through this layer may be captured, and every replay draws fresh noise
+    needs_cover = True
+
+    def __init__(self, prob=0.5):
+        super(Dropout, self).__init__()
+        self.prob = prob
+        self._prob = float(torch.tensor(self.prob * 1., dtype=torch.float32))   # rdn > self.prob * 1. compares in f32
+        self.name = "Dropout"
+        self._rng = DeviceRng()
+
+    def forward(self, image_and_cover):
+        image, cover_image = image_and_cover
+        need_cuda(self.name, image, cover_image)
+        return _DropFn.apply(image, cover_image, self)
+
+    def apply_attack(self, image, cover=None):
+        return self.forward([image, cover])
+
+    def fwd(self, image, cover=None):
+        if cover is None:
+            raise ValueError("Dropout mixes in the cover image: fwd(image, cover=...)")
+        return ops.noise_fwd(ops.NOISE_DROP, image, self._prob, 0.0, self._rng.state_on(image.device), cover=cover)
+
+    def bwd(self, ctx, g):
+        return ops.noise_bwd(ops.NOISE_DROP, g, self._prob, 0.0, ctx)[0]

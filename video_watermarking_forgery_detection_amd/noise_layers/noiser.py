@@ -6,6 +6,7 @@ import random
 
 import torch.nn as nn
 
+from ._device_rng import call_fwd
 from .identity import Identity
 
 
@@ -24,14 +25,15 @@ class Noiser(nn.Module):
 
     def forward(self, encoded_and_cover, id=None):
         enc, cover = encoded_and_cover
-        out = self._pick(id)(enc)
+        sel = self._pick(id)
+        out = sel.apply_attack(enc, cover) if hasattr(sel, "apply_attack") else sel(enc)
         if isinstance(out, tuple):  # Crop returns (image, apex)
             out = out[0]
         return [out, cover]
 
-    def fwd(self, image, id=None):
+    def fwd(self, image, id=None, cover=None):
         sel = self._pick(id)
-        y, c = sel.fwd(image)
+        y, c = call_fwd(sel, image, cover)
         return y, (sel, c)
 
     def bwd(self, ctx, g):

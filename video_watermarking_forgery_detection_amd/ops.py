@@ -1768,3 +1768,113 @@ def scale_dev_(x, scale_dev):
     _lib.check(rc, "wm_scale_dev")
     _wrote(x)
     return x
+
+
+# ----------------------------------------------------------------------------- device RNG and the stochastic / JPEG-Drop attacks (csrc/noise.hip,
+# csrc/jpeg_drop.hip).  `state` is a layer's int64[RNG_STATE_WORDS] device tensor {seed, offset, ...}; a forward returns, beside its output,
+# rec = int64[2] {seed, offset} of the call, from which the backward regenerates the same draws
+RNG_STATE_WORDS = 4
+RNG_UNIFORM, RNG_NORMAL = 0, 1
+NOISE_DROP, NOISE_GAUSS, NOISE_GN, NOISE_SP = 0, 1, 2, 3
+
+
+def rng_state(seed, device, offset=0):
+    """a fresh generator state {seed, offset, 0, 0} on `device` (seed: a 64-bit integer, stored two's complement)"""
+    seed = int(seed) & (2 ** 64 - 1)
+    if seed >= 2 ** 63:
+        seed -= 2 ** 64
+    return torch.tensor([seed, int(offset), 0, 0], dtype=torch.int64).to(device)
+
+
+def rng_fill(state, n, dist=RNG_UNIFORM):
+    """the n draws a kernel consumes for element indices 0..n-1 at (state[0], state[1]); reads the state (or a rec) only"""
+    _need_cuda(state)
+    assert state.dtype == torch.int64 and state.numel() >= 2
+    out = torch.empty(int(n), device=state.device, dtype=torch.float32)
+    rc = _lib.lib().wm_rng_fill(_p(state), _p(out), c_size_t(int(n)), c_int(dist), _stream())
+    _lib.check(rc, "wm_rng_fill")
+    return out
+
+
+def _rng_args(x, state):
+    _need_cuda(x, state)
+    assert state.dtype == torch.int64 and state.numel() == RNG_STATE_WORDS and state.device == x.device
+    rec = torch.empty(2, device=x.device, dtype=torch.int64)
+    return rec
+
+
+def noise_fwd(op, x, a, b, state, cover=None):
+    """per-element attack (NOISE_DROP needs `cover`) -> (y, rec); advances `state` by one counter block in stream order"""
+    _need_cuda(x, cover)
+    x = x.contiguous().float()
+    if cover is not None:
+        cover = cover.contiguous().float()
+        assert cover.shape == x.shape
+    rec = _rng_args(x, state)
+    y = torch.empty_like(x)
+    rc = _lib.lib().wm_noise_fwd(c_int(op), _p(x), _p(cover), _p(y), c_size_t(x.numel()), c_float(a), c_float(b), _p(state), _p(rec),
+                                 _stream())
+    _lib.check(rc, "wm_noise_fwd")
+    _wrote(state)
+    return y, rec
+
+
+def noise_bwd(op, g, a, b, rec, x=None, want_cover=False):
+    """-> (gradient wrt the image, gradient wrt the cover or None); x = the forward's input (NOISE_GAUSS)"""
+    _need_cuda(g, rec, x)
+    g = g.contiguous().float()
+    if op == NOISE_GN:
+        return g, None
+    if x is not None:
+        x = x.contiguous().float()
+    gx = torch.empty_like(g)
+    gc = torch.empty_like(g) if want_cover and op == NOISE_DROP else None
+    rc = _lib.lib().wm_noise_bwd(c_int(op), _p(x), _p(g), _p(gx), _p(gc), c_size_t(g.numel()), c_float(a), c_float(b), _p(rec), _stream())
+    _lib.check(rc, "wm_noise_bwd")
+    return gx, gc
+
+
+def dropout_fwd(x, cover, keep_min, keep_span, state):
+    """dropout.Dropout: one keep mask over H x W shared by every plane -> (y, rec); advances `state` by two counter blocks"""
+    _need_cuda(cover)
+    x, N, H, W = _planes(x)
+    cover = cover.contiguous().float()
+    assert cover.shape == x.shape
+    rec = _rng_args(x, state)
+    y = torch.empty_like(x)
+    rc = _lib.lib().wm_dropout_fwd(_p(x), _p(cover), _p(y), c_int(N), c_int(H), c_int(W), c_float(keep_min), c_float(keep_span), _p(state),
+                                   _p(rec), _stream())
+    _lib.check(rc, "wm_dropout_fwd")
+    _wrote(state)
+    return y, rec
+
+
+def dropout_bwd(g, keep_min, keep_span, rec, want_cover=False):
+    g, N, H, W = _planes(g)
+    gx = torch.empty_like(g)
+    gc = torch.empty_like(g) if want_cover else None
+    rc = _lib.lib().wm_dropout_bwd(_p(g), _p(gx), _p(gc), c_int(N), c_int(H), c_int(W), c_float(keep_min), c_float(keep_span), _p(rec),
+                                   _stream())
+    _lib.check(rc, "wm_dropout_bwd")
+    return gx, gc
+
+
+def _jpeg_drop(name, x, keep):
+    _need_cuda(x)
+    assert x.dim() == 4 and x.shape[1] == 3, "JpegCompression takes [B,3,H,W] images"
+    x = x.contiguous().float()
+    y = torch.empty_like(x)
+    k = (c_int * 3)(*[int(v) for v in keep])
+    rc = getattr(_lib.lib(), name)(_p(x), _p(y), c_int(x.shape[0]), c_int(x.shape[2]), c_int(x.shape[3]), k, _stream())
+    _lib.check(rc, name)
+    return y
+
+
+def jpeg_drop_fwd(x, keep=(25, 9, 9)):
+    """JpegCompression forward (keep = coefficients kept in Y, U, V)"""
+    return _jpeg_drop("wm_jpeg_drop_fwd", x, keep)
+
+
+def jpeg_drop_bwd(g, keep=(25, 9, 9)):
+    """the exact transpose of jpeg_drop_fwd"""
+    return _jpeg_drop("wm_jpeg_drop_bwd", g, keep)
