@@ -35,6 +35,8 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* the library is compiled with -fvisibility=hidden: the functions declared here are its whole export table */
+#pragma GCC visibility push(default)
 
 #define WM_F32 0
 #define WM_BF16 1
@@ -702,6 +704,7 @@ int wm_dropout_bwd(const float* g, float* gx, float* gcover, int N, int H, int W
 int wm_jpeg_drop_fwd(const float* x, float* y, int B, int H, int W, const int* keep, void* stream);
 int wm_jpeg_drop_bwd(const float* gy, float* gx, int B, int H, int W, const int* keep, void* stream);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,11 @@
 """CPU: host-side surface checks that need no GPU -- state_dict keys equal the reference's
 (through the oracle restatement, itself pinned to the reference by test_oracle_golden), the C-ABI
-library loads and exports every symbol include/wm_hip.h declares, and the product path refuses to
-run without a GPU instead of falling back."""
+library exports exactly the symbols include/wm_hip.h declares and is bound with their signatures, and
+the product path refuses to run without a GPU instead of falling back."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 import torch
@@ -27,27 +28,84 @@ def test_state_dict_keys_match_reference_names():
         ref.load_state_dict(a)  # checkpoints interchange
 
 
-def test_library_exports_every_declared_symbol():
+def _built():
     from video_watermarking_forgery_detection_amd import _lib
+    if not (os.path.exists(_lib.LIB_PATH) and os.path.exists(_lib.DEBUG_LIB_PATH)):
+        from video_watermarking_forgery_detection_amd import build
+        build.build(verbose=False)
+    return _lib
+
+
+def _exported_functions(path):
+    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return sorted(f[2] for f in (ln.split() for ln in nm.splitlines()) if len(f) == 3 and f[1] == "T")
+
+
+def test_library_exports_every_declared_symbol():
+    """the header IS the boundary: the release library exports exactly the functions include/wm_hip.h declares -- no C++ internals --
+    and the -DWM_DEBUG twin those plus its wm_debug_* switches"""
+    _lib = _built()
     hdr = open(os.path.join(ROOT, "include", "wm_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     names = sorted(set(re.findall(r"\b(wm_[a-z0-9_]+)\s*\(", hdr)))
-    assert len(names) >= 20
-    if not os.path.exists(_lib.LIB_PATH):
-        from video_watermarking_forgery_detection_amd import build
-        build.build(verbose=False)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    missing = [n for n in names if not hasattr(lib, n)]
-    assert not missing, missing
-    assert lib.wm_abi_version() >= 1
-    # ... and the converse: the header IS the boundary -- every wm_* function the release library exports is declared in it
-    # (the wm_debug_* switches exist only in the -DWM_DEBUG twin, which is not a product library)
-    import subprocess
-    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted({ln.split()[-1] for ln in nm.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T" and ln.split()[-1].startswith("wm_")})
-    assert len(exported) >= len(names) - 5
-    undeclared = [n for n in exported if n not in set(names)]
-    assert not undeclared, undeclared
+    assert len(names) >= 20 and names == sorted(_lib.signatures())
+    exported = _exported_functions(_lib.LIB_PATH)
+    assert not [n for n in exported if n.startswith("_Z")]
+    assert exported == names
+    assert len(_lib.debug_setters()) >= 1
+    assert _exported_functions(_lib.DEBUG_LIB_PATH) == sorted(names + _lib.debug_setters())
+    assert ctypes.CDLL(_lib.LIB_PATH).wm_abi_version() >= 1
+
+
+def test_loaded_handles_carry_the_header_signatures():
+    """every declared function of both handles has the header's argtypes and restype (the debug handle: and its setters take one int);
+    the type map is closed -- a type it does not know is an error, not an untyped argument"""
+    _lib = _built()
+    sigs = _lib.signatures()
+    for h in (_lib.lib(), _lib.debug_lib()):
+        for n, (restype, argtypes) in sigs.items():
+            f = getattr(h, n)
+            assert list(f.argtypes) == argtypes and f.restype is restype, n
+    for n in _lib.debug_setters():
+        f = getattr(_lib.debug_lib(), n)
+        assert list(f.argtypes) == [ctypes.c_int] and f.restype is None, n
+    assert sigs["wm_last_error_string"] == (ctypes.c_char_p, [])
+    assert sigs["wm_conv3x3_wgrad_ws_bytes"] == (ctypes.c_size_t, [ctypes.c_int] * 5)
+    assert sigs["wm_bn_finalize"][1][4] is ctypes.c_double and sigs["wm_bn_finalize"][1][9] is ctypes.c_float
+    assert sigs["wm_amp_found_inf"][1][:2] == [ctypes.c_void_p] * 2           # const float* const*, const int*
+    assert sigs["wm_conv3x3_wgrad_fin"][1][-3:] == [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]   # const WmBnBwdFin*, sweep_reverse, stream
+    for bad in ("int wm_a(long n);", "void wm_b(int n);", "int* wm_c(int n);", "int wm_d(unsigned n);", "int wm_e(int);"):
+        with pytest.raises(RuntimeError):
+            _lib.parse_header(bad)
+    assert _lib.parse_header("int wm_g(void);\nsize_t wm_h(const unsigned char* p, double d /* x */, float f);") == {
+        "wm_g": (ctypes.c_int, []), "wm_h": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_double, ctypes.c_float])}
+
+
+def test_every_direct_call_passes_the_header_arity():
+    """ctypes refuses too few arguments but passes surplus ones through: each call of a wm_* attribute with positional arguments in the
+    package, tests/ and tools/ passes exactly as many as include/wm_hip.h declares (a wm_debug_* setter: one)"""
+    import ast
+    from video_watermarking_forgery_detection_amd import _lib
+    arity = {n: len(a) for n, (_, a) in _lib.signatures().items()}
+    arity.update((n, 1) for n in _lib.debug_setters())
+    bad, seen = [], 0
+    for top in ("video_watermarking_forgery_detection_amd", "tests", "tools"):
+        for dp, _, fs in os.walk(os.path.join(ROOT, top)):
+            for f in fs:
+                if not f.endswith(".py"):
+                    continue
+                path = os.path.join(dp, f)
+                with open(path) as fh:
+                    tree = ast.parse(fh.read(), path)
+                for node in ast.walk(tree):
+                    if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr.startswith("wm_")
+                            and not node.keywords and not any(isinstance(a, ast.Starred) for a in node.args)):
+                        seen += 1
+                        if arity.get(node.func.attr) != len(node.args):
+                            bad.append(f"{os.path.relpath(path, ROOT)}:{node.lineno} {node.func.attr}: {len(node.args)} arguments, "
+                                       f"header: {arity.get(node.func.attr)}")
+    assert seen >= 150
+    assert not bad, bad
 
 
 def test_no_cpu_fallback():

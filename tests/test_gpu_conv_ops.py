@@ -907,9 +907,10 @@ def test_finalisation_riders_keep_the_training_step(debug_lib):
         assert torch.equal(a, b)
 
 
-def test_fused_backward_entry_points_fail_loudly():
+def test_fused_backward_entry_points_fail_loudly_on_complete_calls():
     """the fused backward entry points reject what they do not support with a negative code and a message (no silent fallback):
-    wrong dtype, wrong channel counts, missing partner arguments, an oversized rider"""
+    wrong dtype, wrong channel counts, missing partner arguments, an oversized rider.  Every call passes the header's full argument
+    list; a call one argument short is refused by the typed binding before it reaches the library"""
     import ctypes
     from video_watermarking_forgery_detection_amd import _lib, ops
     L = _lib.lib()
@@ -923,15 +924,19 @@ def test_fused_backward_entry_points_fail_loudly():
         return L.wm_last_error_string().decode()
     # f32 has no fused kernel
     assert not ops.conv3x3_dgrad_applyfused_supported(64, 64, torch.float32) and not ops.conv3x3_gvfused_supported(64, 64, torch.float32)
-    rc = L.wm_conv3x3_dgrad_applyfused(P(g), P(g), P(f), P(coef), P(wpt), P(g), P(g), P(None), P(None), P(None), P(None), 1, 16, 16, 64, 0, None)
+    rc = L.wm_conv3x3_dgrad_applyfused(P(g), P(g), P(f), P(coef), P(wpt), P(g), P(g), P(None), P(None), P(None), P(None), 1, 16, 16, 64, 0, 0, None)
     assert rc < 0 and "unsupported" in err()
+    # the same call without sweep_reverse (17 of 18 arguments: the stream slot would be read from whatever the register holds)
+    short = [P(g), P(g), P(f), P(coef), P(wpt), P(g), P(g), P(None), P(None), P(None), P(None), 1, 16, 16, 64, 0, None]
+    with pytest.raises(TypeError):
+        L.wm_conv3x3_dgrad_applyfused(*short)
     # the feeding layer's sums need all four of ry, r_scale, r_shift, partials
-    rc = L.wm_conv3x3_dgrad_applyfused(P(g), P(g), P(f), P(coef), P(wpt), P(g), P(g), P(g), P(None), P(None), P(part), 1, 16, 16, 64, 1, None)
+    rc = L.wm_conv3x3_dgrad_applyfused(P(g), P(g), P(f), P(coef), P(wpt), P(g), P(g), P(g), P(None), P(None), P(part), 1, 16, 16, 64, 1, 0, None)
     assert rc < 0 and "come together" in err()
     # ... and a 64-channel input gradient
-    rc = L.wm_conv3x3_dgrad_applyfused(P(g), P(g), P(f), P(coef), P(wpt), P(g), P(g), P(g), P(f), P(f), P(part), 1, 16, 16, 32, 1, None)
+    rc = L.wm_conv3x3_dgrad_applyfused(P(g), P(g), P(f), P(coef), P(wpt), P(g), P(g), P(g), P(f), P(f), P(part), 1, 16, 16, 32, 1, 0, None)
     assert rc < 0 and "CinP" in err()
-    rc = L.wm_conv3x3_dgrad_bwdstats(P(g), 64, 48, P(wpt), P(None), P(None), P(None), P(g), P(f), P(f), P(g), P(part), 1, 16, 16, 64, 1, None)
+    rc = L.wm_conv3x3_dgrad_bwdstats(P(g), 64, 48, P(wpt), P(None), P(None), P(None), P(g), P(f), P(f), P(g), P(part), 1, 16, 16, 64, 1, 0, None)
     assert rc < 0 and "unsupported" in err()
     # a rider with more than 256 partial rows is refused by the weight-gradient entry (python wrapper: assertion; C ABI: code)
     big = torch.zeros(300, 2, C, device="cuda")
@@ -942,7 +947,7 @@ def test_fused_backward_entry_points_fail_loudly():
                          invstd=f[3].data_ptr(), dgamma=0, dbeta=0, accumulate=0, coef=coef.data_ptr())
     ws = torch.zeros(ops._lib.lib().wm_conv3x3_wgrad_nslabs(1, 16, 16) * 9 * 64 * 64, device="cuda")
     dw = torch.zeros(C, C, 3, 3, device="cuda")
-    rc = L.wm_conv3x3_wgrad_fin(P(g), 64, 64, P(f[0]), P(f[1]), P(g), 64, 64, P(ws), P(dw), 0, 1, 16, 16, 64, 64, P(None), 1, ctypes.byref(st), None)
+    rc = L.wm_conv3x3_wgrad_fin(P(g), 64, 64, P(f[0]), P(f[1]), P(g), 64, 64, P(ws), P(dw), 0, 1, 16, 16, 64, 64, P(None), 1, ctypes.byref(st), 0, None)
     assert rc < 0 and "rider" in err()
     torch.cuda.synchronize()
 

@@ -5,7 +5,6 @@ whose results are wrong by construction (a probe inside the training step would 
 
 fwd: the forward 64 -> 64 convolution (fused input transform, BatchNorm statistics); bwd: the one-pass backward (premasked form).
 B = 16, 256 x 256, bf16; 40 launches per measurement, the variants interleaved, `rounds` rounds; prints the median per launch."""
-import ctypes
 import os
 import sys
 
@@ -23,9 +22,7 @@ for n in names:
     if n == "release":
         libs[n] = release
         continue
-    L = ctypes.CDLL(os.path.join(ROOT, "tools", "micro", "ab", f"libwm_hip_{n}.so"))
-    L.wm_last_error_string.restype = ctypes.c_char_p
-    libs[n] = L
+    libs[n] = _lib._load(os.path.join(ROOT, "tools", "micro", "ab", f"libwm_hip_{n}.so"))   # typed from the header, as the release handle
 B, H, W, C, dt = 16, 256, 256, 64, torch.bfloat16
 torch.manual_seed(0)
 g = torch.randn(B, H, W, C, device="cuda").to(dt); y = torch.randn(B, H, W, C, device="cuda").to(dt); xr = torch.randn(B, H, W, C, device="cuda").to(dt)

@@ -8,7 +8,6 @@ fixed part is paid by half as many workgroups and one chain's ramps / tails sit 
 
 Same process, same tensors, interleaved rounds: (a) release library, one stream, 2N launches; (b) variant library, two streams, N launches
 each.  Kernels: the forward 64 -> 64 conv (BatchNorm statistics, fused input transform) and the one-pass backward (premasked form)."""
-import ctypes
 import os
 import sys
 import time
@@ -21,8 +20,7 @@ from video_watermarking_forgery_detection_amd import _lib, ops                  
 name = sys.argv[1]
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 full = _lib.lib()
-half = ctypes.CDLL(os.path.join(ROOT, "tools", "micro", "ab", f"libwm_hip_{name}.so"))
-half.wm_last_error_string.restype = ctypes.c_char_p
+half = _lib._load(os.path.join(ROOT, "tools", "micro", "ab", f"libwm_hip_{name}.so"))   # typed from the header, as the release handle
 B, H, W, C, dt = 16, 256, 256, 64, torch.bfloat16
 torch.manual_seed(0)
 N = 12

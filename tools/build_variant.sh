@@ -9,7 +9,8 @@ C=$ROOT/video_watermarking_forgery_detection_amd/csrc
 name=$1; srcs=",$2,"; defs=$3
 python -m video_watermarking_forgery_detection_amd.build > /dev/null
 mkdir -p $ROOT/tools/micro/ab /tmp/wmvar_$name
-FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -fno-slp-vectorize -Rpass-analysis=kernel-resource-usage"
+# the release compile of one source (build.py's FLAGS and per-file extras): a variant differs from it by $defs only
+flags() { PYTHONPATH=$ROOT python -c "import sys; from video_watermarking_forgery_detection_amd import build as b; print(' '.join(b.FLAGS + b.EXTRA.get(sys.argv[1], []) + [b.REMARK]))" $1; }
 objs=""
 for o in $C/_build/*.o; do
   case $o in *.dbg.o) continue;; esac
@@ -17,7 +18,7 @@ for o in $C/_build/*.o; do
   src=${b%.o}; f16=""
   case $src in *.f16) src=${src%.f16}; f16="-DWM_H16_F16";; esac
   case $srcs in
-    *,$src,*) /opt/rocm/bin/hipcc $FL $defs $f16 -I$C -x hip -c ${VARIANT_SRC_DIR:-$C}/$src -o /tmp/wmvar_$name/$b 2> /tmp/wmvar_$name/$b.log; objs="$objs /tmp/wmvar_$name/$b";;
+    *,$src,*) /opt/rocm/bin/hipcc $(flags $src) $defs $f16 -I$C -x hip -c ${VARIANT_SRC_DIR:-$C}/$src -o /tmp/wmvar_$name/$b 2> /tmp/wmvar_$name/$b.log; objs="$objs /tmp/wmvar_$name/$b";;
     *) objs="$objs $o";;
   esac
 done

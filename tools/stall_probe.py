@@ -27,9 +27,6 @@ class Wrap:
             if t1 - t0 > 0.002: slow.append(("inside", name, round((t1 - t0) * 1e3, 1)))
             last[0], last[1] = t1, name
             return r
-        if hasattr(f, "restype"):
-            try: g.restype = f.restype
-            except Exception: pass
         return g
 real = _lib.lib()
 _lib._lib = Wrap(real)

@@ -6,10 +6,15 @@ is raised.  Nothing under oracle/ is ever imported from here.
 Two builds of the same sources live in lib/: libwm_hip.so (release: no knobs, no environment variables, no state between
 calls) is what every product path loads; libwm_hip_dbg.so (-DWM_DEBUG: the wm_debug_* A/B switches) is loaded only on
 request, by tools/ and by the tests that compare a fused kernel with its unfused form (use_debug_library()).
+
+Every handle _load() returns is typed from include/wm_hip.h: each declared function carries the argtypes and restype of its
+prototype, so callers pass plain Python ints, floats, None and ctypes arrays, and a call with too few arguments raises.
 """
 import contextlib
 import ctypes
+import functools
 import os
+import re
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", "libwm_hip.so")
@@ -24,13 +29,73 @@ _release = None
 _debug = None
 
 
-def _load(path):
+# the header's C types -> ctypes.  Closed: a type not listed here is a load error, never an untyped argument
+_ARG = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+_RET = dict(_ARG, **{"const char*": ctypes.c_char_p})
+# `ret name(params);` from the start of a line, the parameter list possibly over several lines
+_DECL = re.compile(r"^[ \t]*([^;{}()#\n]*?)\s*\b(wm_\w+)\s*\(([^()]*)\)\s*;", re.M)
+
+
+def _argtype(param, fn):
+    m = re.fullmatch(r"(.*?[\s*])\s*\w+", param.strip(), flags=re.S)
+    if m is None:
+        raise RuntimeError(f"wm_hip.h: {fn}: unnamed or unparsed parameter {param.strip()!r}")
+    if "*" in m.group(1):
+        return ctypes.c_void_p       # device and host pointers alike: takes None, an int, a ctypes array or byref(struct)
+    t = " ".join(w for w in m.group(1).split() if w != "const")
+    if t not in _ARG:
+        raise RuntimeError(f"wm_hip.h: {fn}: parameter type {t!r} has no ctypes mapping")
+    return _ARG[t]
+
+
+def parse_header(text):
+    """{name: (restype, [argtypes])} of every wm_* function declared in `text` (a C header)"""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    sigs = {}
+    for ret, name, params in _DECL.findall(src):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RET:
+            raise RuntimeError(f"wm_hip.h: {name}: return type {ret!r} has no ctypes mapping")
+        sigs[name] = (_RET[ret], [] if params.strip() == "void" else [_argtype(p, name) for p in params.split(",")])
+    missed = set(re.findall(r"\b(wm_\w+)\s*\(", src)) - set(sigs)
+    if missed:
+        raise RuntimeError(f"wm_hip.h: declarations not parsed: {sorted(missed)}")
+    return sigs
+
+
+@functools.lru_cache(maxsize=None)
+def signatures():
+    """parse_header of include/wm_hip.h"""
+    from .build import HEADER      # (imported here: `python -m ...build` must not find this module already loaded)
+    with open(HEADER) as f:
+        return parse_header(f.read())
+
+
+@functools.lru_cache(maxsize=None)
+def debug_setters():
+    """names of the wm_debug_* switches (WM_KNOB in csrc/): void setter(int), exported by the -DWM_DEBUG build only"""
+    from .build import CSRC
+    names = set()
+    for f in os.listdir(CSRC):
+        if f.endswith((".hip", ".cpp")):
+            with open(os.path.join(CSRC, f)) as fh:
+                names.update(re.findall(r"^\s*WM_KNOB\(\s*\w+\s*,\s*(wm_debug_\w+)", fh.read(), flags=re.M))
+    return sorted(names)
+
+
+def _load(path, debug=False):
+    """a handle on `path` whose functions carry the header's argtypes and restype (debug=True: and the wm_debug_* setters')"""
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} not found: build it with `python -m video_watermarking_forgery_detection_amd.build` "
             "(there is no CPU / PyTorch fallback for the HIP path)")
     h = ctypes.CDLL(path)
-    h.wm_last_error_string.restype = ctypes.c_char_p
+    sigs = dict(signatures())
+    if debug:
+        sigs.update((n, (None, [ctypes.c_int])) for n in debug_setters())
+    for name, (restype, argtypes) in sigs.items():
+        fn = getattr(h, name)
+        fn.restype, fn.argtypes = restype, argtypes
     return h
 
 
@@ -52,7 +117,7 @@ def loaded_path():
 def debug_lib():
     global _debug
     if _debug is None:
-        _debug = _load(DEBUG_LIB_PATH)
+        _debug = _load(DEBUG_LIB_PATH, debug=True)
     return _debug
 
 
@@ -72,13 +137,3 @@ def check(rc, name):
     if rc != 0:
         msg = lib().wm_last_error_string().decode(errors="replace")
         raise RuntimeError(f"{name} failed (rc={rc}): {msg}")
-
-
-def ptr(t):
-    """raw device pointer of a tensor (or NULL for None)."""
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
-
-
-def stream_of(t=None):
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -17,10 +17,11 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 LIBDIR = os.path.join(PKG, "lib")
+HEADER = os.path.join(os.path.dirname(PKG), "include", "wm_hip.h")   # the C ABI: the only symbols the library exports
 LIB = os.path.join(LIBDIR, "libwm_hip.so")
 LIB_DEBUG = os.path.join(LIBDIR, "libwm_hip_dbg.so")   # -DWM_DEBUG: the wm_debug_* A/B switches (tools/, fused-vs-unfused tests)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # MFMA kernels: keep the compiler from SLP-packing scalar f32 VALU into v_pk_*_f32 -- packed f32 issues far slower
 # than two scalar ops beside MFMAs (MI355X_MICROARCH.md, constants table)
 MFMA_FILES = ("conv3x3_ws.hip", "bwd_ws.hip", "bwd_ws8.hip", "bwd_ws16.hip", "wgrad_ws.hip", "upconv_mfma.hip", "conv3x3_stream.hip", "concat_side.hip", "gconv.hip")
@@ -43,7 +44,7 @@ def _sources():
 
 def _deps_mtime():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs.append(os.path.join(PKG, "..", "include", "wm_hip.h"))
+    hdrs.append(HEADER)
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -36,7 +36,7 @@ void wm_set_error(const char* fmt, ...);
 // knob below is a compile-time constant there.  The -DWM_DEBUG build (lib/libwm_hip_dbg.so: tools/ab_step.py and the tests that
 // compare a fused kernel with its unfused form) turns them into process-global switches with wm_debug_* setters.
 #ifdef WM_DEBUG
-#define WM_KNOB(var, setter, dflt) static int var = (dflt); extern "C" void setter(int v) { var = v; }
+#define WM_KNOB(var, setter, dflt) static int var = (dflt); extern "C" __attribute__((visibility("default"))) void setter(int v) { var = v; }
 #else
 #define WM_KNOB(var, setter, dflt) static constexpr int var = (dflt)
 #endif

@@ -9,11 +9,6 @@ import torch
 
 from . import _lib
 
-c_int = ctypes.c_int
-c_float = ctypes.c_float
-c_size_t = ctypes.c_size_t
-c_double = ctypes.c_double
-
 WM_F32, WM_BF16, WM_F16 = 0, 1, 2
 _DT = {torch.float32: WM_F32, torch.bfloat16: WM_BF16, torch.float16: WM_F16}
 
@@ -48,11 +43,11 @@ def _wrote(*ts):
 
 
 def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _p(t):
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+    return None if t is None else t.data_ptr()
 
 
 def _host_floats(vals):
@@ -71,8 +66,8 @@ def jpeg_fwd(x, mode, tables, subsample=0, act16_dtype=None):
     B, _, H, W = x.shape
     a16 = torch.empty(B, H, W, 16, device=x.device, dtype=act16_dtype) if act16_dtype is not None else None
     tb = _host_floats(tables) if tables is not None else None
-    rc = _timed("jpeg_fwd", None, lambda: _lib.lib().wm_jpeg_fwd_act(_p(x), _p(y), _p(a16), c_int(dt_id(act16_dtype) if a16 is not None else WM_F32),
-                                                                     c_int(B), c_int(H), c_int(W), c_int(mode), tb, c_int(subsample), _stream()))
+    rc = _timed("jpeg_fwd", None, lambda: _lib.lib().wm_jpeg_fwd_act(_p(x), _p(y), _p(a16), dt_id(act16_dtype) if a16 is not None else WM_F32, B, H,
+                                                                     W, mode, tb, subsample, _stream()))
     _lib.check(rc, "wm_jpeg_fwd")
     return (y, a16) if act16_dtype is not None else y
 
@@ -84,8 +79,7 @@ def jpeg_bwd(x, gy, mode, tables, subsample=0):
     B, _, H, W = gy.shape
     tb = _host_floats(tables) if tables is not None else None
     xx = x.contiguous() if x is not None else None
-    rc = _timed("jpeg_bwd", None, lambda: _lib.lib().wm_jpeg_bwd(_p(xx), _p(gy), _p(gx), c_int(B), c_int(H), c_int(W), c_int(mode), tb,
-                                                                 c_int(subsample), _stream()))
+    rc = _timed("jpeg_bwd", None, lambda: _lib.lib().wm_jpeg_bwd(_p(xx), _p(gy), _p(gx), B, H, W, mode, tb, subsample, _stream()))
     _lib.check(rc, "wm_jpeg_bwd")
     return gx
 
@@ -100,8 +94,7 @@ def nchw_to_nhwc(x, out, C_off=0, zero_tail=0):
     _need_cuda(x, out)
     x = x.contiguous()
     B, C, H, W = x.shape
-    rc = _lib.lib().wm_nchw_to_nhwc(_p(x), _p(out), c_int(B), c_int(C), c_int(H), c_int(W), c_int(out.shape[-1]),
-                                    c_int(C_off), c_int(zero_tail), c_int(dtype_id(out)), _stream())
+    rc = _lib.lib().wm_nchw_to_nhwc(_p(x), _p(out), B, C, H, W, out.shape[-1], C_off, zero_tail, dtype_id(out), _stream())
     _lib.check(rc, "wm_nchw_to_nhwc")
     return out
 
@@ -113,7 +106,7 @@ def u8_hwc_to_planes(x, scale=1.0 / 255.0):
     x = x.contiguous()
     N, H, W, C = x.shape
     y = torch.empty(N, C, H, W, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_u8_hwc_to_planes(_p(x), _p(y), c_int(N), c_int(H), c_int(W), c_int(C), c_float(scale), _stream())
+    rc = _lib.lib().wm_u8_hwc_to_planes(_p(x), _p(y), N, H, W, C, scale, _stream())
     _lib.check(rc, "wm_u8_hwc_to_planes")
     return y
 
@@ -122,8 +115,7 @@ def nhwc_to_nchw(x, C, C_off=0):
     _need_cuda(x)
     B, H, W, ld = x.shape
     y = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_nhwc_to_nchw(_p(x), _p(y), c_int(B), c_int(C), c_int(H), c_int(W), c_int(ld), c_int(C_off),
-                                    c_int(dtype_id(x)), _stream())
+    rc = _lib.lib().wm_nhwc_to_nchw(_p(x), _p(y), B, C, H, W, ld, C_off, dtype_id(x), _stream())
     _lib.check(rc, "wm_nhwc_to_nchw")
     return y
 
@@ -132,8 +124,7 @@ def broadcast_to_nhwc(v, out, C_off):
     _need_cuda(v, out)
     v = v.contiguous().float()
     B, H, W, ld = out.shape
-    rc = _lib.lib().wm_broadcast_to_nhwc(_p(v), _p(out), c_int(B), c_int(v.shape[1]), c_int(H), c_int(W), c_int(ld),
-                                         c_int(C_off), c_int(dtype_id(out)), _stream())
+    rc = _lib.lib().wm_broadcast_to_nhwc(_p(v), _p(out), B, v.shape[1], H, W, ld, C_off, dtype_id(out), _stream())
     _lib.check(rc, "wm_broadcast_to_nhwc")
     return out
 
@@ -143,8 +134,7 @@ def concat_tail(msg, img, out, C_off):
     _need_cuda(msg, img, out)
     B, H, W, ld = out.shape
     msg = msg.contiguous().float(); img = img.contiguous().float()
-    rc = _lib.lib().wm_concat_tail(_p(msg), _p(img), _p(out), c_int(B), c_int(msg.shape[1]), c_int(H), c_int(W), c_int(ld),
-                                   c_int(C_off), c_int(ld - C_off), c_int(dtype_id(out)), _stream())
+    rc = _lib.lib().wm_concat_tail(_p(msg), _p(img), _p(out), B, msg.shape[1], H, W, ld, C_off, ld - C_off, dtype_id(out), _stream())
     _lib.check(rc, "wm_concat_tail")
     return out
 
@@ -154,16 +144,15 @@ def concat_full(x, scale, shift, msg, img, out, C):
     _need_cuda(x, msg, img, out)
     B, H, W, ld = out.shape
     msg = msg.contiguous().float(); img = img.contiguous().float()
-    rc = _lib.lib().wm_concat_full(_p(x), c_int(x.shape[-1]), _p(scale), _p(shift), _p(msg), _p(img), _p(out), c_int(B), c_int(C),
-                                   c_int(msg.shape[1]), c_int(H), c_int(W), c_int(ld), c_int(dtype_id(out)), _stream())
+    rc = _lib.lib().wm_concat_full(_p(x), x.shape[-1], _p(scale), _p(shift), _p(msg), _p(img), _p(out), B, C, msg.shape[1], H, W, ld, dtype_id(out),
+                                   _stream())
     _lib.check(rc, "wm_concat_full")
     return out
 
 
 def bnrelu_copy(x, scale, shift, out, C_off, C):
     B, H, W, ldx = x.shape
-    rc = _lib.lib().wm_bnrelu_copy(_p(x), c_int(ldx), _p(scale), _p(shift), _p(out), c_int(out.shape[-1]), c_int(C_off),
-                                   c_size_t(B * H * W), c_int(C), c_int(dtype_id(x)), _stream())
+    rc = _lib.lib().wm_bnrelu_copy(_p(x), ldx, _p(scale), _p(shift), _p(out), out.shape[-1], C_off, B * H * W, C, dtype_id(x), _stream())
     _lib.check(rc, "wm_bnrelu_copy")
     return out
 
@@ -175,8 +164,7 @@ def pack_w3x3(w, CoutP, CinP, dtype, perm=None, transpose=False):
     shape = (9, CinP, CoutP) if transpose else (9, CoutP, CinP)
     wp = torch.empty(shape, device=w.device, dtype=dtype)
     pa = _host_ints(perm) if perm is not None else None
-    rc = _lib.lib().wm_pack_w3x3(_p(w), _p(wp), c_int(Cout), c_int(Cin), c_int(CoutP), c_int(CinP), pa,
-                                 c_int(1 if transpose else 0), c_int(dtype_id(wp)), _stream())
+    rc = _lib.lib().wm_pack_w3x3(_p(w), _p(wp), Cout, Cin, CoutP, CinP, pa, 1 if transpose else 0, dtype_id(wp), _stream())
     _lib.check(rc, "wm_pack_w3x3")
     return wp
 
@@ -250,8 +238,7 @@ class PackPlan:
             return
         if self.jobs is None:
             self._build()
-        rc = _lib.lib().wm_pack_w3x3_batch(_p(self.jobs), c_int(self.njobs), c_size_t(self.max_elems),
-                                           c_int(dt_id(self.dtype)), _stream())
+        rc = _lib.lib().wm_pack_w3x3_batch(_p(self.jobs), self.njobs, self.max_elems, dt_id(self.dtype), _stream())
         _lib.check(rc, "wm_pack_w3x3_batch")
         for k, req in self.req.items():
             self.ver[k] = req[0]._version
@@ -260,7 +247,7 @@ class PackPlan:
 
 # ----------------------------------------------------------------------------- conv / bn
 def conv3x3_nparts(B, H, W, Cin, CoutP, dtype):
-    return _lib.lib().wm_conv3x3_nparts(c_int(B), c_int(H), c_int(W), c_int(Cin), c_int(CoutP), c_int(dt_id(dtype)))
+    return _lib.lib().wm_conv3x3_nparts(B, H, W, Cin, CoutP, dt_id(dtype))
 
 
 class _WmBnBwdFin(ctypes.Structure):   # include/wm_hip.h: WmBnBwdFin
@@ -291,7 +278,7 @@ def _fin_rider(fin):
 def _sweep(reverse):
     """sweep_reverse argument of the conv / dgrad / wgrad entry points: walk the tiles backwards (start where the producer of the
     input stopped -- its last tiles are still in the Infinity Cache)"""
-    return c_int(1 if reverse else 0)
+    return 1 if reverse else 0
 
 
 def conv3x3_fwd(x, wp, bias, in_scale, in_shift, want_stats, Cin=None, reverse=False):
@@ -305,8 +292,8 @@ def conv3x3_fwd(x, wp, bias, in_scale, in_shift, want_stats, Cin=None, reverse=F
     st = torch.empty(conv3x3_nparts(B, H, W, Cin, CoutP, x.dtype), 2, CoutP, device=x.device, dtype=torch.float32) if want_stats else None
     info = {"B": B, "H": H, "W": W, "Cin": Cin, "CoutP": CoutP, "xform": in_scale is not None, "dtype": x.dtype}
     rc = _timed("conv3x3_fwd", info, lambda: _lib.lib().wm_conv3x3_fwd(
-        _p(x), c_int(ldx), _p(wp), _p(bias), c_int(0 if bias is None else bias.numel()), _p(in_scale), _p(in_shift),
-        _p(y), c_int(CoutP), _p(st), c_int(B), c_int(H), c_int(W), c_int(Cin), c_int(CoutP), c_int(dtype_id(x)), _sweep(reverse), _stream()))
+        _p(x), ldx, _p(wp), _p(bias), 0 if bias is None else bias.numel(), _p(in_scale), _p(in_shift), _p(y), CoutP, _p(st), B, H, W, Cin, CoutP,
+        dtype_id(x), _sweep(reverse), _stream()))
     _lib.check(rc, "wm_conv3x3_fwd")
     return y, st
 
@@ -320,8 +307,8 @@ def conv3x3_fwd_addin(x, wp, in_scale, in_shift, addend, reverse=False):
     y = torch.empty_like(x)
     st = torch.empty(conv3x3_nparts(B, H, W, 64, 64, x.dtype), 2, 64, device=x.device, dtype=torch.float32)
     info = {"B": B, "H": H, "W": W, "Cin": 64, "CoutP": 64, "xform": True, "dtype": x.dtype, "addin": True}
-    rc = _timed("conv3x3_fwd", info, lambda: _lib.lib().wm_conv3x3_fwd_addin(_p(x), _p(wp), _p(in_scale), _p(in_shift), _p(addend), _p(y), _p(st), c_int(B),
-                                                                             c_int(H), c_int(W), c_int(dtype_id(x)), _sweep(reverse), _stream()))
+    rc = _timed("conv3x3_fwd", info, lambda: _lib.lib().wm_conv3x3_fwd_addin(_p(x), _p(wp), _p(in_scale), _p(in_shift), _p(addend), _p(y), _p(st), B,
+                                                                             H, W, dtype_id(x), _sweep(reverse), _stream()))
     _lib.check(rc, "wm_conv3x3_fwd_addin")
     return y, st
 
@@ -337,8 +324,8 @@ def concat_side_fwd(img, w, bias, msg, dtype, c_msg, L, c_img):
     P = torch.empty(B, H, W, 64, device=img.device, dtype=dtype)
     wside = torch.empty(64 * 32, device=img.device, dtype=dtype)
     mbias = torch.empty(B, 9, 64, device=img.device, dtype=torch.float32)
-    rc = _lib.lib().wm_concat_side_fwd(_p(img), _p(w), _p(bias), _p(msg), _p(wside), _p(mbias), _p(P), c_int(B), c_int(H), c_int(W), c_int(Cin),
-                                       c_int(c_msg), c_int(L), c_int(c_img), c_int(dt_id(dtype)), _stream())
+    rc = _lib.lib().wm_concat_side_fwd(_p(img), _p(w), _p(bias), _p(msg), _p(wside), _p(mbias), _p(P), B, H, W, Cin, c_msg, L, c_img, dt_id(dtype),
+                                       _stream())
     _lib.check(rc, "wm_concat_side_fwd")
     return P
 
@@ -350,17 +337,16 @@ def concat_side_msg_wgrad(dy, msg, dw, accumulate, c_msg, L):
     msg = msg.contiguous().float()
     partial = torch.empty(B, _lib.lib().wm_concat_side_partial_rows(), 64, device=dy.device, dtype=torch.float32)
     S = torch.empty(B, 9, 64, device=dy.device, dtype=torch.float32)
-    rc = _lib.lib().wm_concat_side_msg_wgrad(_p(dy), _p(msg), _p(partial), _p(S), _p(dw), c_int(1 if accumulate else 0), c_int(B), c_int(H), c_int(W),
-                                             c_int(dw.shape[1]), c_int(c_msg), c_int(L), c_int(dtype_id(dy)), _stream())
+    rc = _lib.lib().wm_concat_side_msg_wgrad(_p(dy), _p(msg), _p(partial), _p(S), _p(dw), 1 if accumulate else 0, B, H, W, dw.shape[1], c_msg, L,
+                                             dtype_id(dy), _stream())
     _lib.check(rc, "wm_concat_side_msg_wgrad")
 
 
 def bn_finalize(partials, C, CP, count, gamma, beta, running_mean, running_var, momentum, eps):
     dev = partials.device
     out = torch.empty(4, CP, device=dev, dtype=torch.float32)  # scale, shift, mean, invstd
-    rc = _lib.lib().wm_bn_finalize(_p(partials), c_int(partials.shape[0]), c_int(C), c_int(CP), c_double(count), _p(gamma),
-                                   _p(beta), _p(running_mean), _p(running_var), c_float(momentum), c_float(eps),
-                                   _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _stream())
+    rc = _lib.lib().wm_bn_finalize(_p(partials), partials.shape[0], C, CP, count, _p(gamma), _p(beta), _p(running_mean), _p(running_var), momentum,
+                                   eps, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _stream())
     _lib.check(rc, "wm_bn_finalize")
     return out
 
@@ -371,16 +357,16 @@ def bn_bwd_coef(g, gvec, y, stats, C, gamma, dgamma, dbeta, accumulate):
     B, H, W, CP = y.shape
     hw = H * W
     L = _lib.lib()
-    nparts = L.wm_bn_bwd_nparts(c_size_t(B * hw))
+    nparts = L.wm_bn_bwd_nparts(B * hw)
     dev = y.device
     part = torch.empty(nparts, 2, CP, device=dev, dtype=torch.float32)
-    ldg = c_int(0 if g is None else g.shape[-1])
-    rc = L.wm_bn_bwd_reduce(_p(g), ldg, _p(gvec), _p(y), c_int(CP), _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]),
-                            _p(part), c_int(B), c_size_t(hw), c_int(CP), c_int(dtype_id(y)), _stream())
+    ldg = 0 if g is None else g.shape[-1]
+    rc = L.wm_bn_bwd_reduce(_p(g), ldg, _p(gvec), _p(y), CP, _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(part), B, hw, CP, dtype_id(y),
+                            _stream())
     _lib.check(rc, "wm_bn_bwd_reduce")
     coef = torch.empty(3, CP, device=dev, dtype=torch.float32)
-    rc = L.wm_bn_bwd_finalize(_p(part), c_int(nparts), c_int(C), c_int(CP), c_double(B * hw), _p(gamma), _p(stats[3]),
-                              _p(dgamma), _p(dbeta), c_int(1 if accumulate else 0), _p(coef), _stream())
+    rc = L.wm_bn_bwd_finalize(_p(part), nparts, C, CP, B * hw, _p(gamma), _p(stats[3]), _p(dgamma), _p(dbeta), 1 if accumulate else 0, _p(coef),
+                              _stream())
     _lib.check(rc, "wm_bn_bwd_finalize")
     return coef
 
@@ -390,9 +376,8 @@ def bn_bwd_coef_raw(partials, y, stats, C, gamma, dgamma, dbeta, accumulate):
     (conv3x3_dgrad_bwdstats): no pass over (g, y)."""
     B, H, W, CP = y.shape
     coef = torch.empty(3, CP, device=y.device, dtype=torch.float32)
-    rc = _lib.lib().wm_bn_bwd_finalize_raw(_p(partials), c_int(partials.shape[0]), c_int(C), c_int(CP), c_double(B * H * W), _p(gamma),
-                                           _p(stats[2]), _p(stats[3]), _p(dgamma), _p(dbeta), c_int(1 if accumulate else 0), _p(coef),
-                                           _stream())
+    rc = _lib.lib().wm_bn_bwd_finalize_raw(_p(partials), partials.shape[0], C, CP, B * H * W, _p(gamma), _p(stats[2]), _p(stats[3]), _p(dgamma),
+                                           _p(dbeta), 1 if accumulate else 0, _p(coef), _stream())
     _lib.check(rc, "wm_bn_bwd_finalize_raw")
     return coef
 
@@ -407,12 +392,12 @@ def bn_bwd(g, gvec, y, stats, C, gamma, dgamma, dbeta, accumulate, dbias, coef=N
     dev = y.device
     if coef is None:
         coef = bn_bwd_coef(g, gvec, y, stats, C, gamma, dgamma, dbeta, accumulate)
-    nparts = L.wm_bn_bwd_nparts(c_size_t(B * hw))
-    ldg = c_int(0 if g is None else g.shape[-1])
+    nparts = L.wm_bn_bwd_nparts(B * hw)
+    ldg = 0 if g is None else g.shape[-1]
     dy = torch.empty_like(y)
     bpart = torch.empty(nparts, CP, device=dev, dtype=torch.float32) if dbias is not None else None
-    rc = L.wm_bn_bwd_apply(_p(g), ldg, _p(gvec), _p(y), c_int(CP), _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]),
-                           _p(coef), _p(dy), c_int(CP), _p(bpart), c_int(B), c_size_t(hw), c_int(CP), c_int(dtype_id(y)), _stream())
+    rc = L.wm_bn_bwd_apply(_p(g), ldg, _p(gvec), _p(y), CP, _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(coef), _p(dy), CP, _p(bpart),
+                           B, hw, CP, dtype_id(y), _stream())
     _lib.check(rc, "wm_bn_bwd_apply")
     if dbias is not None:
         colsum(bpart, dbias.numel(), CP, dbias, accumulate)
@@ -420,7 +405,7 @@ def bn_bwd(g, gvec, y, stats, C, gamma, dgamma, dbeta, accumulate, dbias, coef=N
 
 
 def conv3x3_wgrad_bnfused_supported(CinX, CoutY, dtype):
-    return bool(_lib.lib().wm_conv3x3_wgrad_bnfused_supported(c_int(CinX), c_int(CoutY), c_int(dt_id(dtype))))
+    return bool(_lib.lib().wm_conv3x3_wgrad_bnfused_supported(CinX, CoutY, dt_id(dtype)))
 
 
 def conv3x3_wgrad_bnfused(x, g, y, stats, coef, dw, accumulate):
@@ -429,19 +414,17 @@ def conv3x3_wgrad_bnfused(x, g, y, stats, coef, dw, accumulate):
     B, H, W, ldx = x.shape
     CoutY = y.shape[-1]
     L = _lib.lib()
-    L.wm_conv3x3_wgrad_ws_bytes.restype = c_size_t
-    nbytes = L.wm_conv3x3_wgrad_ws_bytes(c_int(B), c_int(H), c_int(W), c_int(ldx), c_int(CoutY))
+    nbytes = L.wm_conv3x3_wgrad_ws_bytes(B, H, W, ldx, CoutY)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
     Cout, Cin = dw.shape[0], dw.shape[1]
     assert dw.is_contiguous() and stats.is_contiguous() and coef.is_contiguous()
-    rc = L.wm_conv3x3_wgrad_bnfused(_p(x), c_int(ldx), c_int(ldx), _p(g), c_int(g.shape[-1]), _p(y), c_int(CoutY), c_int(CoutY),
-                                    _p(stats), _p(coef), _p(ws), _p(dw), c_int(1 if accumulate else 0), c_int(B), c_int(H), c_int(W),
-                                    c_int(Cin), c_int(Cout), c_int(dtype_id(x)), _stream())
+    rc = L.wm_conv3x3_wgrad_bnfused(_p(x), ldx, ldx, _p(g), g.shape[-1], _p(y), CoutY, CoutY, _p(stats), _p(coef), _p(ws), _p(dw),
+                                    1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x), _stream())
     _lib.check(rc, "wm_conv3x3_wgrad_bnfused")
 
 
 def conv3x3_gvfused_supported(CinX, CoutY, dtype):
-    return bool(_lib.lib().wm_conv3x3_gvfused_supported(c_int(CinX), c_int(CoutY), c_int(dt_id(dtype))))
+    return bool(_lib.lib().wm_conv3x3_gvfused_supported(CinX, CoutY, dt_id(dtype)))
 
 
 def conv3x3_wgrad_gvfused(x, in_scale, in_shift, gvec, y, stats, coef, dw, accumulate, fin=None):
@@ -450,15 +433,14 @@ def conv3x3_wgrad_gvfused(x, in_scale, in_shift, gvec, y, stats, coef, dw, accum
     B, H, W, ldx = x.shape
     CoutY = y.shape[-1]
     L = _lib.lib()
-    L.wm_conv3x3_wgrad_ws_bytes.restype = c_size_t
-    nbytes = L.wm_conv3x3_wgrad_ws_bytes(c_int(B), c_int(H), c_int(W), c_int(ldx), c_int(CoutY))
+    nbytes = L.wm_conv3x3_wgrad_ws_bytes(B, H, W, ldx, CoutY)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
     Cout, Cin = dw.shape[0], dw.shape[1]
     assert dw.is_contiguous() and stats.is_contiguous() and coef.is_contiguous() and gvec.is_contiguous() and gvec.shape[-1] == CoutY
     fst, fcoef = _fin_rider(fin)
-    rc = L.wm_conv3x3_wgrad_gvfused_fin(_p(x), c_int(ldx), c_int(ldx), _p(in_scale), _p(in_shift), _p(gvec), _p(y), c_int(CoutY), c_int(CoutY),
-                                        _p(stats), _p(coef), _p(ws), _p(dw), c_int(1 if accumulate else 0), c_int(B), c_int(H), c_int(W),
-                                        c_int(Cin), c_int(Cout), c_int(dtype_id(x)), ctypes.byref(fst) if fst is not None else None, _stream())
+    rc = L.wm_conv3x3_wgrad_gvfused_fin(_p(x), ldx, ldx, _p(in_scale), _p(in_shift), _p(gvec), _p(y), CoutY, CoutY, _p(stats), _p(coef), _p(ws),
+                                        _p(dw), 1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x),
+                                        ctypes.byref(fst) if fst is not None else None, _stream())
     _lib.check(rc, "wm_conv3x3_wgrad_gvfused")
     return fcoef
 
@@ -469,14 +451,14 @@ def conv3x3_dgrad_gvfused(y, wpt, gvec, stats, coef):
     CinP = wpt.shape[1]
     assert wpt.shape[2] == CoutY and stats.is_contiguous() and coef.is_contiguous() and gvec.is_contiguous()
     dx = torch.empty(B, H, W, CinP, device=y.device, dtype=y.dtype)
-    rc = _lib.lib().wm_conv3x3_dgrad_gvfused(_p(y), c_int(CoutY), c_int(CoutY), _p(wpt), _p(gvec), _p(stats), _p(coef), _p(dx), c_int(B),
-                                             c_int(H), c_int(W), c_int(CinP), c_int(dtype_id(y)), _stream())
+    rc = _lib.lib().wm_conv3x3_dgrad_gvfused(_p(y), CoutY, CoutY, _p(wpt), _p(gvec), _p(stats), _p(coef), _p(dx), B, H, W, CinP, dtype_id(y),
+                                             _stream())
     _lib.check(rc, "wm_conv3x3_dgrad_gvfused")
     return dx
 
 
 def conv3x3_dgrad_bwdstats_supported(CoutY, CinP, dtype):
-    return bool(_lib.lib().wm_conv3x3_dgrad_bwdstats_supported(c_int(CoutY), c_int(CinP), c_int(dt_id(dtype))))
+    return bool(_lib.lib().wm_conv3x3_dgrad_bwdstats_supported(CoutY, CinP, dt_id(dtype)))
 
 
 def conv3x3_dgrad_bwdstats(src, wpt, ry, r_scale, r_shift, gvec=None, stats=None, coef=None, reverse=False):
@@ -489,16 +471,15 @@ def conv3x3_dgrad_bwdstats(src, wpt, ry, r_scale, r_shift, gvec=None, stats=None
     assert (gvec is None) == (stats is None) == (coef is None)
     dx = torch.empty(B, H, W, CinP, device=src.device, dtype=src.dtype)
     part = torch.empty(conv3x3_nparts(B, H, W, CoutY, CinP, src.dtype), 2, CinP, device=src.device, dtype=torch.float32)
-    rc = _lib.lib().wm_conv3x3_dgrad_bwdstats(_p(src), c_int(lds), c_int(CoutY), _p(wpt), _p(gvec), _p(stats), _p(coef), _p(ry), _p(r_scale),
-                                              _p(r_shift), _p(dx), _p(part), c_int(B), c_int(H), c_int(W), c_int(CinP),
-                                              c_int(dtype_id(src)), _sweep(reverse), _stream())
+    rc = _lib.lib().wm_conv3x3_dgrad_bwdstats(_p(src), lds, CoutY, _p(wpt), _p(gvec), _p(stats), _p(coef), _p(ry), _p(r_scale), _p(r_shift), _p(dx),
+                                              _p(part), B, H, W, CinP, dtype_id(src), _sweep(reverse), _stream())
     _lib.check(rc, "wm_conv3x3_dgrad_bwdstats")
     dx._wm_masked = True   # the kernel writes gz = g * [z > 0] of the feeding layer (what conv3x3_bwd_fused's premasked staging expects)
     return dx, part
 
 
 def conv3x3_dgrad_applyfused_supported(CoutY, CinP, dtype):
-    return bool(_lib.lib().wm_conv3x3_dgrad_applyfused_supported(c_int(CoutY), c_int(CinP), c_int(dt_id(dtype))))
+    return bool(_lib.lib().wm_conv3x3_dgrad_applyfused_supported(CoutY, CinP, dt_id(dtype)))
 
 
 def conv3x3_dgrad_applyfused(g, y, stats, coef, wpt, ry=None, r_scale=None, r_shift=None, reverse=False, want_dy=True):
@@ -514,8 +495,8 @@ def conv3x3_dgrad_applyfused(g, y, stats, coef, wpt, ry=None, r_scale=None, r_sh
     part = torch.empty(conv3x3_nparts(B, H, W, 64, 64, y.dtype), 2, 64, device=y.device, dtype=torch.float32) if ry is not None else None
     info = {"B": B, "H": H, "W": W, "feed": ry is not None, "dtype": y.dtype}
     rc = _timed("conv3x3_dgrad_applyfused", info, lambda: _lib.lib().wm_conv3x3_dgrad_applyfused(
-        _p(g), _p(y), _p(stats), _p(coef), _p(wpt), _p(dy), _p(dx), _p(ry), _p(r_scale), _p(r_shift), _p(part), c_int(B), c_int(H), c_int(W),
-        c_int(CinP), c_int(dtype_id(y)), _sweep(reverse), _stream()))
+        _p(g), _p(y), _p(stats), _p(coef), _p(wpt), _p(dy), _p(dx), _p(ry), _p(r_scale), _p(r_shift), _p(part), B, H, W, CinP, dtype_id(y),
+        _sweep(reverse), _stream()))
     _lib.check(rc, "wm_conv3x3_dgrad_applyfused")
     if ry is not None:
         dx._wm_masked = True   # as conv3x3_dgrad_bwdstats
@@ -525,8 +506,8 @@ def conv3x3_dgrad_applyfused(g, y, stats, coef, wpt, ry=None, r_scale=None, r_sh
 def conv3x3_bwd_fused_supported(dtype, shape=None):
     """the one-kernel backward exists for this dtype (and, given y's shape [B,H,W,64], the tensor fits its 32-bit offsets)"""
     if shape is None:
-        return bool(_lib.lib().wm_conv3x3_bwd_fused_supported(c_int(dt_id(dtype))))
-    return bool(_lib.lib().wm_conv3x3_bwd_fused_supported_shape(c_int(shape[0]), c_int(shape[1]), c_int(shape[2]), c_int(dt_id(dtype))))
+        return bool(_lib.lib().wm_conv3x3_bwd_fused_supported(dt_id(dtype)))
+    return bool(_lib.lib().wm_conv3x3_bwd_fused_supported_shape(shape[0], shape[1], shape[2], dt_id(dtype)))
 
 
 def conv3x3_bwd_fused_gvec_max_batch():
@@ -545,7 +526,7 @@ def conv3x3_bwd_fused(g, y, stats, coef, wpt, xr, in_scale, in_shift, dw, accumu
     assert (g.shape == y.shape and g.is_contiguous()) if g is not None else (tuple(gvec.shape) == (B, 64) and gvec.is_contiguous() and gvec.dtype == torch.float32)
     assert tuple(wpt.shape) == (9, 64, 64) and stats.is_contiguous() and coef.is_contiguous() and dw.is_contiguous()
     L = _lib.lib()
-    nwg = L.wm_conv3x3_bwd_fused_nwg(c_int(B), c_int(H), c_int(W))
+    nwg = L.wm_conv3x3_bwd_fused_nwg(B, H, W)
     dx = torch.empty_like(y)
     part = torch.empty(nwg, 2, 64, device=y.device, dtype=torch.float32)
     fst, fcoef = _fin_rider(fin(part) if callable(fin) else fin)     # fin: a rider dict, or a function of the partial rows this call produces
@@ -553,11 +534,11 @@ def conv3x3_bwd_fused(g, y, stats, coef, wpt, xr, in_scale, in_shift, dw, accumu
     Cout, Cin = dw.shape[0], dw.shape[1]
     info = {"B": B, "H": H, "W": W, "dtype": y.dtype, "gvec": gvec is not None}
     rc = _timed("conv3x3_bwd_fused", info, lambda: L.wm_conv3x3_bwd_fused(
-        _p(g), _p(gvec), _p(y), _p(stats), _p(coef), _p(wpt), _p(xr), _p(in_scale), _p(in_shift), _p(dx), _p(part), _p(ws), c_int(B), c_int(H),
-        c_int(W), c_int(dtype_id(y)), c_int(1 if premasked else 0), _sweep(reverse), _stream()))
+        _p(g), _p(gvec), _p(y), _p(stats), _p(coef), _p(wpt), _p(xr), _p(in_scale), _p(in_shift), _p(dx), _p(part), _p(ws), B, H, W, dtype_id(y),
+        1 if premasked else 0, _sweep(reverse), _stream()))
     _lib.check(rc, "wm_conv3x3_bwd_fused")
-    rc = L.wm_conv3x3_bwd_fused_reduce(_p(ws), _p(dw), c_int(1 if accumulate else 0), c_int(B), c_int(H), c_int(W), c_int(Cin), c_int(Cout),
-                                       ctypes.byref(fst) if fst is not None else None, _stream())
+    rc = L.wm_conv3x3_bwd_fused_reduce(_p(ws), _p(dw), 1 if accumulate else 0, B, H, W, Cin, Cout, ctypes.byref(fst) if fst is not None else None,
+                                       _stream())
     _lib.check(rc, "wm_conv3x3_bwd_fused_reduce")
     dx._wm_masked = True
     return dx, part, fcoef
@@ -565,7 +546,7 @@ def conv3x3_bwd_fused(g, y, stats, coef, wpt, xr, in_scale, in_shift, dw, accumu
 
 def conv3x3_bwd_fused16_supported(shape, dtype):
     """the one-kernel backward of an image-fed first layer exists for y's shape [B,H,W,64] (whole 8x16 tiles) and dtype"""
-    return bool(_lib.lib().wm_conv3x3_bwd_fused16_supported(c_int(shape[0]), c_int(shape[1]), c_int(shape[2]), c_int(dt_id(dtype))))
+    return bool(_lib.lib().wm_conv3x3_bwd_fused16_supported(shape[0], shape[1], shape[2], dt_id(dtype)))
 
 
 def conv3x3_bwd_fused16(g, y, stats, coef, wpt, x, dw, accumulate, reverse=False, premasked=False):
@@ -575,13 +556,13 @@ def conv3x3_bwd_fused16(g, y, stats, coef, wpt, x, dw, accumulate, reverse=False
     assert C == 64 and g.shape == y.shape and g.is_contiguous() and y.is_contiguous() and tuple(x.shape) == (B, H, W, 16) and x.is_contiguous()
     assert tuple(wpt.shape) == (9, 16, 64) and stats.is_contiguous() and coef.is_contiguous() and dw.is_contiguous() and dw.shape[0] <= 64 and dw.shape[1] <= 16
     L = _lib.lib()
-    nwg = L.wm_conv3x3_bwd_fused16_nwg(c_int(B), c_int(H), c_int(W))
+    nwg = L.wm_conv3x3_bwd_fused16_nwg(B, H, W)
     dx = torch.empty(B, H, W, 16, device=y.device, dtype=y.dtype)
     ws = torch.empty(nwg * 9 * 16 * 64, device=y.device, dtype=torch.float32)
     info = {"B": B, "H": H, "W": W, "dtype": y.dtype}
     rc = _timed("conv3x3_bwd_fused16", info, lambda: L.wm_conv3x3_bwd_fused16(
-        _p(g), _p(y), _p(stats), _p(coef), _p(wpt), _p(x), _p(dx), _p(ws), _p(dw), c_int(1 if accumulate else 0), c_int(B), c_int(H), c_int(W),
-        c_int(dw.shape[1]), c_int(dw.shape[0]), c_int(dtype_id(y)), c_int(1 if premasked else 0), _sweep(reverse), _stream()))
+        _p(g), _p(y), _p(stats), _p(coef), _p(wpt), _p(x), _p(dx), _p(ws), _p(dw), 1 if accumulate else 0, B, H, W, dw.shape[1], dw.shape[0],
+        dtype_id(y), 1 if premasked else 0, _sweep(reverse), _stream()))
     _lib.check(rc, "wm_conv3x3_bwd_fused16")
     return dx
 
@@ -592,7 +573,7 @@ def linear_head_fwd(pooled, w, bias, I):
     B, ldp = pooled.shape
     O = w.shape[0]
     out = torch.empty(B, O, device=pooled.device, dtype=torch.float32)
-    rc = _lib.lib().wm_linear_head_fwd(_p(pooled), c_int(ldp), _p(w), _p(bias), _p(out), c_int(B), c_int(I), c_int(O), _stream())
+    rc = _lib.lib().wm_linear_head_fwd(_p(pooled), ldp, _p(w), _p(bias), _p(out), B, I, O, _stream())
     _lib.check(rc, "wm_linear_head_fwd")
     return out
 
@@ -604,14 +585,14 @@ def linear_head_bwd(pooled, w, g_out, dw, db, accumulate, CP, inv_hw):
     O, I = w.shape
     g = g_out.contiguous().float()
     gvec = torch.empty(B, CP, device=pooled.device, dtype=torch.float32)
-    rc = _lib.lib().wm_linear_head_bwd(_p(pooled), c_int(ldp), _p(w), _p(g), _p(dw), _p(db), c_int(1 if accumulate else 0), _p(gvec),
-                                       c_int(CP), c_float(inv_hw), c_int(B), c_int(I), c_int(O), _stream())
+    rc = _lib.lib().wm_linear_head_bwd(_p(pooled), ldp, _p(w), _p(g), _p(dw), _p(db), 1 if accumulate else 0, _p(gvec), CP, inv_hw, B, I, O,
+                                       _stream())
     _lib.check(rc, "wm_linear_head_bwd")
     return gvec
 
 
 def pooled_head_supported(B, CP, I, O):
-    return bool(_lib.lib().wm_pooled_head_supported(c_int(B), c_int(CP), c_int(I), c_int(O)))
+    return bool(_lib.lib().wm_pooled_head_supported(B, CP, I, O))
 
 
 def pooled_head(out3, I, w, bias, kind, target, messages, gscale, gscale_dev, dw, db, accumulate, inv_hw, C, count, gamma, stats, dgamma, dbeta):
@@ -627,10 +608,9 @@ def pooled_head(out3, I, w, bias, kind, target, messages, gscale, gscale_dev, dw
     gvec = torch.empty(B, CP, device=dev, dtype=torch.float32)
     coef = torch.empty(3, CP, device=dev, dtype=torch.float32)
     msg = messages.contiguous().float() if messages is not None else None
-    rc = _lib.lib().wm_pooled_head(_p(out3), c_int(B), c_int(CP), c_int(I), c_int(O), _p(w), _p(bias), c_int(kind), c_float(float(target)), _p(msg),
-                                   c_float(float(gscale)), _p(gscale_dev), _p(logits), _p(loss), _p(dw), _p(db), c_int(1 if accumulate else 0),
-                                   _p(gvec), c_float(inv_hw), c_int(C), c_double(float(count)), _p(gamma), _p(stats[2]), _p(stats[3]),
-                                   _p(dgamma), _p(dbeta), _p(coef), _stream())
+    rc = _lib.lib().wm_pooled_head(_p(out3), B, CP, I, O, _p(w), _p(bias), kind, float(target), _p(msg), float(gscale), _p(gscale_dev), _p(logits),
+                                   _p(loss), _p(dw), _p(db), 1 if accumulate else 0, _p(gvec), inv_hw, C, float(count), _p(gamma), _p(stats[2]),
+                                   _p(stats[3]), _p(dgamma), _p(dbeta), _p(coef), _stream())
     _lib.check(rc, "wm_pooled_head")
     return logits, loss, gvec, coef
 
@@ -642,8 +622,7 @@ def bce_logits(logits, target, gscale=1.0, want_grad=True, gscale_dev=None):
     x = logits.contiguous().float()
     loss = torch.empty(1, device=x.device, dtype=torch.float32)
     grad = torch.empty_like(x) if want_grad else None
-    rc = _lib.lib().wm_bce_logits(_p(x), c_float(float(target)), c_int(x.numel()), c_float(float(gscale)), _p(gscale_dev), _p(loss), _p(grad),
-                                  _stream())
+    rc = _lib.lib().wm_bce_logits(_p(x), float(target), x.numel(), float(gscale), _p(gscale_dev), _p(loss), _p(grad), _stream())
     _lib.check(rc, "wm_bce_logits")
     return loss, grad
 
@@ -654,7 +633,7 @@ def message_loss(decoded, messages, gscale, want_grad=True, gscale_dev=None):
     d = decoded.contiguous().float(); m = messages.contiguous().float()
     out = torch.empty(2, device=d.device, dtype=torch.float32)
     grad = torch.empty_like(d) if want_grad else None
-    rc = _lib.lib().wm_message_loss(_p(d), _p(m), c_int(d.numel()), c_float(float(gscale)), _p(gscale_dev), _p(out), _p(grad), _stream())
+    rc = _lib.lib().wm_message_loss(_p(d), _p(m), d.numel(), float(gscale), _p(gscale_dev), _p(out), _p(grad), _stream())
     _lib.check(rc, "wm_message_loss")
     return out, grad
 
@@ -662,15 +641,14 @@ def message_loss(decoded, messages, gscale, want_grad=True, gscale_dev=None):
 def hidden_metrics(enc_partials, n_img, msg2, adv, d_cover, d_enc, w_adv, w_enc, w_dec):
     """[7] f32: loss, encoder mse, decoder mse, bitwise error, adversarial bce, D(cover) bce, D(encoded) bce (one launch)"""
     out = torch.empty(7, device=enc_partials.device, dtype=torch.float32)
-    rc = _lib.lib().wm_hidden_metrics(_p(enc_partials), c_int(enc_partials.numel()), c_double(float(n_img)), _p(msg2), _p(adv), _p(d_cover),
-                                      _p(d_enc), c_float(w_adv), c_float(w_enc), c_float(w_dec), _p(out), _stream())
+    rc = _lib.lib().wm_hidden_metrics(_p(enc_partials), enc_partials.numel(), float(n_img), _p(msg2), _p(adv), _p(d_cover), _p(d_enc), w_adv, w_enc,
+                                      w_dec, _p(out), _stream())
     _lib.check(rc, "wm_hidden_metrics")
     return out
 
 
 def colsum(partials, C, ldp, out, accumulate):
-    rc = _lib.lib().wm_colsum_finalize(_p(partials), c_int(partials.shape[0]), c_int(C), c_int(ldp), _p(out),
-                                       c_int(1 if accumulate else 0), _stream())
+    rc = _lib.lib().wm_colsum_finalize(_p(partials), partials.shape[0], C, ldp, _p(out), 1 if accumulate else 0, _stream())
     _lib.check(rc, "wm_colsum_finalize")
 
 
@@ -680,21 +658,18 @@ def conv3x3_wgrad(x, CinX, in_scale, in_shift, dy, dw, accumulate, perm_dev=None
     B, H, W, ldx = x.shape
     CoutY = dy.shape[-1]
     L = _lib.lib()
-    L.wm_conv3x3_wgrad_ws_bytes.restype = c_size_t
-    nbytes = L.wm_conv3x3_wgrad_ws_bytes(c_int(B), c_int(H), c_int(W), c_int(CinX), c_int(CoutY))
+    nbytes = L.wm_conv3x3_wgrad_ws_bytes(B, H, W, CinX, CoutY)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
     Cout, Cin = dw.shape[0], dw.shape[1]
     assert dw.is_contiguous()
-    rc = L.wm_conv3x3_wgrad_fin(_p(x), c_int(ldx), c_int(CinX), _p(in_scale), _p(in_shift), _p(dy), c_int(CoutY), c_int(CoutY),
-                                _p(ws), _p(dw), c_int(1 if accumulate else 0), c_int(B), c_int(H), c_int(W), c_int(Cin),
-                                c_int(Cout), _p(perm_dev), c_int(dtype_id(x)), ctypes.byref(fst) if fst is not None else None, _sweep(reverse),
-                                _stream())
+    rc = L.wm_conv3x3_wgrad_fin(_p(x), ldx, CinX, _p(in_scale), _p(in_shift), _p(dy), CoutY, CoutY, _p(ws), _p(dw), 1 if accumulate else 0, B, H, W,
+                                Cin, Cout, _p(perm_dev), dtype_id(x), ctypes.byref(fst) if fst is not None else None, _sweep(reverse), _stream())
     _lib.check(rc, "wm_conv3x3_wgrad")
     return fcoef
 
 
 def conv3x3_fwd_elu_supported(Cin, CoutP, dtype):
-    return bool(_lib.lib().wm_conv3x3_fwd_elu_supported(c_int(Cin), c_int(CoutP), c_int(dt_id(dtype))))
+    return bool(_lib.lib().wm_conv3x3_fwd_elu_supported(Cin, CoutP, dt_id(dtype)))
 
 
 def conv3x3_fwd_elu(x, wp, bias):
@@ -704,14 +679,14 @@ def conv3x3_fwd_elu(x, wp, bias):
     Cin = wp.shape[2]
     assert wp.shape[1] == 64 and Cin <= ldx
     out = torch.empty(B, H, W, 64, device=x.device, dtype=x.dtype)
-    rc = _lib.lib().wm_conv3x3_fwd_elu(_p(x), c_int(ldx), _p(wp), _p(bias), c_int(0 if bias is None else bias.numel()), _p(out), c_int(B), c_int(H),
-                                       c_int(W), c_int(Cin), c_int(dtype_id(x)), c_int(0), _stream())
+    rc = _lib.lib().wm_conv3x3_fwd_elu(_p(x), ldx, _p(wp), _p(bias), 0 if bias is None else bias.numel(), _p(out), B, H, W, Cin, dtype_id(x), 0,
+                                       _stream())
     _lib.check(rc, "wm_conv3x3_fwd_elu")
     return out
 
 
 def conv3x3_dgrad_elufused_supported(CinP, dtype):
-    return bool(_lib.lib().wm_conv3x3_dgrad_elufused_supported(c_int(CinP), c_int(dt_id(dtype))))
+    return bool(_lib.lib().wm_conv3x3_dgrad_elufused_supported(CinP, dt_id(dtype)))
 
 
 def conv3x3_dgrad_elufused(g, out, wpt, want_gz=True, dx_stride=None):
@@ -726,9 +701,8 @@ def conv3x3_dgrad_elufused(g, out, wpt, want_gz=True, dx_stride=None):
     L = _lib.lib()
     dx = torch.empty(B, H, W, CinP, device=g.device, dtype=g.dtype)
     gz = torch.empty_like(g) if want_gz else None
-    part = torch.empty(L.wm_conv3x3_dgrad_elufused_nparts(c_int(B), c_int(H), c_int(W)), 64, device=g.device, dtype=torch.float32)
-    rc = L.wm_conv3x3_dgrad_elufused(_p(g), _p(out), _p(wpt), _p(dx), _p(gz), _p(part), c_int(B), c_int(H), c_int(W), c_int(CinP),
-                                     c_int(dtype_id(g)), c_int(0), _stream())
+    part = torch.empty(L.wm_conv3x3_dgrad_elufused_nparts(B, H, W), 64, device=g.device, dtype=torch.float32)
+    rc = L.wm_conv3x3_dgrad_elufused(_p(g), _p(out), _p(wpt), _p(dx), _p(gz), _p(part), B, H, W, CinP, dtype_id(g), 0, _stream())
     _lib.check(rc, "wm_conv3x3_dgrad_elufused")
     return dx, gz, part
 
@@ -738,13 +712,11 @@ def conv3x3_wgrad_bias(x, gz, dw, accumulate, bias_partials, db, db_accumulate):
     B, H, W, ldx = x.shape
     CoutY = gz.shape[-1]
     L = _lib.lib()
-    L.wm_conv3x3_wgrad_ws_bytes.restype = c_size_t
-    ws = torch.empty(L.wm_conv3x3_wgrad_ws_bytes(c_int(B), c_int(H), c_int(W), c_int(ldx), c_int(CoutY)) // 4, device=x.device, dtype=torch.float32)
+    ws = torch.empty(L.wm_conv3x3_wgrad_ws_bytes(B, H, W, ldx, CoutY) // 4, device=x.device, dtype=torch.float32)
     Cout, Cin = dw.shape[0], dw.shape[1]
     assert dw.is_contiguous() and db.is_contiguous() and db.numel() == Cout and bias_partials.is_contiguous() and bias_partials.shape[1] == CoutY
-    rc = L.wm_conv3x3_wgrad_bias(_p(x), c_int(ldx), c_int(ldx), _p(gz), c_int(CoutY), c_int(CoutY), _p(ws), _p(dw), c_int(1 if accumulate else 0),
-                                 c_int(B), c_int(H), c_int(W), c_int(Cin), c_int(Cout), c_int(dtype_id(x)), _p(bias_partials),
-                                 c_int(bias_partials.shape[0]), _p(db), c_int(1 if db_accumulate else 0), _stream())
+    rc = L.wm_conv3x3_wgrad_bias(_p(x), ldx, ldx, _p(gz), CoutY, CoutY, _p(ws), _p(dw), 1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x),
+                                 _p(bias_partials), bias_partials.shape[0], _p(db), 1 if db_accumulate else 0, _stream())
     _lib.check(rc, "wm_conv3x3_wgrad_bias")
 
 
@@ -754,11 +726,10 @@ def bnrelu_avgpool_stats(y, scale, shift):
     the active pixels.  Returns (pooled [B,CP], (N+ [B,CP], S+ [B,CP]))."""
     B, H, W, CP = y.shape
     L = _lib.lib()
-    S = L.wm_avgpool_slices(c_size_t(H * W))
+    S = L.wm_avgpool_slices(H * W)
     ws = torch.empty(B * S * 3 * CP, device=y.device, dtype=torch.float32)
     out3 = torch.empty(3, B, CP, device=y.device, dtype=torch.float32)
-    rc = L.wm_bnrelu_avgpool_stats(_p(y), c_int(CP), _p(scale), _p(shift), _p(out3), _p(ws), c_int(B), c_size_t(H * W), c_int(CP),
-                                   c_int(dtype_id(y)), _stream())
+    rc = L.wm_bnrelu_avgpool_stats(_p(y), CP, _p(scale), _p(shift), _p(out3), _p(ws), B, H * W, CP, dtype_id(y), _stream())
     _lib.check(rc, "wm_bnrelu_avgpool_stats")
     return out3[0], (out3[1], out3[2])
 
@@ -769,7 +740,7 @@ def pooled_bwd_rows(gvec, pool_stats):
     npos, ysum = pool_stats
     assert gvec.is_contiguous() and npos.is_contiguous() and ysum.is_contiguous() and npos.shape == gvec.shape
     rows = torch.empty(B, 2, CP, device=gvec.device, dtype=torch.float32)
-    rc = _lib.lib().wm_pooled_bn_bwd_rows(_p(gvec), _p(npos), _p(ysum), c_int(B), c_int(CP), _p(rows), _stream())
+    rc = _lib.lib().wm_pooled_bn_bwd_rows(_p(gvec), _p(npos), _p(ysum), B, CP, _p(rows), _stream())
     _lib.check(rc, "wm_pooled_bn_bwd_rows")
     return rows
 
@@ -780,9 +751,8 @@ def bn_bwd_coef_pooled(gvec, pool_stats, y, stats, C, gamma, dgamma, dbeta, accu
     npos, ysum = pool_stats
     assert gvec.is_contiguous() and npos.is_contiguous() and ysum.is_contiguous() and tuple(gvec.shape) == (B, CP) == tuple(npos.shape)
     coef = torch.empty(3, CP, device=y.device, dtype=torch.float32)
-    rc = _lib.lib().wm_bn_bwd_finalize_pooled(_p(gvec), _p(npos), _p(ysum), c_int(B), c_int(C), c_int(CP), c_double(B * H * W), _p(gamma),
-                                              _p(stats[2]), _p(stats[3]), _p(dgamma), _p(dbeta), c_int(1 if accumulate else 0), _p(coef),
-                                              _stream())
+    rc = _lib.lib().wm_bn_bwd_finalize_pooled(_p(gvec), _p(npos), _p(ysum), B, C, CP, B * H * W, _p(gamma), _p(stats[2]), _p(stats[3]), _p(dgamma),
+                                              _p(dbeta), 1 if accumulate else 0, _p(coef), _stream())
     _lib.check(rc, "wm_bn_bwd_finalize_pooled")
     return coef
 
@@ -790,11 +760,10 @@ def bn_bwd_coef_pooled(gvec, pool_stats, y, stats, C, gamma, dgamma, dbeta, accu
 def bnrelu_avgpool(y, scale, shift):
     B, H, W, CP = y.shape
     L = _lib.lib()
-    S = L.wm_avgpool_slices(c_size_t(H * W))
+    S = L.wm_avgpool_slices(H * W)
     ws = torch.empty(B * S * CP, device=y.device, dtype=torch.float32)
     out = torch.empty(B, CP, device=y.device, dtype=torch.float32)
-    rc = L.wm_bnrelu_avgpool(_p(y), c_int(CP), _p(scale), _p(shift), _p(out), _p(ws), c_int(B), c_size_t(H * W), c_int(CP),
-                             c_int(dtype_id(y)), _stream())
+    rc = L.wm_bnrelu_avgpool(_p(y), CP, _p(scale), _p(shift), _p(out), _p(ws), B, H * W, CP, dtype_id(y), _stream())
     _lib.check(rc, "wm_bnrelu_avgpool")
     return out
 
@@ -806,8 +775,8 @@ def conv1x1_head_fwd(y, scale, shift, w, bias, act=0, want_act16=False):
     Cout = w.shape[0]
     out = torch.empty(B, Cout, H, W, device=y.device, dtype=torch.float32)
     a16 = torch.empty(B, H, W, 16, device=y.device, dtype=y.dtype) if want_act16 else None
-    rc = _lib.lib().wm_conv1x1_head_fwd_act(_p(y), c_int(Cin), _p(scale), _p(shift), _p(w), _p(bias), _p(out), _p(a16), c_int(B),
-                                            c_size_t(H * W), c_int(Cin), c_int(Cout), c_int(act), c_int(dtype_id(y)), _stream())
+    rc = _lib.lib().wm_conv1x1_head_fwd_act(_p(y), Cin, _p(scale), _p(shift), _p(w), _p(bias), _p(out), _p(a16), B, H * W, Cin, Cout, act,
+                                            dtype_id(y), _stream())
     _lib.check(rc, "wm_conv1x1_head_fwd")
     return (out, a16) if want_act16 else out
 
@@ -818,13 +787,13 @@ def conv1x1_head_bwd(y, scale, shift, w, gout, dw, dbias, accumulate, want_bn_pa
     B, H, W, Cin = y.shape
     Cout = w.shape[0]
     L = _lib.lib()
-    nparts = L.wm_conv1x1_head_nparts(c_size_t(B * H * W))
+    nparts = L.wm_conv1x1_head_nparts(B * H * W)
     part = torch.empty(nparts, Cout * (Cin + 1), device=y.device, dtype=torch.float32)
     bnp = torch.empty(nparts, 2, Cin, device=y.device, dtype=torch.float32) if want_bn_partials and scale is not None else None
     g = torch.empty_like(y)
     gout = gout.contiguous()
-    rc = L.wm_conv1x1_head_bwd(_p(y), c_int(Cin), _p(scale), _p(shift), _p(w), _p(gout), _p(g), c_int(Cin), _p(part), _p(bnp), c_int(B),
-                               c_size_t(H * W), c_int(Cin), c_int(Cout), c_int(dtype_id(y)), _stream())
+    rc = L.wm_conv1x1_head_bwd(_p(y), Cin, _p(scale), _p(shift), _p(w), _p(gout), _p(g), Cin, _p(part), _p(bnp), B, H * W, Cin, Cout, dtype_id(y),
+                               _stream())
     _lib.check(rc, "wm_conv1x1_head_bwd")
     ldp = Cout * (Cin + 1)
     colsum(part, Cout * Cin, ldp, dw, accumulate)
@@ -843,7 +812,7 @@ def mse_fwd_bwd(a, b, gscale, want_grad=True, gscale_dev=None):
     nparts = max(1, min(1024, (n + 4095) // 4096))
     part = torch.empty(nparts, device=a.device, dtype=torch.float32)
     grad = torch.empty_like(a) if want_grad else None
-    rc = _lib.lib().wm_mse_fwd_bwd(_p(a), _p(b), _p(grad), c_float(gscale), _p(gscale_dev), _p(part), c_int(nparts), c_size_t(n), _stream())
+    rc = _lib.lib().wm_mse_fwd_bwd(_p(a), _p(b), _p(grad), gscale, _p(gscale_dev), _p(part), nparts, n, _stream())
     _lib.check(rc, "wm_mse_fwd_bwd")
     return part, grad
 
@@ -859,24 +828,23 @@ def image_grad_mse(g, a, b, gscale, C=3, C_off=0, gscale_dev=None):
     nparts = max(1, min(1024, (n + 4095) // 4096))
     out = torch.empty_like(a)
     part = torch.empty(nparts, device=a.device, dtype=torch.float32)
-    rc = _lib.lib().wm_image_grad_mse(_p(g), c_int(ld), c_int(C_off), _p(a), _p(b), _p(out), c_float(gscale), _p(gscale_dev), _p(part), c_int(nparts),
-                                      c_int(B), c_int(C), c_int(H), c_int(W), c_int(dtype_id(g)), _stream())
+    rc = _lib.lib().wm_image_grad_mse(_p(g), ld, C_off, _p(a), _p(b), _p(out), gscale, _p(gscale_dev), _p(part), nparts, B, C, H, W, dtype_id(g),
+                                      _stream())
     _lib.check(rc, "wm_image_grad_mse")
     return out, part
 
 
 def axpy_(a, b, s=1.0):
     assert a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
-    rc = _lib.lib().wm_axpy(_p(a), _p(b), c_float(s), c_size_t(a.numel()), _stream())
+    rc = _lib.lib().wm_axpy(_p(a), _p(b), s, a.numel(), _stream())
     _lib.check(rc, "wm_axpy")
     _wrote(a)
     return a
 
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, decoupled=False, grad_scale=1.0):
-    rc = _lib.lib().wm_adam_step(_p(p), _p(g), _p(m), _p(v), c_size_t(p.numel()), c_float(lr), c_float(beta1), c_float(beta2),
-                                 c_float(eps), c_float(weight_decay), c_int(1 if decoupled else 0), c_int(step),
-                                 c_float(grad_scale), _stream())
+    rc = _lib.lib().wm_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, 1 if decoupled else 0, step, grad_scale,
+                                 _stream())
     _lib.check(rc, "wm_adam_step")
     _wrote(p, m, v)
 
@@ -887,8 +855,8 @@ ADAM_HYPER = 8   # WM_ADAM_HYPER
 def adam_hyper(lr, beta1, beta2, step, eps, weight_decay):
     """the WM_ADAM_HYPER floats a replayed step reads (host arithmetic, no launch): (lr / (1 - beta1^step), sqrt(1 - beta2^step), lr, beta1,
     beta2, eps, weight_decay, 0) -- the first two exactly as wm_adam_step derives them, the rest rounded to f32 as its arguments are"""
-    out = (c_float * ADAM_HYPER)()
-    rc = _lib.lib().wm_adam_hyper(c_float(lr), c_float(beta1), c_float(beta2), c_float(eps), c_float(weight_decay), c_int(step), out)
+    out = (ctypes.c_float * ADAM_HYPER)()
+    rc = _lib.lib().wm_adam_hyper(lr, beta1, beta2, eps, weight_decay, step, out)
     _lib.check(rc, "wm_adam_hyper")
     return tuple(float(x) for x in out)
 
@@ -897,8 +865,7 @@ def adam_step_dev(p, g, m, v, hyper_dev, decoupled=False, grad_scale=1.0):
     """adam_step with every number but `decoupled` read from the device tensor hyper_dev [ADAM_HYPER] f32 (adam_hyper's block): what a
     captured step launches -- the caller refreshes hyper_dev before each replay"""
     assert hyper_dev.is_cuda and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= ADAM_HYPER and hyper_dev.is_contiguous()
-    rc = _lib.lib().wm_adam_step_dev(_p(p), _p(g), _p(m), _p(v), c_size_t(p.numel()), c_int(1 if decoupled else 0), _p(hyper_dev),
-                                     c_float(grad_scale), _stream())
+    rc = _lib.lib().wm_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), 1 if decoupled else 0, _p(hyper_dev), grad_scale, _stream())
     _lib.check(rc, "wm_adam_step_dev")
     _wrote(p, m, v)
 
@@ -928,11 +895,11 @@ class AmpState:
         parts = [nonfinite(g) for g in grads]
         arr = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
         ns = (ctypes.c_int * len(parts))(*[p.numel() for p in parts])
-        rc = _lib.lib().wm_amp_found_inf(arr, ns, c_int(len(parts)), _p(self.state), c_int(k), _stream())
+        rc = _lib.lib().wm_amp_found_inf(arr, ns, len(parts), _p(self.state), k, _stream())
         _lib.check(rc, "wm_amp_found_inf")
 
     def update(self):
-        rc = _lib.lib().wm_amp_update(_p(self.state), c_int(max(1, self.nopt)), _stream())
+        rc = _lib.lib().wm_amp_update(_p(self.state), max(1, self.nopt), _stream())
         _lib.check(rc, "wm_amp_update")
 
     def get_scale(self):
@@ -964,9 +931,8 @@ def adam_step_amp(p, g, m, v, lr, beta1, beta2, eps, weight_decay, amp, k, decou
     replace the arguments at each replay"""
     if hyper_dev is not None:
         assert hyper_dev.is_cuda and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= ADAM_HYPER and hyper_dev.is_contiguous()
-    rc = _lib.lib().wm_adam_step_amp(_p(p), _p(g), _p(m), _p(v), c_size_t(p.numel()), c_float(lr), c_float(beta1), c_float(beta2), c_float(eps),
-                                     c_float(weight_decay), c_int(1 if decoupled else 0), c_float(grad_scale), _p(amp.state), c_int(k),
-                                     _p(hyper_dev), _stream())
+    rc = _lib.lib().wm_adam_step_amp(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, 1 if decoupled else 0, grad_scale,
+                                     _p(amp.state), k, _p(hyper_dev), _stream())
     _lib.check(rc, "wm_adam_step_amp")
     _wrote(p, m, v)
 
@@ -975,7 +941,7 @@ def sumsq(x):
     n = x.numel()
     nparts = max(1, min(1024, (n + 4095) // 4096))
     part = torch.empty(nparts, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_sumsq(_p(x), c_size_t(n), _p(part), c_int(nparts), _stream())
+    rc = _lib.lib().wm_sumsq(_p(x), n, _p(part), nparts, _stream())
     _lib.check(rc, "wm_sumsq")
     return part
 
@@ -985,7 +951,7 @@ def nonfinite(x):
     n = x.numel()
     nparts = max(1, min(1024, (n + 4095) // 4096))
     part = torch.empty(nparts, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_nonfinite(_p(x), c_size_t(n), _p(part), c_int(nparts), _stream())
+    rc = _lib.lib().wm_nonfinite(_p(x), n, _p(part), nparts, _stream())
     _lib.check(rc, "wm_nonfinite")
     return part
 
@@ -996,7 +962,7 @@ def clamp_quant(x):
     _need_cuda(x)
     x = x.contiguous().float()
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_clamp_quant_fwd(_p(x), _p(y), c_size_t(x.numel()), _stream())
+    rc = _lib.lib().wm_clamp_quant_fwd(_p(x), _p(y), x.numel(), _stream())
     _lib.check(rc, "wm_clamp_quant_fwd")
     return y
 
@@ -1012,12 +978,12 @@ def splice_fwd(enc, real=None, prev=None, mask=None, want_fwd=False):
     tam = torch.empty_like(enc) if prev is not None else None
     part = None
     if real is not None:
-        part = torch.empty(L.wm_splice_nparts(c_size_t(enc.numel())), device=enc.device, dtype=torch.float64)
+        part = torch.empty(L.wm_splice_nparts(enc.numel()), device=enc.device, dtype=torch.float64)
         real = real.contiguous()
     if prev is not None:
         prev = prev.contiguous(); mask = mask.contiguous()
         assert prev.shape == enc.shape and tuple(mask.shape) == (B, 1, H, W) and mask.dtype == torch.float32
-    rc = L.wm_splice_fwd(_p(enc), _p(real), _p(prev), _p(mask), _p(fwd), _p(tam), _p(part), c_int(B), c_int(C), c_size_t(H * W), _stream())
+    rc = L.wm_splice_fwd(_p(enc), _p(real), _p(prev), _p(mask), _p(fwd), _p(tam), _p(part), B, C, H * W, _stream())
     _lib.check(rc, "wm_splice_fwd")
     return fwd, tam, part
 
@@ -1025,8 +991,7 @@ def splice_fwd(enc, real=None, prev=None, mask=None, want_fwd=False):
 def psnr_gate(partials, n, threshold=33.0, w_below=1.0, w_above=0.8):
     """[2] f32 device tensor: (PSNR, forward-loss weight) -- IRNcrop_model.py:379-388, no host sync"""
     out = torch.empty(2, device=partials.device, dtype=torch.float32)
-    rc = _lib.lib().wm_psnr_gate(_p(partials), c_int(partials.numel()), c_double(float(n)), c_float(threshold), c_float(w_below),
-                                 c_float(w_above), _p(out), _stream())
+    rc = _lib.lib().wm_psnr_gate(_p(partials), partials.numel(), float(n), threshold, w_below, w_above, _p(out), _stream())
     _lib.check(rc, "wm_psnr_gate")
     return out
 
@@ -1038,8 +1003,7 @@ def mse_fwd_bwd_gated(a, b, gscale, gate, gscale_dev=None):
     nparts = max(1, min(1024, (n + 4095) // 4096))
     part = torch.empty(nparts, device=a.device, dtype=torch.float32)
     grad = torch.empty_like(a)
-    rc = _lib.lib().wm_mse_fwd_bwd_gated(_p(a), _p(b), _p(grad), c_float(gscale), _p(gate), _p(gscale_dev), _p(part), c_int(nparts), c_size_t(n),
-                                         _stream())
+    rc = _lib.lib().wm_mse_fwd_bwd_gated(_p(a), _p(b), _p(grad), gscale, _p(gate), _p(gscale_dev), _p(part), nparts, n, _stream())
     _lib.check(rc, "wm_mse_fwd_bwd_gated")
     return part, grad
 
@@ -1055,8 +1019,8 @@ def bce_logits_target(p, target, gscale=1.0, want_grad=True, chain_sigmoid=False
     part = torch.empty(nparts, device=p.device, dtype=torch.float32)
     loss = torch.empty(1, device=p.device, dtype=torch.float32)
     grad = torch.empty_like(p) if want_grad else None
-    rc = _lib.lib().wm_bce_logits_target(_p(p), _p(target), c_size_t(n), c_float(gscale), _p(gscale_dev), _p(part), c_int(nparts), _p(loss), _p(grad),
-                                         c_int(1 if chain_sigmoid else 0), _stream())
+    rc = _lib.lib().wm_bce_logits_target(_p(p), _p(target), n, gscale, _p(gscale_dev), _p(part), nparts, _p(loss), _p(grad),
+                                         1 if chain_sigmoid else 0, _stream())
     _lib.check(rc, "wm_bce_logits_target")
     return loss, grad
 
@@ -1065,7 +1029,7 @@ def masked_axpy_(a, g, mask):
     """a += g * (1 - mask), mask [B,1,H,W] broadcast over channels"""
     B, C, H, W = a.shape
     assert a.is_contiguous() and g.is_contiguous() and g.shape == a.shape and mask.is_contiguous() and tuple(mask.shape) == (B, 1, H, W)
-    rc = _lib.lib().wm_masked_axpy(_p(a), _p(g), _p(mask), c_int(B), c_int(C), c_size_t(H * W), _stream())
+    rc = _lib.lib().wm_masked_axpy(_p(a), _p(g), _p(mask), B, C, H * W, _stream())
     _lib.check(rc, "wm_masked_axpy")
     _wrote(a)
     return a
@@ -1076,7 +1040,7 @@ def mask_threshold(p, threshold=0.5):
     _need_cuda(p)
     p = p.contiguous().float()
     out = torch.empty(p.shape, device=p.device, dtype=torch.uint8)
-    rc = _lib.lib().wm_mask_threshold(_p(p), c_float(threshold), _p(out), c_size_t(p.numel()), _stream())
+    rc = _lib.lib().wm_mask_threshold(_p(p), threshold, _p(out), p.numel(), _stream())
     _lib.check(rc, "wm_mask_threshold")
     return out
 
@@ -1090,10 +1054,10 @@ def clip_grad_norm_(flats, max_norm, parts=None):
     ns = (ctypes.c_int * len(parts))(*[p.numel() for p in parts])
     out = torch.empty(2, device=flats[0].device, dtype=torch.float32)
     L = _lib.lib()
-    rc = L.wm_clip_coef(arr, ns, c_int(len(parts)), c_float(float(max_norm)), _p(out), _stream())
+    rc = L.wm_clip_coef(arr, ns, len(parts), float(max_norm), _p(out), _stream())
     _lib.check(rc, "wm_clip_coef")
     for f in flats:
-        rc = L.wm_scale_dev(_p(f), c_size_t(f.numel()), _p(out), _stream())
+        rc = L.wm_scale_dev(_p(f), f.numel(), _p(out), _stream())
         _lib.check(rc, "wm_scale_dev")
     return out
 
@@ -1151,7 +1115,7 @@ def _planes(x):
 def stencil3(x, w9):
     x, N, H, W = _planes(x)
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_stencil3_fwd(_p(x), _p(y), c_int(N), c_int(H), c_int(W), _host_floats(w9), _stream())
+    rc = _lib.lib().wm_stencil3_fwd(_p(x), _p(y), N, H, W, _host_floats(w9), _stream())
     _lib.check(rc, "wm_stencil3_fwd")
     return y
 
@@ -1160,7 +1124,7 @@ def median_fwd(x, k, want_idx=True):
     x, N, H, W = _planes(x)
     y = torch.empty_like(x)
     idx = torch.empty(x.shape, device=x.device, dtype=torch.int8) if want_idx else None
-    rc = _lib.lib().wm_median_fwd(_p(x), _p(y), _p(idx), c_int(N), c_int(H), c_int(W), c_int(k), _stream())
+    rc = _lib.lib().wm_median_fwd(_p(x), _p(y), _p(idx), N, H, W, k, _stream())
     _lib.check(rc, "wm_median_fwd")
     return y, idx
 
@@ -1168,7 +1132,7 @@ def median_fwd(x, k, want_idx=True):
 def median_bwd(gy, idx, k):
     gy, N, H, W = _planes(gy)
     gx = torch.empty_like(gy)
-    rc = _lib.lib().wm_median_bwd(_p(gy), _p(idx), _p(gx), c_int(N), c_int(H), c_int(W), c_int(k), _stream())
+    rc = _lib.lib().wm_median_bwd(_p(gy), _p(idx), _p(gx), N, H, W, k, _stream())
     _lib.check(rc, "wm_median_bwd")
     return gx
 
@@ -1179,8 +1143,7 @@ def resample_fwd(x, rect, out_hw, kind, clamp01=False):
     h0, hs, w0, ws = rect
     OH, OW = out_hw
     y = torch.empty(x.shape[0], x.shape[1], OH, OW, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_resample_fwd(_p(x), _p(y), c_int(N), c_int(H), c_int(W), c_int(h0), c_int(hs), c_int(w0), c_int(ws),
-                                    c_int(OH), c_int(OW), c_int(kind), c_int(1 if clamp01 else 0), _stream())
+    rc = _lib.lib().wm_resample_fwd(_p(x), _p(y), N, H, W, h0, hs, w0, ws, OH, OW, kind, 1 if clamp01 else 0, _stream())
     _lib.check(rc, "wm_resample_fwd")
     return y
 
@@ -1195,12 +1158,10 @@ def resample_bwd(gy, y_clamped, in_hw, rect, kind, separable=True):
     yc = y_clamped.contiguous() if y_clamped is not None else None
     if separable:
         tmp = torch.empty(N, OH, W, device=gy.device, dtype=torch.float32)
-        rc = _lib.lib().wm_resample_bwd_sep(_p(gy), _p(yc), _p(gx), _p(tmp), c_int(N), c_int(H), c_int(W), c_int(h0), c_int(hs), c_int(w0),
-                                            c_int(ws), c_int(OH), c_int(OW), c_int(kind), _stream())
+        rc = _lib.lib().wm_resample_bwd_sep(_p(gy), _p(yc), _p(gx), _p(tmp), N, H, W, h0, hs, w0, ws, OH, OW, kind, _stream())
         _lib.check(rc, "wm_resample_bwd_sep")
         return gx
-    rc = _lib.lib().wm_resample_bwd(_p(gy), _p(yc), _p(gx), c_int(N), c_int(H), c_int(W), c_int(h0), c_int(hs), c_int(w0),
-                                    c_int(ws), c_int(OH), c_int(OW), c_int(kind), _stream())
+    rc = _lib.lib().wm_resample_bwd(_p(gy), _p(yc), _p(gx), N, H, W, h0, hs, w0, ws, OH, OW, kind, _stream())
     _lib.check(rc, "wm_resample_bwd")
     return gx
 
@@ -1209,7 +1170,7 @@ def quant(x):
     _need_cuda(x)
     x = x.contiguous().float()
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_quant_fwd(_p(x), _p(y), c_size_t(x.numel()), _stream())
+    rc = _lib.lib().wm_quant_fwd(_p(x), _p(y), x.numel(), _stream())
     _lib.check(rc, "wm_quant_fwd")
     return y
 
@@ -1220,9 +1181,8 @@ def bnrelu_maxpool2(y, scale, shift, C, act_out=None, act_c0=0):
     full-resolution map into act_out[..., act_c0:act_c0+C] (the skip half of a concat buffer)."""
     B, H, W, ld = y.shape
     pooled = torch.empty(B, H // 2, W // 2, C, device=y.device, dtype=y.dtype)
-    rc = _lib.lib().wm_bnrelu_maxpool2(_p(y), c_int(ld), _p(scale), _p(shift), _p(pooled), c_int(C), _p(act_out),
-                                       c_int(0 if act_out is None else act_out.shape[-1]), c_int(act_c0), c_int(B), c_int(H),
-                                       c_int(W), c_int(C), c_int(dtype_id(y)), _stream())
+    rc = _lib.lib().wm_bnrelu_maxpool2(_p(y), ld, _p(scale), _p(shift), _p(pooled), C, _p(act_out), 0 if act_out is None else act_out.shape[-1],
+                                       act_c0, B, H, W, C, dtype_id(y), _stream())
     _lib.check(rc, "wm_bnrelu_maxpool2")
     return pooled
 
@@ -1235,16 +1195,15 @@ def maxpool2_bwd(y, scale, shift, gpooled, g_skip, g_skip_c0, C):
     ldgs = 0
     if g_skip is not None:
         ldgs = g_skip.shape[-1]
-        gs_ptr = ctypes.c_void_p(g_skip.data_ptr() + g_skip_c0 * g_skip.element_size())
-    rc = _lib.lib().wm_maxpool2_bwd(_p(y), c_int(ld), _p(scale), _p(shift), _p(gpooled), c_int(gpooled.shape[-1]), gs_ptr,
-                                    c_int(ldgs), _p(g), c_int(C), c_int(B), c_int(H), c_int(W), c_int(C), c_int(dtype_id(y)),
+        gs_ptr = g_skip.data_ptr() + g_skip_c0 * g_skip.element_size()
+    rc = _lib.lib().wm_maxpool2_bwd(_p(y), ld, _p(scale), _p(shift), _p(gpooled), gpooled.shape[-1], gs_ptr, ldgs, _p(g), C, B, H, W, C, dtype_id(y),
                                     _stream())
     _lib.check(rc, "wm_maxpool2_bwd")
     return g
 
 
 def upconv2x2_mfma_supported(Cin, Cout, dtype):
-    return bool(_lib.lib().wm_upconv2x2_mfma_supported(c_int(Cin), c_int(Cout), c_int(dt_id(dtype))))
+    return bool(_lib.lib().wm_upconv2x2_mfma_supported(Cin, Cout, dt_id(dtype)))
 
 
 def upconv2x2_pack(w, dtype=torch.bfloat16):
@@ -1252,7 +1211,7 @@ def upconv2x2_pack(w, dtype=torch.bfloat16):
     Cin, Cout = w.shape[0], w.shape[1]
     wf = torch.empty(4 * Cout, Cin, device=w.device, dtype=dtype)
     wb = torch.empty(Cin, 4 * Cout, device=w.device, dtype=dtype)
-    rc = _lib.lib().wm_upconv2x2_pack(_p(w), _p(wf), _p(wb), c_int(Cin), c_int(Cout), c_int(dt_id(dtype)), _stream())
+    rc = _lib.lib().wm_upconv2x2_pack(_p(w), _p(wf), _p(wb), Cin, Cout, dt_id(dtype), _stream())
     _lib.check(rc, "wm_upconv2x2_pack")
     return wf, wb
 
@@ -1263,12 +1222,12 @@ def upconv2x2_fwd(x, scale, shift, w, bias, out, c0):
     Cin, Cout = w.shape[0], w.shape[1]
     if upconv2x2_mfma_supported(Cin, Cout, x.dtype):
         wf, _ = upconv2x2_pack(w, x.dtype)
-        rc = _lib.lib().wm_upconv2x2_fwd_mfma(_p(x), c_int(ldx), _p(scale), _p(shift), _p(wf), _p(bias), _p(out), c_int(out.shape[-1]),
-                                              c_int(c0), c_int(B), c_int(H), c_int(W), c_int(Cin), c_int(Cout), c_int(dtype_id(x)), _stream())
+        rc = _lib.lib().wm_upconv2x2_fwd_mfma(_p(x), ldx, _p(scale), _p(shift), _p(wf), _p(bias), _p(out), out.shape[-1], c0, B, H, W, Cin, Cout,
+                                              dtype_id(x), _stream())
         _lib.check(rc, "wm_upconv2x2_fwd_mfma")
         return out
-    rc = _lib.lib().wm_upconv2x2_fwd(_p(x), c_int(ldx), _p(scale), _p(shift), _p(w), _p(bias), _p(out), c_int(out.shape[-1]),
-                                     c_int(c0), c_int(B), c_int(H), c_int(W), c_int(Cin), c_int(Cout), c_int(dtype_id(x)), _stream())
+    rc = _lib.lib().wm_upconv2x2_fwd(_p(x), ldx, _p(scale), _p(shift), _p(w), _p(bias), _p(out), out.shape[-1], c0, B, H, W, Cin, Cout, dtype_id(x),
+                                     _stream())
     _lib.check(rc, "wm_upconv2x2_fwd")
     return out
 
@@ -1281,24 +1240,22 @@ def upconv2x2_bwd(x, scale, shift, w, gy, c0, dw, dbias, accumulate):
     if upconv2x2_mfma_supported(Cin, Cout, x.dtype):
         _, wb = upconv2x2_pack(w, x.dtype)
         gx = torch.empty(B, H, W, Cin, device=x.device, dtype=x.dtype)
-        rc = L.wm_upconv2x2_dgrad_mfma(_p(gy), c_int(gy.shape[-1]), c_int(c0), _p(wb), _p(gx), c_int(Cin), c_int(B), c_int(H), c_int(W),
-                                       c_int(Cin), c_int(Cout), c_int(dtype_id(x)), _stream())
+        rc = L.wm_upconv2x2_dgrad_mfma(_p(gy), gy.shape[-1], c0, _p(wb), _p(gx), Cin, B, H, W, Cin, Cout, dtype_id(x), _stream())
         _lib.check(rc, "wm_upconv2x2_dgrad_mfma")
-        ns = L.wm_upconv2x2_wgrad_nsplit(c_int(B), c_int(H), c_int(W), c_int(Cin), c_int(Cout))
+        ns = L.wm_upconv2x2_wgrad_nsplit(B, H, W, Cin, Cout)
         part = torch.empty(ns, Cin, 4 * Cout, device=x.device, dtype=torch.float32)
         bpart = torch.empty(ns, 4 * Cout, device=x.device, dtype=torch.float32)
-        rc = L.wm_upconv2x2_wgrad_mfma(_p(x), c_int(ldx), _p(scale), _p(shift), _p(gy), c_int(gy.shape[-1]), c_int(c0), _p(part), _p(bpart),
-                                       _p(dw), _p(dbias), c_int(1 if accumulate else 0), c_int(B), c_int(H), c_int(W), c_int(Cin),
-                                       c_int(Cout), c_int(dtype_id(x)), _stream())
+        rc = L.wm_upconv2x2_wgrad_mfma(_p(x), ldx, _p(scale), _p(shift), _p(gy), gy.shape[-1], c0, _p(part), _p(bpart), _p(dw), _p(dbias),
+                                       1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x), _stream())
         _lib.check(rc, "wm_upconv2x2_wgrad_mfma")
         return gx
-    chunks = L.wm_upconv2x2_dw_chunks(c_int(B), c_int(H), c_int(W))
+    chunks = L.wm_upconv2x2_dw_chunks(B, H, W)
     N = 4 * Cout
     part = torch.empty(chunks, (Cin + 1) * N, device=x.device, dtype=torch.float32)
     w_t = w.permute(2, 3, 1, 0).reshape(N, Cin).contiguous()
     gx = torch.empty(B, H, W, Cin, device=x.device, dtype=x.dtype)
-    rc = L.wm_upconv2x2_bwd(_p(x), c_int(ldx), _p(scale), _p(shift), _p(w_t), _p(gy), c_int(gy.shape[-1]), c_int(c0), _p(gx),
-                            c_int(Cin), _p(part), c_int(B), c_int(H), c_int(W), c_int(Cin), c_int(Cout), c_int(dtype_id(x)), _stream())
+    rc = L.wm_upconv2x2_bwd(_p(x), ldx, _p(scale), _p(shift), _p(w_t), _p(gy), gy.shape[-1], c0, _p(gx), Cin, _p(part), B, H, W, Cin, Cout,
+                            dtype_id(x), _stream())
     _lib.check(rc, "wm_upconv2x2_bwd")
     red = torch.empty((Cin + 1) * N, device=x.device, dtype=torch.float32)
     colsum(part, (Cin + 1) * N, (Cin + 1) * N, red, False)
@@ -1323,7 +1280,7 @@ def diffjpeg_fwd(x, rounding, factor):
     x = x.contiguous()
     y = torch.empty_like(x)
     B, _, H, W = x.shape
-    rc = _lib.lib().wm_diffjpeg_fwd(_p(x), _p(y), c_int(B), c_int(H), c_int(W), c_int(rounding), c_float(factor), _stream())
+    rc = _lib.lib().wm_diffjpeg_fwd(_p(x), _p(y), B, H, W, rounding, factor, _stream())
     _lib.check(rc, "wm_diffjpeg_fwd")
     return y
 
@@ -1333,7 +1290,7 @@ def diffjpeg_bwd(x, gy, rounding, factor):
     x = x.contiguous(); gy = gy.contiguous()
     gx = torch.empty_like(gy)
     B, _, H, W = x.shape
-    rc = _lib.lib().wm_diffjpeg_bwd(_p(x), _p(gy), _p(gx), c_int(B), c_int(H), c_int(W), c_int(rounding), c_float(factor), _stream())
+    rc = _lib.lib().wm_diffjpeg_bwd(_p(x), _p(gy), _p(gx), B, H, W, rounding, factor, _stream())
     _lib.check(rc, "wm_diffjpeg_bwd")
     return gx
 
@@ -1362,8 +1319,7 @@ def gconv_pack(w, rows, cols, transpose, dtype):
     w = w.contiguous()
     Cout, Cin, KH, KW = w.shape
     wp = torch.empty(KH * KW, rows, cols, device=w.device, dtype=dtype)
-    rc = _lib.lib().wm_gconv_pack(_p(w), _p(wp), c_int(Cout), c_int(Cin), c_int(KH), c_int(KW), c_int(rows), c_int(cols), c_int(1 if transpose else 0),
-                                  c_int(dt_id(dtype)), _stream())
+    rc = _lib.lib().wm_gconv_pack(_p(w), _p(wp), Cout, Cin, KH, KW, rows, cols, 1 if transpose else 0, dt_id(dtype), _stream())
     _lib.check(rc, "wm_gconv_pack")
     return wp
 
@@ -1379,8 +1335,8 @@ def gconv_fwd(x, wp, bias, out_hw, KH, KW, stride, pad, dgrad=False):
         raise ValueError("bias must be f32 with one entry per (padded) output channel")
     OH, OW = out_hw
     out = torch.empty(B, OH, OW, NC, device=x.device, dtype=x.dtype)
-    rc = _lib.lib().wm_gconv_fwd(_p(x), _p(wp), _p(bias), _p(out), c_int(B), c_int(IH), c_int(IW), c_int(KC), c_int(OH), c_int(OW), c_int(NC),
-                                 c_int(KH), c_int(KW), c_int(stride), c_int(pad), c_int(1 if dgrad else 0), c_int(dt_id(x.dtype)), _stream())
+    rc = _lib.lib().wm_gconv_fwd(_p(x), _p(wp), _p(bias), _p(out), B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, 1 if dgrad else 0, dt_id(x.dtype),
+                                 _stream())
     _lib.check(rc, "wm_gconv_fwd")
     return out
 
@@ -1394,8 +1350,7 @@ def gconv_wgrad(dout, x, Cout, Cin, KH, KW, stride, pad, want_bias=True, dw_acc=
     if x.shape[0] != B or x.dtype != dout.dtype:
         raise ValueError("gconv_wgrad: operands disagree")
     L = _lib.lib()
-    L.wm_gconv_wgrad_scratch_floats.restype = c_size_t
-    partial = torch.empty(L.wm_gconv_wgrad_scratch_floats(c_int(B), c_int(OH), c_int(OW), c_int(KC), c_int(NC), c_int(KH), c_int(KW)), device=x.device,
+    partial = torch.empty(L.wm_gconv_wgrad_scratch_floats(B, OH, OW, KC, NC, KH, KW), device=x.device,
                           dtype=torch.float32)
     acc = dw_acc is not None
     if acc and (not dw_acc.is_contiguous() or dw_acc.numel() != Cout * Cin * KH * KW or dw_acc.dtype != torch.float32 or
@@ -1403,9 +1358,8 @@ def gconv_wgrad(dout, x, Cout, Cin, KH, KW, stride, pad, want_bias=True, dw_acc=
         raise ValueError("gconv_wgrad: accumulation targets do not match the gradients")
     dw = dw_acc if acc else torch.empty(Cout, Cin, KH, KW, device=x.device, dtype=torch.float32)
     db = (db_acc if acc else torch.empty(Cout, device=x.device, dtype=torch.float32)) if want_bias else None
-    rc = _lib.lib().wm_gconv_wgrad(_p(dout), _p(x), _p(partial), _p(dw), _p(db), c_int(1 if acc else 0), c_int(B), c_int(IH), c_int(IW), c_int(KC), c_int(OH),
-                                   c_int(OW), c_int(NC), c_int(KH), c_int(KW), c_int(stride), c_int(pad), c_int(Cout), c_int(Cin),
-                                   c_int(dt_id(x.dtype)), _stream())
+    rc = _lib.lib().wm_gconv_wgrad(_p(dout), _p(x), _p(partial), _p(dw), _p(db), 1 if acc else 0, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad,
+                                   Cout, Cin, dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_gconv_wgrad")
     return dw, db
 
@@ -1418,10 +1372,8 @@ def gcolsum(x, creal, out_acc=None):
         raise ValueError("gcolsum: accumulation target does not match")
     out = out_acc if out_acc is not None else torch.empty(creal, device=x.device, dtype=torch.float32)
     L = _lib.lib()
-    L.wm_gcolsum_scratch_floats.restype = c_size_t
-    scratch = torch.empty(L.wm_gcolsum_scratch_floats(c_size_t(x.numel() // C), c_int(C)), device=x.device, dtype=torch.float32)
-    rc = L.wm_gcolsum(_p(x), c_size_t(x.numel() // C), c_int(C), _p(out), c_int(creal), c_int(0 if out_acc is None else 1), _p(scratch), c_int(dt_id(x.dtype)),
-                      _stream())
+    scratch = torch.empty(L.wm_gcolsum_scratch_floats(x.numel() // C, C), device=x.device, dtype=torch.float32)
+    rc = L.wm_gcolsum(_p(x), x.numel() // C, C, _p(out), creal, 0 if out_acc is None else 1, _p(scratch), dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_gcolsum")
     return out
 
@@ -1430,7 +1382,7 @@ def unary_fwd(x, kind):
     _need_cuda(x)
     x = x.contiguous()
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_unary_fwd(_p(x), _p(y), c_size_t(x.numel()), c_int(ACT_KINDS[kind]), c_int(dt_id(x.dtype)), _stream())
+    rc = _lib.lib().wm_unary_fwd(_p(x), _p(y), x.numel(), ACT_KINDS[kind], dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_unary_fwd")
     return y
 
@@ -1439,7 +1391,7 @@ def unary_bwd(x, gy, kind):
     _need_cuda(x, gy)
     gy = gy.contiguous()
     gx = torch.empty_like(x)
-    rc = _lib.lib().wm_unary_bwd(_p(x), _p(gy), _p(gx), c_size_t(x.numel()), c_int(ACT_KINDS[kind]), c_int(dt_id(x.dtype)), _stream())
+    rc = _lib.lib().wm_unary_bwd(_p(x), _p(gy), _p(gx), x.numel(), ACT_KINDS[kind], dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_unary_bwd")
     return gx
 
@@ -1456,11 +1408,9 @@ def unary_bwd_colsum(x, gy, kind, creal, db_acc=None):
         raise ValueError("unary_bwd_colsum: accumulation target does not match")
     db = db_acc if db_acc is not None else torch.empty(creal, device=x.device, dtype=torch.float32)
     L = _lib.lib()
-    L.wm_unary_bwd_colsum_scratch_floats.restype = c_size_t
-    part = torch.empty(L.wm_unary_bwd_colsum_scratch_floats(c_size_t(npix), c_int(C)), device=x.device, dtype=torch.float32)
-    rc = L.wm_unary_bwd_colsum(_p(x), _p(gy), _p(gx), c_size_t(npix), c_int(C), c_int(ACT_BWD_KINDS[kind]), _p(part), _p(db), c_int(creal),
-                               c_int(0 if db_acc is None else 1),
-                               c_int(dt_id(x.dtype)), _stream())
+    part = torch.empty(L.wm_unary_bwd_colsum_scratch_floats(npix, C), device=x.device, dtype=torch.float32)
+    rc = L.wm_unary_bwd_colsum(_p(x), _p(gy), _p(gx), npix, C, ACT_BWD_KINDS[kind], _p(part), _p(db), creal, 0 if db_acc is None else 1,
+                               dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_unary_bwd_colsum")
     return gx, db
 
@@ -1471,7 +1421,7 @@ def add_scaled(a, b, alpha=1.0):
         raise ValueError("add_scaled: operands disagree")
     a, b = a.contiguous(), b.contiguous()
     out = torch.empty_like(a)
-    rc = _lib.lib().wm_add_scaled(_p(a), _p(b), _p(out), c_size_t(a.numel()), c_float(alpha), c_int(dt_id(a.dtype)), _stream())
+    rc = _lib.lib().wm_add_scaled(_p(a), _p(b), _p(out), a.numel(), alpha, dt_id(a.dtype), _stream())
     _lib.check(rc, "wm_add_scaled")
     return out
 
@@ -1483,8 +1433,7 @@ def qfatt_fwd(x, res, gamma, beta):
     gamma, beta = gamma.contiguous(), beta.contiguous()
     assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.shape == beta.shape and gamma.shape[0] == B
     out = torch.empty_like(x)
-    rc = _lib.lib().wm_qfatt_fwd(_p(x), _p(res), _p(gamma), _p(beta), _p(out), c_int(B), c_size_t(H * W), c_int(C), c_int(gamma.shape[1]),
-                                 c_int(dt_id(x.dtype)), _stream())
+    rc = _lib.lib().wm_qfatt_fwd(_p(x), _p(res), _p(gamma), _p(beta), _p(out), B, H * W, C, gamma.shape[1], dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_qfatt_fwd")
     return out
 
@@ -1497,10 +1446,8 @@ def qfatt_bwd(g, res, gamma):
     gg = torch.zeros_like(gamma)
     gb = torch.zeros_like(gamma)
     L = _lib.lib()
-    L.wm_qfatt_bwd_scratch_floats.restype = c_size_t
-    scratch = torch.empty(L.wm_qfatt_bwd_scratch_floats(c_int(B), c_size_t(H * W), c_int(gamma.shape[1])), device=g.device, dtype=torch.float32)
-    rc = L.wm_qfatt_bwd(_p(g), _p(res), _p(gamma), _p(gres), _p(gg), _p(gb), _p(scratch), c_int(B), c_size_t(H * W), c_int(C), c_int(gamma.shape[1]),
-                        c_int(dt_id(g.dtype)), _stream())
+    scratch = torch.empty(L.wm_qfatt_bwd_scratch_floats(B, H * W, gamma.shape[1]), device=g.device, dtype=torch.float32)
+    rc = L.wm_qfatt_bwd(_p(g), _p(res), _p(gamma), _p(gres), _p(gg), _p(gb), _p(scratch), B, H * W, C, gamma.shape[1], dt_id(g.dtype), _stream())
     _lib.check(rc, "wm_qfatt_bwd")
     return gres, gg, gb
 
@@ -1509,7 +1456,7 @@ def gpool_fwd(x):
     x = _nhwc(x)
     B, H, W, C = x.shape
     out = torch.empty(B, C, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_gpool_fwd(_p(x), _p(out), c_int(B), c_size_t(H * W), c_int(C), c_int(dt_id(x.dtype)), _stream())
+    rc = _lib.lib().wm_gpool_fwd(_p(x), _p(out), B, H * W, C, dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_gpool_fwd")
     return out
 
@@ -1519,7 +1466,7 @@ def gpool_bwd(g, shape, dtype):
     B, H, W, C = shape
     g = g.contiguous().float()
     gx = torch.empty(B, H, W, C, device=g.device, dtype=dtype)
-    rc = _lib.lib().wm_gpool_bwd(_p(g), _p(gx), c_int(B), c_size_t(H * W), c_int(C), c_int(dt_id(dtype)), _stream())
+    rc = _lib.lib().wm_gpool_bwd(_p(g), _p(gx), B, H * W, C, dt_id(dtype), _stream())
     _lib.check(rc, "wm_gpool_bwd")
     return gx
 
@@ -1534,8 +1481,7 @@ def pad_nchw_to_nhwc(x, pads, mode, dtype):
     B, C, H, W = x.shape
     l, r, t, b = pads
     out = torch.empty(B, H + t + b, W + l + r, cpad(C), device=x.device, dtype=dtype)
-    rc = _lib.lib().wm_pad_nchw_to_nhwc(_p(x), _p(out), c_int(B), c_int(C), c_int(H), c_int(W), c_int(l), c_int(r), c_int(t), c_int(b), c_int(mode),
-                                        c_int(out.shape[3]), c_int(dt_id(dtype)), _stream())
+    rc = _lib.lib().wm_pad_nchw_to_nhwc(_p(x), _p(out), B, C, H, W, l, r, t, b, mode, out.shape[3], dt_id(dtype), _stream())
     _lib.check(rc, "wm_pad_nchw_to_nhwc")
     return out
 
@@ -1545,8 +1491,7 @@ def pad_nchw_to_nhwc_bwd(gp, shape, pads, mode):
     B, C, H, W = shape
     l, r, t, b = pads
     gx = torch.empty(B, C, H, W, device=gp.device, dtype=torch.float32)
-    rc = _lib.lib().wm_pad_nchw_to_nhwc_bwd(_p(gp), _p(gx), c_int(B), c_int(C), c_int(H), c_int(W), c_int(l), c_int(r), c_int(t), c_int(b), c_int(mode),
-                                            c_int(gp.shape[3]), c_int(dt_id(gp.dtype)), _stream())
+    rc = _lib.lib().wm_pad_nchw_to_nhwc_bwd(_p(gp), _p(gx), B, C, H, W, l, r, t, b, mode, gp.shape[3], dt_id(gp.dtype), _stream())
     _lib.check(rc, "wm_pad_nchw_to_nhwc_bwd")
     return gx
 
@@ -1555,8 +1500,7 @@ def gunpack_nchw(x, C, H, W):
     x = _nhwc(x)
     B, PH, PW, CP = x.shape
     out = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_gunpack_nchw(_p(x), _p(out), c_int(B), c_int(C), c_int(H), c_int(W), c_int(PH), c_int(PW), c_int(CP), c_int(dt_id(x.dtype)),
-                                    _stream())
+    rc = _lib.lib().wm_gunpack_nchw(_p(x), _p(out), B, C, H, W, PH, PW, CP, dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_gunpack_nchw")
     return out
 
@@ -1567,8 +1511,7 @@ def gunpack_nchw_bwd(g, shape, dtype):
     B, C, H, W = g.shape
     _, PH, PW, CP = shape
     gx = torch.empty(B, PH, PW, CP, device=g.device, dtype=dtype)
-    rc = _lib.lib().wm_gunpack_nchw_bwd(_p(g), _p(gx), c_int(B), c_int(C), c_int(H), c_int(W), c_int(PH), c_int(PW), c_int(CP), c_int(dt_id(dtype)),
-                                        _stream())
+    rc = _lib.lib().wm_gunpack_nchw_bwd(_p(g), _p(gx), B, C, H, W, PH, PW, CP, dt_id(dtype), _stream())
     _lib.check(rc, "wm_gunpack_nchw_bwd")
     return gx
 
@@ -1582,9 +1525,8 @@ def spectral_norm_fwd(w, u, v, do_iter):
     sigma = torch.empty(1, device=w.device, dtype=torch.float32)
     wsn = torch.empty_like(w)
     L = _lib.lib()
-    L.wm_spectral_norm_scratch_floats.restype = c_size_t
-    scratch = torch.empty(L.wm_spectral_norm_scratch_floats(c_int(M), c_int(N)), device=w.device, dtype=torch.float32)
-    rc = L.wm_spectral_norm_fwd(_p(w), _p(u), _p(v), _p(sigma), _p(wsn), _p(scratch), c_int(M), c_int(N), c_int(1 if do_iter else 0), _stream())
+    scratch = torch.empty(L.wm_spectral_norm_scratch_floats(M, N), device=w.device, dtype=torch.float32)
+    rc = L.wm_spectral_norm_fwd(_p(w), _p(u), _p(v), _p(sigma), _p(wsn), _p(scratch), M, N, 1 if do_iter else 0, _stream())
     _lib.check(rc, "wm_spectral_norm_fwd")
     return wsn, sigma
 
@@ -1595,7 +1537,7 @@ def spectral_norm_bwd(g, wsn, u, v, sigma):
     M, N = g.shape[0], g.numel() // g.shape[0]
     partial = torch.empty(256, device=g.device, dtype=torch.float32)
     gw = torch.empty_like(g)
-    rc = _lib.lib().wm_spectral_norm_bwd(_p(g), _p(wsn), _p(u), _p(v), _p(sigma), _p(partial), _p(gw), c_int(M), c_int(N), c_int(0), _stream())
+    rc = _lib.lib().wm_spectral_norm_bwd(_p(g), _p(wsn), _p(u), _p(v), _p(sigma), _p(partial), _p(gw), M, N, 0, _stream())
     _lib.check(rc, "wm_spectral_norm_bwd")
     return gw
 
@@ -1604,7 +1546,7 @@ def bayar_constrain_(w):
     """the Bayar constraint on w [Co,Ci,5,5] in place (conditional_jpeg_generator.py:814-817)"""
     _need_cuda(w)
     assert w.dtype == torch.float32 and w.is_contiguous() and w.shape[-2:] == (5, 5)
-    rc = _lib.lib().wm_bayar_constrain(_p(w), c_int(w.shape[0] * w.shape[1]), _stream())
+    rc = _lib.lib().wm_bayar_constrain(_p(w), w.shape[0] * w.shape[1], _stream())
     _lib.check(rc, "wm_bayar_constrain")
     return w
 
@@ -1625,8 +1567,8 @@ def haar(x, C, fac, up, by_wavelet=False):
             raise ValueError(f"haar analysis needs even height / width and {C} channels, got {tuple(x.shape)}")
         H, W = XH // 2, XW // 2
         out = torch.empty(B, H, W, cpad(4 * C), device=x.device, dtype=x.dtype)
-    rc = _lib.lib().wm_haar(_p(x), _p(out), c_int(B), c_int(H), c_int(W), c_int(C), c_int(CPin), c_int(out.shape[3]), c_float(fac),
-                            c_int((1 if up else 0) | (2 if by_wavelet else 0)), c_int(dt_id(x.dtype)), _stream())
+    rc = _lib.lib().wm_haar(_p(x), _p(out), B, H, W, C, CPin, out.shape[3], fac, (1 if up else 0) | (2 if by_wavelet else 0), dt_id(x.dtype),
+                            _stream())
     _lib.check(rc, "wm_haar")
     return out
 
@@ -1637,8 +1579,7 @@ def chan_copy_(dst, doff, src, soff, n):
     if dst.shape[:3] != src.shape[:3] or dst.dtype != src.dtype:
         raise ValueError("chan_copy_: pixel grids / dtypes disagree")
     npix = dst.shape[0] * dst.shape[1] * dst.shape[2]
-    rc = _lib.lib().wm_chan_copy(_p(src), _p(dst), c_size_t(npix), c_int(src.shape[3]), c_int(soff), c_int(dst.shape[3]), c_int(doff), c_int(n),
-                                 c_int(dt_id(dst.dtype)), _stream())
+    rc = _lib.lib().wm_chan_copy(_p(src), _p(dst), npix, src.shape[3], soff, dst.shape[3], doff, n, dt_id(dst.dtype), _stream())
     _lib.check(rc, "wm_chan_copy")
     return dst
 
@@ -1655,8 +1596,8 @@ def chan_place(dstride, a, aoff, adst, na, b=None, boff=0, bdst=0, nb=0):
         raise ValueError("chan_place: the channel stride must be a multiple of 16")
     out = torch.empty(*a.shape[:3], dstride, device=a.device, dtype=a.dtype)
     npix = a.shape[0] * a.shape[1] * a.shape[2]
-    rc = _lib.lib().wm_chan_place(_p(a), c_int(a.shape[3]), c_int(aoff), c_int(adst), c_int(na), _p(b), c_int(b.shape[3] if b is not None else 0), c_int(boff),
-                                  c_int(bdst), c_int(nb), _p(out), c_int(dstride), c_size_t(npix), c_int(dt_id(a.dtype)), _stream())
+    rc = _lib.lib().wm_chan_place(_p(a), a.shape[3], aoff, adst, na, _p(b), b.shape[3] if b is not None else 0, boff, bdst, nb, _p(out), dstride,
+                                  npix, dt_id(a.dtype), _stream())
     _lib.check(rc, "wm_chan_place")
     return out
 
@@ -1667,8 +1608,7 @@ def coupling_fwd(x, s, t, clamp, eps, rev):
         raise ValueError("coupling_fwd: operands disagree")
     x, s, t = x.contiguous(), s.contiguous(), t.contiguous()
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_coupling_fwd(_p(x), _p(s), _p(t), _p(y), c_size_t(x.numel()), c_float(clamp), c_float(eps), c_int(1 if rev else 0),
-                                    c_int(dt_id(x.dtype)), _stream())
+    rc = _lib.lib().wm_coupling_fwd(_p(x), _p(s), _p(t), _p(y), x.numel(), clamp, eps, 1 if rev else 0, dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_coupling_fwd")
     return y
 
@@ -1677,8 +1617,7 @@ def coupling_bwd(g, v, s, clamp, eps, rev):
     _need_cuda(g, v, s)
     g = g.contiguous()
     gx, gs, gt = torch.empty_like(g), torch.empty_like(g), torch.empty_like(g)
-    rc = _lib.lib().wm_coupling_bwd(_p(g), _p(v), _p(s), _p(gx), _p(gs), _p(gt), c_size_t(g.numel()), c_float(clamp), c_float(eps),
-                                    c_int(1 if rev else 0), c_int(dt_id(g.dtype)), _stream())
+    rc = _lib.lib().wm_coupling_bwd(_p(g), _p(v), _p(s), _p(gx), _p(gs), _p(gt), g.numel(), clamp, eps, 1 if rev else 0, dt_id(g.dtype), _stream())
     _lib.check(rc, "wm_coupling_bwd")
     return gx, gs, gt
 
@@ -1698,7 +1637,7 @@ def smooth_l1(a, b, beta=1.0, want_grad=True):
     part = torch.empty(_nparts(n), device=a.device, dtype=torch.float32)
     loss = torch.empty(1, device=a.device, dtype=torch.float32)
     grad = torch.empty_like(a) if want_grad else None
-    rc = _lib.lib().wm_smooth_l1(_p(a), _p(b), c_size_t(n), c_float(beta), _p(part), c_int(part.numel()), _p(loss), _p(grad), _stream())
+    rc = _lib.lib().wm_smooth_l1(_p(a), _p(b), n, beta, _p(part), part.numel(), _p(loss), _p(grad), _stream())
     _lib.check(rc, "wm_smooth_l1")
     return loss, grad
 
@@ -1711,7 +1650,7 @@ def bce_prob(p, target, want_grad=True):
     part = torch.empty(_nparts(n), device=p.device, dtype=torch.float32)
     loss = torch.empty(1, device=p.device, dtype=torch.float32)
     grad = torch.empty_like(p) if want_grad else None
-    rc = _lib.lib().wm_bce_prob(_p(p), c_float(target), c_size_t(n), _p(part), c_int(part.numel()), _p(loss), _p(grad), _stream())
+    rc = _lib.lib().wm_bce_prob(_p(p), target, n, _p(part), part.numel(), _p(loss), _p(grad), _stream())
     _lib.check(rc, "wm_bce_prob")
     return loss, grad
 
@@ -1726,7 +1665,7 @@ def cross_entropy(logits, labels, want_grad=True):
     B, K = logits.shape
     loss = torch.empty(1, device=logits.device, dtype=torch.float32)
     grad = torch.empty_like(logits) if want_grad else None
-    rc = _lib.lib().wm_cross_entropy(_p(logits), _p(labels), c_int(B), c_int(K), c_int(K), _p(loss), _p(grad), _stream())
+    rc = _lib.lib().wm_cross_entropy(_p(logits), _p(labels), B, K, K, _p(loss), _p(grad), _stream())
     _lib.check(rc, "wm_cross_entropy")
     return loss, grad
 
@@ -1735,7 +1674,7 @@ def clamp01_fwd(x):
     _need_cuda(x)
     x = x.contiguous().float()
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_clamp01_fwd(_p(x), _p(y), c_size_t(x.numel()), _stream())
+    rc = _lib.lib().wm_clamp01_fwd(_p(x), _p(y), x.numel(), _stream())
     _lib.check(rc, "wm_clamp01_fwd")
     return y
 
@@ -1744,7 +1683,7 @@ def clamp01_bwd(x, g):
     _need_cuda(x, g)
     g = g.contiguous().float()
     gx = torch.empty_like(g)
-    rc = _lib.lib().wm_clamp01_bwd(_p(x), _p(g), _p(gx), c_size_t(g.numel()), _stream())
+    rc = _lib.lib().wm_clamp01_bwd(_p(x), _p(g), _p(gx), g.numel(), _stream())
     _lib.check(rc, "wm_clamp01_bwd")
     return gx
 
@@ -1755,7 +1694,7 @@ def psnr255(a, b):
     a, b = a.contiguous().float(), b.contiguous().float()
     n = a.numel()
     part = torch.empty(_nparts(n), device=a.device, dtype=torch.float64)
-    rc = _lib.lib().wm_psnr255_partials(_p(a), _p(b), c_size_t(n), _p(part), c_int(part.numel()), _stream())
+    rc = _lib.lib().wm_psnr255_partials(_p(a), _p(b), n, _p(part), part.numel(), _stream())
     _lib.check(rc, "wm_psnr255_partials")
     return psnr_gate(part, n)[0:1]
 
@@ -1764,7 +1703,7 @@ def scale_dev_(x, scale_dev):
     """x *= scale_dev[0] (a device scalar)"""
     _need_cuda(x, scale_dev)
     assert x.is_contiguous() and x.dtype == torch.float32 and scale_dev.dtype == torch.float32
-    rc = _lib.lib().wm_scale_dev(_p(x), c_size_t(x.numel()), _p(scale_dev), _stream())
+    rc = _lib.lib().wm_scale_dev(_p(x), x.numel(), _p(scale_dev), _stream())
     _lib.check(rc, "wm_scale_dev")
     _wrote(x)
     return x
@@ -1791,7 +1730,7 @@ def rng_fill(state, n, dist=RNG_UNIFORM):
     _need_cuda(state)
     assert state.dtype == torch.int64 and state.numel() >= 2
     out = torch.empty(int(n), device=state.device, dtype=torch.float32)
-    rc = _lib.lib().wm_rng_fill(_p(state), _p(out), c_size_t(int(n)), c_int(dist), _stream())
+    rc = _lib.lib().wm_rng_fill(_p(state), _p(out), int(n), dist, _stream())
     _lib.check(rc, "wm_rng_fill")
     return out
 
@@ -1812,8 +1751,7 @@ def noise_fwd(op, x, a, b, state, cover=None):
         assert cover.shape == x.shape
     rec = _rng_args(x, state)
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_noise_fwd(c_int(op), _p(x), _p(cover), _p(y), c_size_t(x.numel()), c_float(a), c_float(b), _p(state), _p(rec),
-                                 _stream())
+    rc = _lib.lib().wm_noise_fwd(op, _p(x), _p(cover), _p(y), x.numel(), a, b, _p(state), _p(rec), _stream())
     _lib.check(rc, "wm_noise_fwd")
     _wrote(state)
     return y, rec
@@ -1829,7 +1767,7 @@ def noise_bwd(op, g, a, b, rec, x=None, want_cover=False):
         x = x.contiguous().float()
     gx = torch.empty_like(g)
     gc = torch.empty_like(g) if want_cover and op == NOISE_DROP else None
-    rc = _lib.lib().wm_noise_bwd(c_int(op), _p(x), _p(g), _p(gx), _p(gc), c_size_t(g.numel()), c_float(a), c_float(b), _p(rec), _stream())
+    rc = _lib.lib().wm_noise_bwd(op, _p(x), _p(g), _p(gx), _p(gc), g.numel(), a, b, _p(rec), _stream())
     _lib.check(rc, "wm_noise_bwd")
     return gx, gc
 
@@ -1842,8 +1780,7 @@ def dropout_fwd(x, cover, keep_min, keep_span, state):
     assert cover.shape == x.shape
     rec = _rng_args(x, state)
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_dropout_fwd(_p(x), _p(cover), _p(y), c_int(N), c_int(H), c_int(W), c_float(keep_min), c_float(keep_span), _p(state),
-                                   _p(rec), _stream())
+    rc = _lib.lib().wm_dropout_fwd(_p(x), _p(cover), _p(y), N, H, W, keep_min, keep_span, _p(state), _p(rec), _stream())
     _lib.check(rc, "wm_dropout_fwd")
     _wrote(state)
     return y, rec
@@ -1853,8 +1790,7 @@ def dropout_bwd(g, keep_min, keep_span, rec, want_cover=False):
     g, N, H, W = _planes(g)
     gx = torch.empty_like(g)
     gc = torch.empty_like(g) if want_cover else None
-    rc = _lib.lib().wm_dropout_bwd(_p(g), _p(gx), _p(gc), c_int(N), c_int(H), c_int(W), c_float(keep_min), c_float(keep_span), _p(rec),
-                                   _stream())
+    rc = _lib.lib().wm_dropout_bwd(_p(g), _p(gx), _p(gc), N, H, W, keep_min, keep_span, _p(rec), _stream())
     _lib.check(rc, "wm_dropout_bwd")
     return gx, gc
 
@@ -1864,8 +1800,8 @@ def _jpeg_drop(name, x, keep):
     assert x.dim() == 4 and x.shape[1] == 3, "JpegCompression takes [B,3,H,W] images"
     x = x.contiguous().float()
     y = torch.empty_like(x)
-    k = (c_int * 3)(*[int(v) for v in keep])
-    rc = getattr(_lib.lib(), name)(_p(x), _p(y), c_int(x.shape[0]), c_int(x.shape[2]), c_int(x.shape[3]), k, _stream())
+    k = _host_ints(keep)
+    rc = getattr(_lib.lib(), name)(_p(x), _p(y), x.shape[0], x.shape[2], x.shape[3], k, _stream())
     _lib.check(rc, name)
     return y
 
