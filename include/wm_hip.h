@@ -704,6 +704,35 @@ int wm_dropout_bwd(const float* g, float* gx, float* gcover, int N, int H, int W
 int wm_jpeg_drop_fwd(const float* x, float* y, int B, int H, int W, const int* keep, void* stream);
 int wm_jpeg_drop_bwd(const float* gy, float* gx, int B, int H, int W, const int* keep, void* stream);
 
+/* ------------------------------------------------------------------ image-quality and mask metrics (csrc/ssim.hip)
+ * replaces pytorch_ssim/__init__.py:7-40 (_ssim and its autograd backward: the fidelity loss of models/IRN_model.py:569-570),
+ * metrics.py:5-46 (EdgeAccuracy's sums, PSNR) and calculate_f1.py:5-41 (TN / TP / FN / FP of a thresholded mask).  f32 NCHW images
+ * [B,C,H,W], any H, W >= 1, B*C <= 65535.  No atomics: per-workgroup partials and a fixed-order finalise, bitwise reproducible.
+ * win11: HOST pointer to the 11 window coefficients (gauss / gauss.sum() evaluated in float32, as the reference builds them).
+ * wm_ssim_fwd: one fused launch (both images' tiles with a 5-pixel halo in LDS, separable passes for x, y, x^2, y^2, xy, the map formed
+ *   in registers and never written).  partials [B * wm_ssim_nparts(C,H,W)] doubles, image b's contiguous.  dplanes (may be NULL)
+ *   [3][B,C,H,W] = dS/dp, dS/dq, dS/dr of every pixel (p = w*x, q = w*x^2, r = w*xy): what wm_ssim_bwd convolves.
+ * wm_ssim_finalize: out[0] = mean over everything (size_average=True), out[1 + b] = mean of image b (size_average=False).
+ * wm_ssim_bwd: grad (+)= g * (w*Dp + 2x . w*Dq + y . w*Dr), the gradient wrt the FIRST image x of the forward that wrote dplanes;
+ *   g = gscale * gscale_dev[0] (device, may be NULL) * gout_dev[per_image ? b : 0] (device, may be NULL = 1) / (per_image ? CHW : BCHW);
+ *   accumulate != 0 adds into grad.  For the second image call the forward and this with the images swapped.
+ * wm_psnr_partials: partials [nparts <= 2048] doubles of sum (a - b)^2 (float images, no truncation; wm_psnr255_partials is the int form);
+ * wm_psnr_finalize: out[0] = 20 log10(max_val) - 10 log10(mse), 0 when mse == 0 (metrics.py:41-42).
+ * wm_confusion_counts: pred / gt masks of B images x per_image elements, f32 or (pred_u8 / gt_u8 != 0) uint8; P = pred > thr_pred,
+ *   G = gt > thr_gt; partials [B * wm_confusion_nparts(per_image) * 4] int64 scratch; out [(1 + B) * 4] int64 = {TN, TP, FN, FP} in total,
+ *   then of each image (TN: !P !G, TP: P G, FN: !P G, FP: P !G). */
+int wm_ssim_nparts(int C, int H, int W);
+int wm_ssim_fwd(const float* x, const float* y, int B, int C, int H, int W, const float* win11, double* partials, float* dplanes,
+                void* stream);
+int wm_ssim_finalize(const double* partials, int B, int C, int H, int W, float* out, void* stream);
+int wm_ssim_bwd(const float* dplanes, const float* x, const float* y, float* grad, int B, int C, int H, int W, const float* win11,
+                const float* gout_dev, int per_image, float gscale, const float* gscale_dev, int accumulate, void* stream);
+int wm_psnr_partials(const float* a, const float* b, size_t n, double* partials, int nparts, void* stream);
+int wm_psnr_finalize(const double* partials, int nparts, double n, float max_val, float* out, void* stream);
+int wm_confusion_nparts(size_t per_image);
+int wm_confusion_counts(const void* pred, int pred_u8, const void* gt, int gt_u8, float thr_pred, float thr_gt, int B, size_t per_image,
+                        long long* partials, long long* out, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -357,7 +357,7 @@ class _StepGraph:
 
 class Hidden:
     def __init__(self, configuration: HiDDenConfiguration, device: torch.device, noiser, tb_logger=None,
-                 compute_dtype=torch.bfloat16, grad_sync=None, amp=None, keep_dead_discriminator_grads=True):
+                 compute_dtype=torch.bfloat16, grad_sync=None, amp=None, keep_dead_discriminator_grads=True, ssim_weight=0.0):
         """
         :param configuration: sizes / loss weights (options.HiDDenConfiguration)
         :param device: must be a cuda (ROCm) device -- the step has no CPU path
@@ -377,6 +377,11 @@ class Hidden:
         :param amp: optional ops.AmpState -- torch.cuda.amp.GradScaler semantics on the device (models/IRNcrop_model.py:143,
                     407-416): every loss gradient is multiplied by its scale, both optimisers step through it.  Required in
                     practice with compute_dtype=torch.float16 (the gradients of a 3M-element mean loss underflow f16 otherwise)
+        :param ssim_weight: weight w of the structural-similarity fidelity term (models/IRN_model.py:569-570: gen_loss += w * (-ssim(encoded,
+                    cover)), w = 0.1 or 0.01 there).  0 (default): no SSIM kernel is launched and the step is the three-term one bit for bit.
+                    > 0: the term's gradient is added into the encoded image's gradient, and the value is logged as ('SSFW', ssim) among
+                    the step's extra logs.  The logged 'loss' keeps its three-term meaning (adversarial + encoder MSE + decoder MSE) either
+                    way.  Also settable afterwards as `hidden.ssim_weight`
         """
         device = torch.device(device)
         if device.type != "cuda":
@@ -401,6 +406,7 @@ class Hidden:
         from ..distributed import as_grad_sync
         self.grad_sync = as_grad_sync(grad_sync)
         self.keep_dead_discriminator_grads = bool(keep_dead_discriminator_grads)
+        self.ssim_weight = float(ssim_weight)
         self.amp = amp
         self.amp_owner = True   # this object calls amp.update() at the end of a step (a wrapping model may take that over)
         if amp is not None:
@@ -441,8 +447,8 @@ class Hidden:
         """the AMP loss scale as a device scalar (None without a scaler): scaler.scale(loss).backward()"""
         return self.amp.scale if self.amp is not None else None
 
-    def _run_noiser(self, enc, cover):
-        n = self.encoder_decoder.noiser
+    def _run_noiser(self, enc, cover, n=None):
+        n = self.encoder_decoder.noiser if n is None else n
         if hasattr(n, "fwd") and hasattr(n, "bwd"):
             kw = {}
             if _accepts_id(n.fwd):   # Combined / Noiser / the attack cycle take a deterministic choice; single layers do not
@@ -475,14 +481,27 @@ class Hidden:
         if ck is not None:
             # (the optimisers' numbers are read from device memory at each replay, _StepGraph._hyper_refresh: only `decoupled`, a code path,
             # needs a graph of its own)
-            key = (tuple(images.shape), tuple(messages.shape), self.noise_id, self.keep_dead_discriminator_grads, self.lazy_losses, self.two_streams, self.skip_zero_attack_gradient,
-                   self.encoder_decoder.encoder.compute_dtype, ck, self.optimizer_discrim.decoupled, self.optimizer_enc_dec.decoupled)
+            key = self._graph_key(images, messages, ck)
             g = self._graphs.get(key)
             if g is None and len(self._graphs) < self.MAX_GRAPHS:
                 g = self._graphs[key] = _StepGraph(self)
             if g is not None:
                 return g.step(images, messages)
         return self._step_eager(images, messages, extra_encoded_grad, clip, enc_gate)
+
+    def _graph_key(self, images, messages, ck):
+        """what a captured step depends on beside the tensors' contents: shapes, the attack variant and every switch that selects launches"""
+        return (tuple(images.shape), tuple(messages.shape), self.noise_id, self.keep_dead_discriminator_grads, self.lazy_losses, self.two_streams,
+                self.skip_zero_attack_gradient, self.encoder_decoder.encoder.compute_dtype, ck, self.optimizer_discrim.decoupled,
+                self.optimizer_enc_dec.decoupled, float(self.ssim_weight))
+
+    def _ssim_term(self, encoded, images):
+        """the structural-similarity fidelity term ssim_weight * (-SSIM(encoded, cover)): (SSIM value, its gradient wrt encoded in a buffer of
+        its own, times the AMP scale) -- two fused launches and a finalise; (None, None) at weight 0"""
+        if not self.ssim_weight > 0:
+            return None, None
+        val, planes = ops.ssim(encoded, images, True, want_grad=True)
+        return val, ops.ssim_bwd(planes, encoded, images, gscale=-self.ssim_weight, gscale_dev=self._gsd())
 
     def _step_eager(self, images, messages, extra_encoded_grad=None, clip=None, enc_gate=None):
         vals, extra_logs, outs = self._step_launches(images, messages, extra_encoded_grad, clip, enc_gate)
@@ -529,6 +548,7 @@ class Hidden:
         D.bwd(c, None, gD, accumulate=False, need_input_grad=False)       # zero_grad + backward
 
         encoded, cE = enc_net.fwd(images, messages)
+        ssim_val, g_ssim = self._ssim_term(encoded, images)   # (before the attack: the order of the two-chain schedule)
         noised, cN = self._run_noiser(encoded, images)
 
         d_on_encoded, d_loss_on_encoded, c = D.fwd_loss(encoded, self.encoded_label, 1.0, gD, accumulate=True, gscale_dev=self._gsd())   # encoded.detach()
@@ -567,6 +587,8 @@ class Hidden:
             g_enc = D.bwd(c, g, gD, accumulate=True, need_input_grad=True, weight_grads=self.keep_dead_discriminator_grads)
             enc_part, g_mse = ops.mse_fwd_bwd_gated(encoded, images, 2.0 * cfg.encoder_loss / n_img, gate[1:2], gscale_dev=self._gsd())
             ops.axpy_(g_enc, g_mse)
+        if g_ssim is not None:
+            ops.axpy_(g_enc, g_ssim)
         zero_attack = self.skip_zero_attack_gradient and _noise_bwd_is_zero(ed.noiser, cN)
         g_noised = dec_net.bwd(cDec, None, gDec, accumulate=False, need_input_grad=not zero_attack)
         # data parallel: the decoder's bucket goes out now and travels while the attack and the encoder run their backward
@@ -579,6 +601,8 @@ class Hidden:
             extra_logs = extra_encoded_grad(encoded, images, g_enc)
         if gate is not None:
             extra_logs = [('PF', gate[0:1])] + list(extra_logs)
+        if ssim_val is not None:
+            extra_logs = list(extra_logs) + [('SSFW', ssim_val.reshape(1))]
         if gs is not None:
             # the encoder in two reverse-order buckets: [after_concat, final] leaves under the body layers' backward
             cut = enc_net.body_param_count()
@@ -612,6 +636,8 @@ class Hidden:
             A: D(cover) fwd/bwd . . . . . . | wait encoded | D(enc.detach()) fwd/bwd, Adam(D), D(enc) fwd, dgrad to the image, + MSE gradient
             B: encoder fwd | attack fwd, decoder fwd, message loss, decoder bwd, attack bwd
             join: g_enc += attack gradient; encoder bwd; Adam(enc + dec); the seven scalars
+        (ssim_weight > 0: SSIM forward and backward on B right after the encoder's forward, into a buffer of their own; A adds it to g_enc
+        with an axpy after the MSE gradient -- the one-chain step issues the same launches, so the two stay bit-identical)
         (an attack that passes back zeros -- Jpeg's torch.round, skip_zero_attack_gradient -- leaves chain B without a successor in the
         encoder: the encoder's backward then runs on chain A right behind the discriminator's, beside the decoder's backward)
 
@@ -637,6 +663,12 @@ class Hidden:
                 engine.image_to_act(encoded, dt)         # (on the producing stream: chain A and -- under an Identity attack -- the decoder read it)
             ev_enc = torch.cuda.Event()
             ev_enc.record(sB)
+            # the SSIM term needs only encoded and the cover: here, in stream order ahead of the attack's kernels (never beside them), while
+            # chain A runs the discriminator; chain A waits for ev_ssim before it adds the term's gradient
+            ssim_val, g_ssim = self._ssim_term(encoded, images)
+            if g_ssim is not None:
+                ev_ssim = torch.cuda.Event()
+                ev_ssim.record(sB)
             noised, cN = self._run_noiser(encoded, images)
             decoded, msg_out, cDec = dec_net.fwd_loss(noised, messages, 2.0 * cfg.decoder_loss / (B * cfg.message_length), gDec, accumulate=False,
                                                       gscale_dev=self._gsd())
@@ -654,6 +686,9 @@ class Hidden:
             g_img = D.bwd(c, g, gD, accumulate=True, need_input_grad=True, weight_grads=self.keep_dead_discriminator_grads, raw_input_grad=True)
             n_img = encoded.numel()
             g_enc, enc_part = ops.image_grad_mse(g_img, encoded, images, 2.0 * cfg.encoder_loss / n_img, gscale_dev=self._gsd())
+            if g_ssim is not None:   # before the encoder's backward wherever that runs (zero_attack: right below, on this chain)
+                sA.wait_event(ev_ssim)
+                ops.axpy_(g_enc, g_ssim)
             if zero_attack:
                 # nothing of chain B reaches the encoder's gradient (the attack passes back zeros): the encoder's backward continues chain A,
                 # beside the decoder's backward on chain B, and the chains meet only at the optimiser step
@@ -671,7 +706,7 @@ class Hidden:
         # allocates and ANOTHER reads (encoded and its NHWC form, g_enc, g_from_noise, the encoder's activations in cE, the loss scalars) is
         # referenced until this function returns, and a side stream is given work only between a fork (wait_stream(main)) and the join
         # above -- so a block that returns to a side stream's pool is not handed out again before main's readers of it are ordered ahead
-        return vals, [], (encoded, noised, decoded)
+        return vals, ([('SSFW', ssim_val.reshape(1))] if ssim_val is not None else []), (encoded, noised, decoded)
 
     def _chain_streams(self):
         if self._streams is None:
@@ -711,6 +746,38 @@ class Hidden:
             'discr_encod_bce': vals[6],
         }
         return losses, (encoded, noised, decoded)
+
+    def evaluate_on_batch(self, batch: list, noisers=None):
+        """What a trained model is worth on one batch, read with ONE device -> host copy by the caller: eval-mode BatchNorm and no_grad like
+        validate_on_batch.  Returns (values, names): a float32 device tensor and its column names --
+            'PSNR', 'SSIM'                       of encoded against cover (metrics.PSNR(1.0), pytorch_ssim.ssim), once per batch;
+            'BER/<name>', 'dec_mse/<name>'       per attack layer in `noisers` (default: the configured one): the share of wrong bits of
+                                                 round(decoded) clamped to [0, 1], and the decoder's MSE against the message.
+        Nothing here synchronises with the host."""
+        images, messages = batch
+        images = images.to(self.device, torch.float32).contiguous()
+        messages = messages.to(self.device, torch.float32).contiguous()
+        ed = self.encoder_decoder
+        enc_net, dec_net = ed.encoder, ed.decoder
+        noisers = [ed.noiser] if noisers is None else list(noisers)
+        was = ed.training
+        ed.eval()
+        try:
+            with torch.no_grad():
+                encoded, _ = enc_net.fwd(images, messages, training=False)
+                vals = [ops.psnr(encoded, images, 1.0), ops.ssim(encoded, images, True).reshape(1)]
+                names = ['PSNR', 'SSIM']
+                for n in noisers:
+                    noised, _ = self._run_noiser(encoded, images, n)
+                    decoded, _ = dec_net.fwd(noised.contiguous(), training=False)
+                    decoded = decoded.float()
+                    vals.append((decoded.round().clamp(0, 1) - messages).abs().mean().reshape(1))
+                    vals.append(F.mse_loss(decoded, messages).reshape(1))
+                    name = getattr(n, "name", None) or type(n).__name__
+                    names += ['BER/' + name, 'dec_mse/' + name]
+                return torch.cat(vals), names
+        finally:
+            ed.train(was)
 
     def to_stirng(self):
         return '{}\n{}'.format(str(self.encoder_decoder), str(self.discriminator))

@@ -179,7 +179,12 @@ class IRNrhiModel(BaseModel):
         if opt['dist'] and torch.distributed.get_world_size() > 1:
             from ..distributed import GradSync
             grad_sync = GradSync()
-        self.hidden = Hidden(cfg, self.device, self.attack, None, compute_dtype=dtype, grad_sync=grad_sync, amp=self.amp)
+        # train.ssim_weight (default 0 = off): the structural-similarity fidelity term w * (-ssim(encoded, cover)) of the reference's trainers
+        # (models/IRN_model.py:569-570), logged as SSFW
+        self.hidden = Hidden(cfg, self.device, self.attack, None, compute_dtype=dtype, grad_sync=grad_sync, amp=self.amp,
+                             ssim_weight=float(_get(train_opt, 'ssim_weight', default=0.0) or 0.0))
+        # train.eval_metrics (default false): evaluate() appends robustness_report() to its logs
+        self.eval_metrics = bool(_get(train_opt, 'eval_metrics', default=False))
         # train.two_streams (default true): the step's two independent chains on two streams wherever a step has them to itself (one GPU, no
         # localisation branch / clipping / PSNR gate: Hidden._train_step_two_chains); same results bit for bit
         self.hidden.two_streams = bool(_get(train_opt, 'two_streams', default=True))
@@ -385,6 +390,8 @@ class IRNrhiModel(BaseModel):
             messages = torch.randint(0, 2, (self.real_H.shape[0], L), device=self.device).float()
             losses, _ = self.hidden.validate_on_batch([self.real_H, messages])
             logs = [(k.strip(), v) for k, v in losses.items()]
+            if self.eval_metrics:
+                logs += self.robustness_report(messages)
         # ---- finally (IRNrhi_model.py:690-698)
         if step % self.save_interval == 10 and self.rank <= 0 and train:
             self.save(self.global_step)
@@ -416,6 +423,61 @@ class IRNrhiModel(BaseModel):
             sheet = stitch_images(postprocess(x), *cols, img_per_row=1)
             os.makedirs(self.image_dump_dir, exist_ok=True)
             sheet.save(os.path.join(self.image_dump_dir, str(step).zfill(5) + ".png"))
+
+    @torch.no_grad()
+    def robustness_report(self, messages=None):
+        """How good the model is on the fed batch, in Progbar format [(name, float)]: ('PSNR', .), ('SSIM', .) of the watermarked batch, and per
+        layer of the attack cycle ('BER/<layer>', .), ('dec_mse/<layer>', .) (Hidden.evaluate_on_batch).  With train.localizer and a fed mask:
+        the tampered batch is built as in training (_gate: quantised encoded spliced with the previous batch by the mask), every non-geometric
+        attack runs on it, and the localiser's thresholded mask is scored against self.mask: ('F1/<layer>', .), ('precision/<layer>', .),
+        ('recall/<layer>', .).  Everything is computed on the device and read with one copy at the end."""
+        if self.real_H is None:
+            raise RuntimeError("robustness_report: feed_data first")
+        images = torch.clamp(self.real_H, 0, 1)
+        B = images.shape[0]
+        if messages is None:
+            messages = self.messages if self.messages is not None else torch.randint(0, 2, (B, self.hidden.config.message_length),
+                                                                                     device=self.device).float()
+        layers = self.attack.layers or [Identity()]
+        names_of = [getattr(l, "name", None) or type(l).__name__ for l in layers]
+
+        class _Fixed:   # one layer of the cycle with the cycle's fixed arguments (Resize 0.7, the Crop rectangle)
+            def __init__(self, cycle, i, name):
+                self.cycle, self.i, self.name = cycle, i, name
+
+            def fwd(self, image, cover=None):
+                out = self.cycle.fwd(image, id=self.i, cover=cover)
+                self.name = self.cycle.name   # (a layer may name itself in its forward: G_Blur -> GaussianBlur)
+                return out
+
+            def bwd(self, ctx, g):
+                return self.cycle.bwd(ctx, g)
+        noisers = [_Fixed(self.attack, i, n) for i, n in enumerate(names_of)] if self.attack.layers else [Identity()]
+        vals, names = self.hidden.evaluate_on_batch([images, messages], noisers)
+        vals, names = [vals], list(names)
+        if self.localizer is not None and self.mask is not None and self.previous_images is not None:
+            from .. import metrics
+            enc_net = self.netG.encoder
+            was = self.netG.training
+            self.netG.eval()
+            try:
+                encoded, _ = enc_net.fwd(images, messages.to(self.device, torch.float32).contiguous(), training=False)
+            finally:
+                self.netG.train(was)
+            _, tampered, _ = ops.splice_fwd(encoded, real=images, prev=self.previous_images, mask=self.mask)
+            for i, (layer, lname) in enumerate(zip(layers, names_of)):
+                if isinstance(layer, (Crop, Resize)):   # the localiser sees no geometric attack (IRNcrop_model.py:362-366)
+                    continue
+                attacked, _ = self.attack.fwd(tampered, id=i, cover=images)
+                lname = self.attack.name
+                pred = self.localise_mask(ops.clamp_quant(attacked.contiguous()))
+                c = ops.confusion_counts(pred, self.mask, 0.5, 0.5)[0]
+                sc = metrics.scores_from_counts(c)
+                tp, fp, fn = sc["TP"].double(), sc["FP"].double(), sc["FN"].double()
+                vals.append(torch.stack([sc["F1"], tp / (tp + fp), tp / (tp + fn)]).float())
+                names += ['F1/' + lname, 'precision/' + lname, 'recall/' + lname]
+        host = torch.cat(vals).tolist()   # the one device -> host read
+        return list(zip(names, host))
 
     def evaluate(self, *args, **kwargs):
         return self.optimize_parameters(self.global_step, train=False)

@@ -1699,6 +1699,105 @@ def psnr255(a, b):
     return psnr_gate(part, n)[0:1]
 
 
+# ----------------------------------------------------------------------------- image-quality and mask metrics (csrc/ssim.hip)
+_SSIM_WIN = None
+
+
+def ssim_window():
+    """the 11 taps of the reference's window (pytorch_ssim/__init__.py:7-9): Gaussian, sigma 1.5, gauss / gauss.sum() evaluated in float32"""
+    global _SSIM_WIN
+    if _SSIM_WIN is None:
+        import math
+        g = torch.tensor([math.exp(-((i - 5) ** 2) / (2 * 1.5 ** 2)) for i in range(11)], dtype=torch.float32)
+        _SSIM_WIN = _host_floats((g / g.sum()).tolist())
+    return _SSIM_WIN
+
+
+def _ssim_args(a, b):
+    _need_cuda(a, b)
+    if a.dim() != 4 or a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError("ssim: two float32 [B,C,H,W] images of one shape expected")
+    return a.contiguous(), b.contiguous()
+
+
+def ssim(a, b, size_average=True, want_grad=False):
+    """pytorch_ssim._ssim(a, b) with the 11 x 11 window: a 0-dim device tensor (size_average) or the [B] per-image means, no host sync.
+    want_grad: -> (value, dplanes [3,B,C,H,W]), the derivative planes ssim_bwd(dplanes, a, b, ...) turns into the gradient wrt a"""
+    a, b = _ssim_args(a, b)
+    B, C, H, W = a.shape
+    L = _lib.lib()
+    part = torch.empty(B * L.wm_ssim_nparts(C, H, W), device=a.device, dtype=torch.float64)
+    dpl = torch.empty((3,) + tuple(a.shape), device=a.device, dtype=torch.float32) if want_grad else None
+    out = torch.empty(1 + B, device=a.device, dtype=torch.float32)
+    rc = _timed("ssim_fwd", None, lambda: L.wm_ssim_fwd(_p(a), _p(b), B, C, H, W, ssim_window(), _p(part), _p(dpl), _stream()))
+    _lib.check(rc, "wm_ssim_fwd")
+    rc = L.wm_ssim_finalize(_p(part), B, C, H, W, _p(out), _stream())
+    _lib.check(rc, "wm_ssim_finalize")
+    val = out[0] if size_average else out[1:]
+    return (val, dpl) if want_grad else val
+
+
+def ssim_bwd(dplanes, a, b, gout=None, per_image=False, gscale=1.0, gscale_dev=None, out=None, accumulate=False):
+    """gradient wrt a of gscale * gscale_dev[0] * sum(gout * ssim(a, b)), from the planes ssim(a, b, want_grad=True) wrote.  gout: device
+    f32, one element (the mean's upstream gradient) or [B] with per_image (size_average=False); None = 1.  out: the buffer to write, or
+    with accumulate to add into (one launch, no axpy)"""
+    a, b = _ssim_args(a, b)
+    _need_cuda(dplanes, gout, gscale_dev, out)
+    B, C, H, W = a.shape
+    assert dplanes.shape == (3,) + tuple(a.shape) and dplanes.is_contiguous() and dplanes.dtype == torch.float32
+    if gout is not None:
+        gout = gout.contiguous()
+        assert gout.dtype == torch.float32 and gout.numel() == (B if per_image else 1)
+    if out is None:
+        if accumulate:
+            raise ValueError("ssim_bwd: accumulate needs the buffer to add into (out=)")
+        out = torch.empty_like(a)
+    assert out.shape == a.shape and out.is_contiguous() and out.dtype == torch.float32
+    rc = _timed("ssim_bwd", None, lambda: _lib.lib().wm_ssim_bwd(_p(dplanes), _p(a), _p(b), _p(out), B, C, H, W, ssim_window(), _p(gout),
+                                                                 1 if per_image else 0, gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
+    _lib.check(rc, "wm_ssim_bwd")
+    _wrote(out)
+    return out
+
+
+def psnr(a, b, max_val):
+    """metrics.PSNR(max_val)(a, b) on float images -> [1] device scalar (0 when equal), no host sync"""
+    _need_cuda(a, b)
+    a, b = a.contiguous().float(), b.contiguous().float()
+    if a.shape != b.shape:
+        raise ValueError("psnr: shapes disagree")
+    n = a.numel()
+    part = torch.empty(_nparts(n), device=a.device, dtype=torch.float64)
+    out = torch.empty(1, device=a.device, dtype=torch.float32)
+    L = _lib.lib()
+    rc = _timed("psnr", None, lambda: L.wm_psnr_partials(_p(a), _p(b), n, _p(part), part.numel(), _stream()))
+    _lib.check(rc, "wm_psnr_partials")
+    rc = L.wm_psnr_finalize(_p(part), part.numel(), float(n), float(max_val), _p(out), _stream())
+    _lib.check(rc, "wm_psnr_finalize")
+    return out
+
+
+def confusion_counts(pred, gt, thr_pred, thr_gt):
+    """pred, gt: masks [B, ...] (float32 or uint8) of one shape -> int64 [1 + B, 4] device tensor: row 0 the totals, row 1 + b image b's
+    (TN, TP, FN, FP) of pred > thr_pred against gt > thr_gt (calculate_f1.py:5-20), exact"""
+    _need_cuda(pred, gt)
+    if pred.shape != gt.shape or pred.dim() < 1 or pred.numel() == 0:
+        raise ValueError("confusion_counts: two non-empty masks of one shape expected")
+    for t in (pred, gt):
+        if t.dtype not in (torch.float32, torch.uint8):
+            raise TypeError("confusion_counts: float32 or uint8 masks")
+    pred, gt = pred.contiguous(), gt.contiguous()
+    B = pred.shape[0]
+    per = pred.numel() // B
+    L = _lib.lib()
+    part = torch.empty(B * L.wm_confusion_nparts(per) * 4, device=pred.device, dtype=torch.int64)
+    out = torch.empty(1 + B, 4, device=pred.device, dtype=torch.int64)
+    rc = _timed("confusion_counts", None, lambda: L.wm_confusion_counts(_p(pred), int(pred.dtype == torch.uint8), _p(gt), int(gt.dtype == torch.uint8),
+                                                                        thr_pred, thr_gt, B, per, _p(part), _p(out), _stream()))
+    _lib.check(rc, "wm_confusion_counts")
+    return out
+
+
 def scale_dev_(x, scale_dev):
     """x *= scale_dev[0] (a device scalar)"""
     _need_cuda(x, scale_dev)
