@@ -79,37 +79,45 @@ def _merge(p, H, W):
 
 
 def compress(x, factor, rounding):
-    """x [B,3,H,W] in [0,1], H,W multiples of 16 -> (y [B,HW/64,8,8], cb, cr [B,HW/256,8,8])."""
+    """x [B,3,H,W] in [0,1], H,W multiples of 16 -> (y [B,HW/64,8,8], cb, cr [B,HW/256,8,8]).
+    The constants are the reference's float32 values; they and the arithmetic follow x.dtype (float32 like the reference, or float64)."""
+    dt = x.dtype
     img = (x * 255).permute(0, 2, 3, 1)
     m = torch.from_numpy(np.array([[0.299, 0.587, 0.114], [-0.168736, -0.331264, 0.5],
-                                   [0.5, -0.418688, -0.081312]], dtype=np.float32).T.copy())
-    ycc = torch.tensordot(img, m, dims=1) + torch.tensor([0., 128., 128.])
+                                   [0.5, -0.418688, -0.081312]], dtype=np.float32).T.copy()).to(dt)
+    ycc = torch.tensordot(img, m, dims=1) + torch.tensor([0., 128., 128.], dtype=dt)
     ycc_c = ycc.permute(0, 3, 1, 2)
     cb = F.avg_pool2d(ycc_c[:, 1:2], 2, 2)[:, 0]
     cr = F.avg_pool2d(ycc_c[:, 2:3], 2, 2)[:, 0]
     yy = ycc[..., 0]
-    T, scale = _dct_tensor()
+    T, scale = (t.to(dt) for t in _dct_tensor())
     outs = []
     for comp, tbl in ((yy, Y_TABLE), (cb, C_TABLE), (cr, C_TABLE)):
         blk = _split(comp) - 128
         d = scale * torch.tensordot(blk, T, dims=2)
-        outs.append(rounding(d / (tbl * factor)))
+        outs.append(rounding(d / (tbl * factor).to(dt)))
     return tuple(outs)
 
 
-def decompress(y, cb, cr, H, W, factor):
-    T, alpha = _idct_tensor()
+def decompress_rgb(y, cb, cr, H, W, factor):
+    """decompress_jpeg up to its clamp: RGB on the 0..255 scale, not yet limited to it."""
+    dt = y.dtype
+    T, alpha = (t.to(dt) for t in _idct_tensor())
     comps = []
     for comp, tbl, (h, w) in ((y, Y_TABLE, (H, W)), (cb, C_TABLE, (H // 2, W // 2)), (cr, C_TABLE, (H // 2, W // 2))):
-        d = comp * (tbl * factor)
+        d = comp * (tbl * factor).to(dt)
         img = 0.25 * torch.tensordot(d * alpha, T, dims=2) + 128
         comps.append(_merge(img, h, w))
     yy, cbb, crr = comps
     cbb = cbb.repeat_interleave(2, 1).repeat_interleave(2, 2)
     crr = crr.repeat_interleave(2, 1).repeat_interleave(2, 2)
     img = torch.stack([yy, cbb, crr], dim=3)
-    m = torch.from_numpy(np.array([[1., 0., 1.402], [1, -0.344136, -0.714136], [1, 1.772, 0]], dtype=np.float32).T.copy())
-    rgb = torch.tensordot(img + torch.tensor([0, -128., -128.]), m, dims=1).permute(0, 3, 1, 2)
+    m = torch.from_numpy(np.array([[1., 0., 1.402], [1, -0.344136, -0.714136], [1, 1.772, 0]], dtype=np.float32).T.copy()).to(dt)
+    return torch.tensordot(img + torch.tensor([0, -128., -128.], dtype=dt), m, dims=1).permute(0, 3, 1, 2)
+
+
+def decompress(y, cb, cr, H, W, factor):
+    rgb = decompress_rgb(y, cb, cr, H, W, factor)
     rgb = torch.min(255 * torch.ones_like(rgb), torch.max(torch.zeros_like(rgb), rgb))
     return rgb / 255
 

@@ -248,6 +248,7 @@ __device__ __forceinline__ void store_act16_t(T* __restrict__ a, const Task& t, 
         for (int c = 0; c < 3; ++c)
 #pragma unroll
             for (int j = 0; j < 8; ++j) lds[(c * 8 + r) * LDS_BLK + blk * 8 + j] = v[c][j];
+        wave_lds_sync();  // the reads below take other lanes' entries (t.valid is wave-uniform: no lane has left yet)
         if (!t.valid) return;
         const int lane = threadIdx.x & 63, y0 = t.y - r, xs = t.x0 - blk * 8;
 #pragma unroll
