@@ -733,6 +733,39 @@ int wm_confusion_nparts(size_t per_image);
 int wm_confusion_counts(const void* pred, int pred_u8, const void* gt, int gt_u8, float thr_pred, float thr_gt, int B, size_t per_image,
                         long long* partials, long long* out, void* stream);
 
+/* ------------------------------------------------------------------ Dice (overlap) loss (csrc/dice.hip)
+ * replaces dice_loss.py:44-61 (BinaryDiceLoss.forward: the mask-head loss tianchi_model.py:48,101 constructs), :81-96 (DiceLoss.forward: softmax
+ * over the classes, the class loop with ignore_index and weight, / C) and the autograd backward of both.  Everything f32; no atomics, no
+ * host synchronisation: double partials per workgroup and a fixed-order finalise, bitwise reproducible.  B <= 65535.
+ * pw (the reference's p): 1 and 2 take paths without powf, any other positive value goes through powf.
+ * reduction: WM_DICE_MEAN / WM_DICE_SUM (one device scalar) / WM_DICE_NONE ([B]).
+ * wm_dice_sums: p, target [B, per_sample] (any per_sample: 16-byte loads with a scalar head and tail) ->
+ *   partials [B * wm_dice_nparts(per_sample) * 3] doubles, sample b's contiguous: {sum p*t, sum p^pw, sum t^pw} per workgroup.
+ * wm_dice_softmax_sums: logits, target [B,C,HW] (NCHW planes, C <= 32, WM_E_BADARG above); s = softmax over the C planes, formed per pixel
+ *   and never written -> partials [B*C * wm_dice_nparts(HW) * 3] doubles, unit (b, c)'s contiguous: the same three sums of (s_c, t_c).
+ * wm_dice_finalize: C = 1 (with ignore_index < 0, weight NULL) for wm_dice_sums' partials.  coef [B*C][2] doubles = {num = sum p*t + smooth,
+ *   den = sum p^pw + sum t^pw + smooth} per unit (what the backward reads); loss_b = sum_c w_c (1 - num/den) / C with
+ *   w_c = (c == ignore_index ? 0 : weight ? weight[c] (device, [C]) : 1) -- the division is by C even when a class is ignored, as :96 --;
+ *   loss_out = [B] (none), or one scalar: sum_b loss_b (sum), that / B (mean).
+ * wm_dice_bwd: grad (+)= g * (num * pw * p^(pw-1) - t * den) / den^2, g = gscale * gscale_dev[0] (device, may be NULL) *
+ *   gout_dev[none ? b : 0] (device, may be NULL = 1) / (mean ? B : 1); chain_sigmoid != 0: p is a sigmoid output s(z) (the UNet head) and the
+ *   gradient is taken wrt z (multiplied by p*(1-p)), as wm_bce_logits_target does; accumulate != 0 adds into grad.
+ * wm_dice_softmax_bwd: grad (+)= d loss / d logits: dz_c = s_c * (g_c - sum_k g_k s_k), g_c = g * w_c / C * (the binary derivative of unit
+ *   (b, c) at s_c); the softmax is recomputed per pixel.  Same g, ignore_index and weight as the finalise call. */
+#define WM_DICE_MEAN 0
+#define WM_DICE_SUM 1
+#define WM_DICE_NONE 2
+int wm_dice_nparts(size_t per_sample);
+int wm_dice_sums(const float* p, const float* target, int B, size_t per_sample, float pw, double* partials, void* stream);
+int wm_dice_softmax_sums(const float* logits, const float* target, int B, int C, size_t HW, float pw, double* partials, void* stream);
+int wm_dice_finalize(const double* partials, int B, int C, size_t per_sample, double smooth, int reduction, int ignore_index,
+                     const float* weight, double* coef, float* loss_out, void* stream);
+int wm_dice_bwd(const float* p, const float* target, const double* coef, float* grad, int B, size_t per_sample, float pw, int reduction,
+                const float* gout_dev, float gscale, const float* gscale_dev, int chain_sigmoid, int accumulate, void* stream);
+int wm_dice_softmax_bwd(const float* logits, const float* target, const double* coef, float* grad, int B, int C, size_t HW, float pw,
+                        int reduction, int ignore_index, const float* weight, const float* gout_dev, float gscale, const float* gscale_dev,
+                        int accumulate, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -212,6 +212,9 @@ class IRNrhiModel(BaseModel):
                 self.optimizer_localizer.attach_amp(self.amp)
             self.optimizers.append(self.optimizer_localizer)
             self.localizer_weight = _get(train_opt, 'localizer_weight', default=1.0)
+            # train.dice_weight (default 0 = off): w * BinaryDiceLoss()(pred, mask) next to the BCE term (the reference's dice_loss.py, the
+            # mask-head loss of its tianchi_model.py:48,101); its gradient is added into the BCE gradient by the Dice backward itself; logged as Dice
+            self.dice_weight = float(_get(train_opt, 'dice_weight', default=0.0) or 0.0)
         self.psnr_gate = bool(_get(train_opt, 'psnr_gate', default=True))   # IRNcrop_model.py:379-388
         # log side (IRNcrop_model.py:78,399-400: SummaryWriter scalars; :421-437: an image sheet every 500 steps at step % 500 == 10)
         tb_dir = _get(train_opt, 'tensorboard_dir', default=None)
@@ -309,6 +312,10 @@ class IRNrhiModel(BaseModel):
             # the reference applies BCEWithLogits to the sigmoid output (:378,391-393); the kernel chains sigmoid'
             loss, g_logit = ops.bce_logits_target(pred, mask, self.localizer_weight, chain_sigmoid=True,
                                                   gscale_dev=self.amp.scale if self.amp is not None else None)
+            dice = None
+            if self.dice_weight > 0:   # three launches: sums, finalise, backward accumulated into g_logit (the same loss scale, on the device)
+                dice, _ = ops.dice_binary(pred, mask, 1.0, 2.0, 'mean', want_grad=True, chain_sigmoid=True, gscale=self.dice_weight,
+                                          gscale_dev=self.amp.scale if self.amp is not None else None, grad_out=g_logit)
             grads = engine.grad_dict(net)
             # data parallel: the localiser's 31 MB of gradients leave in four reverse-order buckets from inside its backward
             gs, pending = self.grad_sync, []
@@ -327,7 +334,7 @@ class IRNrhiModel(BaseModel):
         self.optimizer_localizer.step(grad_scale=gscale)
         g_tamp = self.attack.bwd(cA, g_att)
         ops.masked_axpy_(g_enc, g_tamp.contiguous(), mask)
-        return [('lB', loss), ('CE', loss), ('Kind', kind), ('LocKind', self.attack.name)]
+        return [('lB', loss), ('CE', loss)] + ([('Dice', dice)] if dice is not None else []) + [('Kind', kind), ('LocKind', self.attack.name)]
 
     def _clip(self, flats):
         if self.gradient_clipping:

@@ -1808,6 +1808,134 @@ def scale_dev_(x, scale_dev):
     return x
 
 
+# ----------------------------------------------------------------------------- Dice loss (csrc/dice.hip)
+DICE_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}    # WM_DICE_MEAN / WM_DICE_SUM / WM_DICE_NONE
+
+
+def _dice_reduction(reduction):
+    try:
+        return DICE_REDUCTIONS[reduction]
+    except (KeyError, TypeError):
+        raise Exception('Unexpected reduction {}'.format(reduction)) from None   # the reference's exception (dice_loss.py:61)
+
+
+def _dice_pair(name, a, b):
+    _need_cuda(a, b)
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise TypeError(name + ": float32 tensors expected")
+    return a.contiguous(), b.contiguous()
+
+
+def _dice_finalize(L, part, B, C, per, smooth, red, ignore_index, weight, device):
+    coef = torch.empty(B * C, 2, device=device, dtype=torch.float64)
+    loss = torch.empty(B if red == DICE_REDUCTIONS["none"] else 1, device=device, dtype=torch.float32)
+    rc = L.wm_dice_finalize(_p(part), B, C, per, float(smooth), red, -1 if ignore_index is None else int(ignore_index), _p(weight), _p(coef),
+                            _p(loss), _stream())
+    _lib.check(rc, "wm_dice_finalize")
+    return loss, coef
+
+
+def _dice_bwd_args(name, x, gout, B, red, gscale_dev, out, accumulate):
+    _need_cuda(gout, gscale_dev, out)
+    if gout is not None:
+        gout = gout.contiguous()
+        assert gout.dtype == torch.float32 and gout.numel() == (B if red == DICE_REDUCTIONS["none"] else 1)
+    if out is None:
+        if accumulate:
+            raise ValueError(name + ": accumulate needs the buffer to add into (out=)")
+        out = torch.empty_like(x)
+    assert out.numel() == x.numel() and out.is_contiguous() and out.dtype == torch.float32
+    return gout, out
+
+
+def dice_binary_fwd(p, target, smooth=1.0, pw=2.0, reduction="mean"):
+    """BinaryDiceLoss(smooth, pw, reduction)(p, target) for float32 [B, ...] tensors -> (loss, coef): loss a [1] device tensor (mean, sum) or
+    [B] (none); coef [B,2] float64 = (num, den) per sample, what dice_binary_bwd reads.  Two launches, no host sync"""
+    red = _dice_reduction(reduction)
+    p, target = _dice_pair("dice_binary", p, target)
+    B = p.shape[0]
+    if B == 0 or p.numel() != target.numel() or p.numel() == 0:
+        raise ValueError("dice_binary: two non-empty tensors of one size expected")
+    per = p.numel() // B
+    L = _lib.lib()
+    part = torch.empty(B * L.wm_dice_nparts(per) * 3, device=p.device, dtype=torch.float64)
+    rc = _timed("dice_sums", None, lambda: L.wm_dice_sums(_p(p), _p(target), B, per, float(pw), _p(part), _stream()))
+    _lib.check(rc, "wm_dice_sums")
+    return _dice_finalize(L, part, B, 1, per, smooth, red, None, None, p.device)
+
+
+def dice_binary_bwd(p, target, coef, pw=2.0, reduction="mean", gout=None, gscale=1.0, gscale_dev=None, chain_sigmoid=False, out=None,
+                    accumulate=False):
+    """gradient wrt p of gscale * gscale_dev[0] * sum(gout * loss) from the coef dice_binary_fwd wrote; chain_sigmoid: p is a sigmoid
+    output s(z) and the gradient is wrt z.  gout: device f32, one element or [B] with reduction none; None = 1.  out: the buffer to write,
+    or with accumulate to add into (one launch, no axpy)"""
+    red = _dice_reduction(reduction)
+    p, target = _dice_pair("dice_binary_bwd", p, target)
+    B = p.shape[0]
+    gout, out = _dice_bwd_args("dice_binary_bwd", p, gout, B, red, gscale_dev, out, accumulate)
+    rc = _timed("dice_bwd", None, lambda: _lib.lib().wm_dice_bwd(_p(p), _p(target), _p(coef), _p(out), B, p.numel() // B, float(pw), red, _p(gout),
+                                                                 gscale, _p(gscale_dev), 1 if chain_sigmoid else 0, 1 if accumulate else 0, _stream()))
+    _lib.check(rc, "wm_dice_bwd")
+    _wrote(out)
+    return out
+
+
+def dice_binary(p, target, smooth=1.0, pw=2.0, reduction="mean", want_grad=True, chain_sigmoid=False, gscale=1.0, gscale_dev=None, grad_out=None):
+    """the binary Dice loss and its gradient: (loss, grad or None), loss UNSCALED, grad = gscale * gscale_dev[0] * d loss / d p (wrt the
+    pre-sigmoid input with chain_sigmoid).  grad_out: an existing gradient buffer of p's size the result is ADDED into (and returned)"""
+    loss, coef = dice_binary_fwd(p, target, smooth, pw, reduction)
+    if not want_grad:
+        return loss, None
+    return loss, dice_binary_bwd(p, target, coef, pw, reduction, None, gscale, gscale_dev, chain_sigmoid, grad_out, grad_out is not None)
+
+
+def _dice_softmax_args(logits, target, weight):
+    logits, target = _dice_pair("dice_softmax", logits, target)
+    if logits.dim() < 2 or logits.shape != target.shape or logits.numel() == 0:
+        raise ValueError("dice_softmax: two non-empty float32 [B,C,...] tensors of one shape expected")
+    B, C = logits.shape[0], logits.shape[1]
+    if weight is not None:
+        _need_cuda(weight)
+        weight = weight.contiguous()
+        assert weight.dtype == torch.float32 and weight.numel() == C
+    return logits, target, weight, B, C, logits.numel() // (B * C)
+
+
+def dice_softmax_fwd(logits, target, smooth=1.0, pw=2.0, reduction="mean", ignore_index=None, weight=None):
+    """DiceLoss(weight, ignore_index, smooth=, p=, reduction=)(logits, target) on float32 [B,C,...] logits and one-hot targets, C <= 32 ->
+    (loss, coef [B*C,2] float64).  The softmax over the classes is formed inside the kernel and never written"""
+    red = _dice_reduction(reduction)
+    logits, target, weight, B, C, HW = _dice_softmax_args(logits, target, weight)
+    L = _lib.lib()
+    part = torch.empty(B * C * L.wm_dice_nparts(HW) * 3, device=logits.device, dtype=torch.float64)
+    rc = _timed("dice_softmax_sums", None, lambda: L.wm_dice_softmax_sums(_p(logits), _p(target), B, C, HW, float(pw), _p(part), _stream()))
+    _lib.check(rc, "wm_dice_softmax_sums")
+    return _dice_finalize(L, part, B, C, HW, smooth, red, ignore_index, weight, logits.device)
+
+
+def dice_softmax_bwd(logits, target, coef, pw=2.0, reduction="mean", ignore_index=None, weight=None, gout=None, gscale=1.0, gscale_dev=None,
+                     out=None, accumulate=False):
+    """gradient wrt the logits of gscale * gscale_dev[0] * sum(gout * loss), from the coef dice_softmax_fwd wrote (same ignore_index, weight)"""
+    red = _dice_reduction(reduction)
+    logits, target, weight, B, C, HW = _dice_softmax_args(logits, target, weight)
+    gout, out = _dice_bwd_args("dice_softmax_bwd", logits, gout, B, red, gscale_dev, out, accumulate)
+    rc = _timed("dice_softmax_bwd", None, lambda: _lib.lib().wm_dice_softmax_bwd(
+        _p(logits), _p(target), _p(coef), _p(out), B, C, HW, float(pw), red, -1 if ignore_index is None else int(ignore_index), _p(weight), _p(gout),
+        gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
+    _lib.check(rc, "wm_dice_softmax_bwd")
+    _wrote(out)
+    return out
+
+
+def dice_softmax(logits, target, smooth=1.0, pw=2.0, reduction="mean", want_grad=True, ignore_index=None, weight=None, gscale=1.0,
+                 gscale_dev=None, grad_out=None):
+    """the multi-class Dice loss and its gradient wrt the logits: (loss, grad or None), as dice_binary"""
+    loss, coef = dice_softmax_fwd(logits, target, smooth, pw, reduction, ignore_index, weight)
+    if not want_grad:
+        return loss, None
+    return loss, dice_softmax_bwd(logits, target, coef, pw, reduction, ignore_index, weight, None, gscale, gscale_dev, grad_out, grad_out is not None)
+
+
 # ----------------------------------------------------------------------------- device RNG and the stochastic / JPEG-Drop attacks (csrc/noise.hip,
 # csrc/jpeg_drop.hip).  `state` is a layer's int64[RNG_STATE_WORDS] device tensor {seed, offset, ...}; a forward returns, beside its output,
 # rec = int64[2] {seed, offset} of the call, from which the backward regenerates the same draws
