@@ -766,6 +766,46 @@ int wm_dice_softmax_bwd(const float* logits, const float* target, const double* 
                         int reduction, int ignore_index, const float* weight, const float* gout_dev, float gscale, const float* gscale_dev,
                         int accumulate, void* stream);
 
+/* ------------------------------------------------------------------ pixel- and gradient-domain image losses (csrc/imgloss.hip)
+ * replaces models/modules/loss.py:5-22 (ReconstructionLoss), loss.py:413-423 (GradientLoss), loss.py:309-360 (ExclusionLoss) and the autograd
+ * backward of each.  f32 NCHW contiguous tensors; no atomics, no host synchronisation: double partials per workgroup and a fixed-order
+ * one-workgroup finalise, bitwise reproducible.  Every loss is one device scalar.  In every backward g = gscale * gscale_dev[0] (device, may
+ * be NULL) * gout_dev[0] (device, may be NULL = 1) and accumulate != 0 adds into the gradient buffer.
+ * wm_recon_sums: x, target [B, per_sample] (any per_sample: 16-byte loads with a scalar head and tail) -> partials [B * wm_recon_nparts(per_sample)]
+ *   doubles of sum f(x - t): f = d^2 (WM_RECON_L2), sqrt(d^2 + eps) (WM_RECON_LCHAR), d (WM_RECON_L1: the reference's signed sum, no abs).
+ * wm_recon_finalize: loss_out[0] = sum of the partials / B.
+ * wm_recon_bwd: grad (+)= g / B * f'(x - t); a negative gscale gives the gradient wrt the target.
+ * wm_gradloss_sums: a = N = B*C planes [H, W], H, W >= 2 -> partials [N * wm_gradloss_nparts(H, W) * 2] doubles {sum |a[y][x] - a[y][x+1]|,
+ *   sum |a[y][x] - a[y+1][x]|};  wm_gradloss_finalize: loss_out[0] = sum_x / (N H (W-1)) + sum_y / (N (H-1) W);
+ *   wm_gradloss_bwd: gather form, the subgradient of |.| at 0 is 0.
+ * wm_excl_fwd: img1 [B,C1,H,W], img2 [B,C2,H,W], 1 <= C1, C2 <= 4, 1 <= levels <= 3, H and W >= 2 << (levels - 1) (WM_E_BADARG otherwise: the
+ *   reference would take the mean of an empty tensor).  Level l is the image 2 x 2 average-pooled l times (floor); per level, direction
+ *   (0 = gradx, rows: img[y+1] - img[y]; 1 = grady, columns) and channel pair, s = 2 sigmoid(diff) - 1 and the sum of s1^2 s2^2 ->
+ *   partials [levels*2*C1*C2][wm_excl_nparts(B, H, W)] doubles.  Both images are read once (16 x 32 tiles with a 4-pixel halo, pooled in LDS).
+ * wm_excl_finalize: means [levels][2][C1*C2] doubles (term k = i2*C1 + i1 pairs img1's channel i1 with img2's i2: the reference's list order),
+ *   loss_out[0] = sum means^0.25 / (levels * 9) / 2 (9 whatever C1*C2 is, as the reference), coef [levels][2][C1*C2] doubles =
+ *   d loss / d (one product of that term) -- 0 for a term whose mean is 0: it contributes no gradient (the reference: NaN).
+ * wm_excl_bwd: gather form, one launch; grad1 / grad2 (either may be NULL) (+)= g * d loss / d img1, img2. */
+#define WM_RECON_L2 0
+#define WM_RECON_LCHAR 1
+#define WM_RECON_L1 2
+int wm_recon_nparts(size_t per_sample);
+int wm_recon_sums(const float* x, const float* target, int B, size_t per_sample, int kind, float eps, double* partials, void* stream);
+int wm_recon_finalize(const double* partials, int B, size_t per_sample, float* loss_out, void* stream);
+int wm_recon_bwd(const float* x, const float* target, float* grad, int B, size_t per_sample, int kind, float eps, const float* gout_dev,
+                 float gscale, const float* gscale_dev, int accumulate, void* stream);
+int wm_gradloss_nparts(int H, int W);
+int wm_gradloss_sums(const float* a, int N, int H, int W, double* partials, void* stream);
+int wm_gradloss_finalize(const double* partials, int N, int H, int W, float* loss_out, void* stream);
+int wm_gradloss_bwd(const float* a, float* grad, int N, int H, int W, const float* gout_dev, float gscale, const float* gscale_dev,
+                    int accumulate, void* stream);
+int wm_excl_nparts(int B, int H, int W);
+int wm_excl_fwd(const float* img1, const float* img2, int B, int C1, int C2, int H, int W, int levels, double* partials, void* stream);
+int wm_excl_finalize(const double* partials, int B, int C1, int C2, int H, int W, int levels, double* means, double* coef, float* loss_out,
+                     void* stream);
+int wm_excl_bwd(const float* img1, const float* img2, const double* coef, float* grad1, float* grad2, int B, int C1, int C2, int H, int W,
+                int levels, const float* gout_dev, float gscale, const float* gscale_dev, int accumulate, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

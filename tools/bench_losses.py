@@ -6,6 +6,9 @@
 Device events around each stage, the two alternating in one process, median over --iters rounds; also the Dice launches alone and the
 algorithmic bytes they move.  Prints one JSON line.
 
+Then the three image losses of csrc/imgloss.hip at 16 x 3 x 256 x 256 (forward + backward wrt every input), each against the same loss
+composed from torch ops under autograd on the same GPU: a second JSON line, {"image_losses": ...}.
+
     python tools/bench_losses.py [--iters 300] [--batch 16] [--size 256]
 """
 import argparse
@@ -70,6 +73,74 @@ def main():
     out["dice_added_us"] = round(out["bce_plus_dice_us_median"] - out["bce_only_us_median"], 2)
     out["dice_algorithmic_bytes"] = 2 * n + 4 * n       # sums read pred + mask; backward reads pred, mask, the gradient and writes it
     print(json.dumps(out))
+    print(json.dumps({"image_losses": image_losses(a)}))
+
+
+def _torch_exclusion(x, y, level=3):
+    """the exclusion loss from torch ops, as a trainer without the fused kernel would write it"""
+    total = 0
+    for _ in range(level):
+        for dx, dy in ((x[:, :, 1:] - x[:, :, :-1], y[:, :, 1:] - y[:, :, :-1]), (x[..., 1:] - x[..., :-1], y[..., 1:] - y[..., :-1])):
+            s1, s2 = 2 * torch.sigmoid(dx) - 1, 2 * torch.sigmoid(dy) - 1
+            for i in range(x.shape[1]):
+                for j in range(y.shape[1]):
+                    total = total + (s1[:, i] ** 2 * s2[:, j] ** 2).mean() ** 0.25
+        x, y = torch.nn.functional.avg_pool2d(x, 2), torch.nn.functional.avg_pool2d(y, 2)
+    return total / (level * 9) / 2
+
+
+def image_losses(a):
+    g = torch.Generator().manual_seed(2)
+    shape = (a.batch, 3, a.size, a.size)
+    x, y = torch.rand(shape, generator=g).cuda(), torch.rand(shape, generator=g).cuda()
+    xa, ya = x.clone().requires_grad_(True), y.clone().requires_grad_(True)
+
+    def hip_excl():
+        loss, _, coef = ops.exclusion_fwd(x, y, 3)
+        return loss, ops.exclusion_bwd(x, y, coef, 3)
+
+    def hip_recon():
+        loss, gx = ops.recon_loss(x, y, "l_char", 1e-6, want_grad=True)
+        return loss, gx, ops.recon_loss_bwd(x, y, "l_char", 1e-6, gscale=-1.0)
+
+    def hip_gradl():
+        return ops.gradient_loss(x), ops.gradient_loss_bwd(x)
+
+    def torch_excl():
+        return torch.autograd.grad(_torch_exclusion(xa, ya), (xa, ya))
+
+    def torch_recon():
+        d = xa - ya
+        return torch.autograd.grad(torch.sqrt(d * d + 1e-6).sum((1, 2, 3)).mean(), (xa, ya))
+
+    def torch_gradl():
+        return torch.autograd.grad((xa[..., :-1] - xa[..., 1:]).abs().mean() + (xa[:, :, :-1] - xa[:, :, 1:]).abs().mean(), xa)
+
+    stages = {"exclusion_hip": hip_excl, "exclusion_torch": torch_excl, "recon_l_char_hip": hip_recon, "recon_l_char_torch": torch_recon,
+              "gradient_hip": hip_gradl, "gradient_torch": torch_gradl}
+    for fn in stages.values():
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    iters = max(10, a.iters // 6)
+    times = {k: [] for k in stages}
+    for _ in range(iters):
+        for k, fn in stages.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) * 1e3)
+    n = x.numel() * 4
+    out = {"shape": list(shape), "iters": iters, "what": "forward + backward wrt every input, device events, microseconds"}
+    for k, v in times.items():
+        v.sort()
+        out[k + "_us_median"] = round(statistics.median(v), 2)
+        out[k + "_us_p10_p90"] = [round(v[len(v) // 10], 2), round(v[(9 * len(v)) // 10], 2)]
+    # algorithmic bytes: the forward reads both images once; the backward reads them once more and writes the gradients
+    out["algorithmic_bytes"] = {"exclusion": 2 * n + 2 * n + 2 * n, "recon": 2 * n + 2 * (2 * n + n), "gradient": n + n + n}
+    return out
 
 
 if __name__ == "__main__":

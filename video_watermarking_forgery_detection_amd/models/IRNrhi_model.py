@@ -181,8 +181,13 @@ class IRNrhiModel(BaseModel):
             grad_sync = GradSync()
         # train.ssim_weight (default 0 = off): the structural-similarity fidelity term w * (-ssim(encoded, cover)) of the reference's trainers
         # (models/IRN_model.py:569-570), logged as SSFW
+        # train.lambda_fit_forw (default 0 = off) and train.pixel_criterion_forw (l2 | l1 | l_char, default l2), the reference's own keys
+        # (models/IRNrhi_model.py:102,153-155): lambda_fit_forw * ReconstructionLoss(encoded, cover, pixel_criterion_forw), logged as RecFW.
+        # The term is a per-sample SUM, 196,608 x an MSE at 3 x 256 x 256
         self.hidden = Hidden(cfg, self.device, self.attack, None, compute_dtype=dtype, grad_sync=grad_sync, amp=self.amp,
-                             ssim_weight=float(_get(train_opt, 'ssim_weight', default=0.0) or 0.0))
+                             ssim_weight=float(_get(train_opt, 'ssim_weight', default=0.0) or 0.0),
+                             recon_weight=float(_get(train_opt, 'lambda_fit_forw', default=0.0) or 0.0),
+                             recon_type=_get(train_opt, 'pixel_criterion_forw', default='l2') or 'l2')
         # train.eval_metrics (default false): evaluate() appends robustness_report() to its logs
         self.eval_metrics = bool(_get(train_opt, 'eval_metrics', default=False))
         # train.two_streams (default true): the step's two independent chains on two streams wherever a step has them to itself (one GPU, no

@@ -1936,6 +1936,157 @@ def dice_softmax(logits, target, smooth=1.0, pw=2.0, reduction="mean", want_grad
     return loss, dice_softmax_bwd(logits, target, coef, pw, reduction, ignore_index, weight, None, gscale, gscale_dev, grad_out, grad_out is not None)
 
 
+# ----------------------------------------------------------------------------- pixel- and gradient-domain image losses (csrc/imgloss.hip)
+RECON_KINDS = {"l2": 0, "l_char": 1, "l1": 2}    # WM_RECON_L2 / WM_RECON_LCHAR / WM_RECON_L1
+
+
+def _f32_cuda(name, *ts):
+    _need_cuda(*ts)
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError(name + ": contiguous float32 tensors expected")
+
+
+def _loss_bwd_args(name, x, gout, gscale_dev, out, accumulate):
+    _need_cuda(gout, gscale_dev, out)
+    if gout is not None:
+        gout = gout.contiguous()
+        assert gout.dtype == torch.float32 and gout.numel() == 1
+    if out is None:
+        if accumulate:
+            raise ValueError(name + ": accumulate needs the buffer to add into (out=)")
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.is_contiguous() and out.dtype == torch.float32
+    return gout, out
+
+
+def _recon_args(name, x, t, kind):
+    if kind not in RECON_KINDS:
+        raise ValueError("%s: kind must be one of %s, got %r" % (name, ", ".join(RECON_KINDS), kind))
+    _f32_cuda(name, x, t)
+    if x.dim() < 1 or x.shape != t.shape or x.numel() == 0:
+        raise ValueError(name + ": two non-empty tensors of one shape expected")
+    return x.shape[0], x.numel() // x.shape[0], RECON_KINDS[kind]
+
+
+def recon_loss_fwd(x, t, kind="l_char", eps=1e-6):
+    """ReconstructionLoss(eps=eps)(x, t, kind): mean over the batch of the per-sample SUM of f(x - t), f = d^2 (l2), sqrt(d^2 + eps)
+    (l_char) or d (l1: the reference's signed sum, without abs) -> a [1] device tensor.  Two launches, no host sync"""
+    B, per, k = _recon_args("recon_loss", x, t, kind)
+    L = _lib.lib()
+    part = torch.empty(B * L.wm_recon_nparts(per), device=x.device, dtype=torch.float64)
+    loss = torch.empty(1, device=x.device, dtype=torch.float32)
+    rc = _timed("recon_sums", None, lambda: L.wm_recon_sums(_p(x), _p(t), B, per, k, float(eps), _p(part), _stream()))
+    _lib.check(rc, "wm_recon_sums")
+    rc = L.wm_recon_finalize(_p(part), B, per, _p(loss), _stream())
+    _lib.check(rc, "wm_recon_finalize")
+    return loss
+
+
+def recon_loss_bwd(x, t, kind="l_char", eps=1e-6, gout=None, gscale=1.0, gscale_dev=None, out=None, accumulate=False):
+    """gradient wrt x of gscale * gscale_dev[0] * gout[0] * recon_loss(x, t); a negative gscale gives the gradient wrt t.  out: the buffer to
+    write, or with accumulate to add into (one launch, no axpy)"""
+    B, per, k = _recon_args("recon_loss_bwd", x, t, kind)
+    gout, out = _loss_bwd_args("recon_loss_bwd", x, gout, gscale_dev, out, accumulate)
+    rc = _timed("recon_bwd", None, lambda: _lib.lib().wm_recon_bwd(_p(x), _p(t), _p(out), B, per, k, float(eps), _p(gout), gscale, _p(gscale_dev),
+                                                                   1 if accumulate else 0, _stream()))
+    _lib.check(rc, "wm_recon_bwd")
+    _wrote(out)
+    return out
+
+
+def recon_loss(x, t, kind="l_char", eps=1e-6, want_grad=False, gscale=1.0, gscale_dev=None, grad_out=None):
+    """the reconstruction loss, and with want_grad its gradient wrt x: a [1] device tensor, or (loss, grad) with loss UNSCALED and
+    grad = gscale * gscale_dev[0] * d loss / dx.  grad_out: an existing gradient buffer the result is ADDED into (and returned)"""
+    loss = recon_loss_fwd(x, t, kind, eps)
+    if not want_grad:
+        return loss
+    return loss, recon_loss_bwd(x, t, kind, eps, None, gscale, gscale_dev, grad_out, grad_out is not None)
+
+
+def _gradloss_args(name, a):
+    _f32_cuda(name, a)
+    if a.dim() != 4 or a.numel() == 0:
+        raise ValueError(name + ": a non-empty [B,C,H,W] tensor expected")
+    return a.shape[0] * a.shape[1], a.shape[2], a.shape[3]
+
+
+def gradient_loss(a):
+    """GradientLoss()(a): mean |a[..., :-1] - a[..., 1:]| + mean |a[..., :-1, :] - a[..., 1:, :]| -> a [1] device tensor; H, W >= 2"""
+    N, H, W = _gradloss_args("gradient_loss", a)
+    L = _lib.lib()
+    part = torch.empty(N * max(1, L.wm_gradloss_nparts(H, W)) * 2, device=a.device, dtype=torch.float64)
+    loss = torch.empty(1, device=a.device, dtype=torch.float32)
+    rc = _timed("gradloss_sums", None, lambda: L.wm_gradloss_sums(_p(a), N, H, W, _p(part), _stream()))
+    _lib.check(rc, "wm_gradloss_sums")
+    rc = L.wm_gradloss_finalize(_p(part), N, H, W, _p(loss), _stream())
+    _lib.check(rc, "wm_gradloss_finalize")
+    return loss
+
+
+def gradient_loss_bwd(a, gout=None, gscale=1.0, gscale_dev=None, out=None, accumulate=False):
+    """gradient wrt a of gscale * gscale_dev[0] * gout[0] * gradient_loss(a); the subgradient of |.| at 0 is 0, as torch's"""
+    N, H, W = _gradloss_args("gradient_loss_bwd", a)
+    gout, out = _loss_bwd_args("gradient_loss_bwd", a, gout, gscale_dev, out, accumulate)
+    rc = _timed("gradloss_bwd", None, lambda: _lib.lib().wm_gradloss_bwd(_p(a), _p(out), N, H, W, _p(gout), gscale, _p(gscale_dev),
+                                                                         1 if accumulate else 0, _stream()))
+    _lib.check(rc, "wm_gradloss_bwd")
+    _wrote(out)
+    return out
+
+
+def _excl_args(name, img1, img2, level):
+    _f32_cuda(name, img1, img2)
+    if img1.dim() != 4 or img2.dim() != 4 or img1.shape[0] != img2.shape[0] or img1.shape[2:] != img2.shape[2:] or img1.numel() == 0:
+        raise ValueError(name + ": two non-empty [B,C,H,W] tensors of one batch and image size expected")
+    return img1.shape[0], img1.shape[1], img2.shape[1], img1.shape[2], img1.shape[3], int(level)
+
+
+def exclusion_fwd(img1, img2, level=3):
+    """ExclusionLoss(level)(img1, img2) -> (loss [1] f32, means [level, 2, C1*C2] f64, coef [level, 2, C1*C2] f64 -- what exclusion_bwd reads).
+    means[l, d, i2*C1 + i1] = mean of s1^2 s2^2 over level l's differences in direction d (0 = gradx, 1 = grady) of img1's channel i1 and
+    img2's i2.  1 <= level <= 3, 1 <= C1, C2 <= 4, H and W >= 2 << (level - 1) (the library refuses anything else).  Two launches, no host sync"""
+    B, C1, C2, H, W, level = _excl_args("exclusion", img1, img2, level)
+    L = _lib.lib()
+    n = max(1, level) * 2 * C1 * C2
+    part = torch.empty(n * max(1, L.wm_excl_nparts(B, H, W)), device=img1.device, dtype=torch.float64)
+    rc = _timed("excl_fwd", None, lambda: L.wm_excl_fwd(_p(img1), _p(img2), B, C1, C2, H, W, level, _p(part), _stream()))
+    _lib.check(rc, "wm_excl_fwd")
+    means = torch.empty(level, 2, C1 * C2, device=img1.device, dtype=torch.float64)
+    coef = torch.empty_like(means)
+    loss = torch.empty(1, device=img1.device, dtype=torch.float32)
+    rc = L.wm_excl_finalize(_p(part), B, C1, C2, H, W, level, _p(means), _p(coef), _p(loss), _stream())
+    _lib.check(rc, "wm_excl_finalize")
+    return loss, means, coef
+
+
+def exclusion(img1, img2, level=3, want_terms=False):
+    """the exclusion loss as a [1] device tensor; want_terms: (loss, the [level, 2, C1*C2] float64 means under the fourth roots)"""
+    loss, means, _ = exclusion_fwd(img1, img2, level)
+    return (loss, means) if want_terms else loss
+
+
+def exclusion_bwd(img1, img2, coef, level=3, want=(True, True), gout=None, gscale=1.0, gscale_dev=None, out=(None, None), accumulate=False):
+    """gradients of gscale * gscale_dev[0] * gout[0] * exclusion(img1, img2, level) from the coef exclusion_fwd wrote -> (grad1, grad2), None
+    where want[i] is false.  out: buffers to write, or with accumulate to add into.  One launch.  A term whose mean is exactly 0 (a constant
+    image) contributes a zero gradient (the reference: NaN)"""
+    B, C1, C2, H, W, level = _excl_args("exclusion_bwd", img1, img2, level)
+    if not (want[0] or want[1]):
+        return None, None
+    _need_cuda(coef)
+    assert coef.dtype == torch.float64 and coef.is_contiguous() and coef.numel() == level * 2 * C1 * C2
+    g = []
+    for x, w, o in zip((img1, img2), want, out):
+        if w:
+            gout, o = _loss_bwd_args("exclusion_bwd", x, gout, gscale_dev, o, accumulate)
+        g.append(o if w else None)
+    rc = _timed("excl_bwd", None, lambda: _lib.lib().wm_excl_bwd(_p(img1), _p(img2), _p(coef), _p(g[0]), _p(g[1]), B, C1, C2, H, W, level, _p(gout),
+                                                                 gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
+    _lib.check(rc, "wm_excl_bwd")
+    _wrote(*g)
+    return g[0], g[1]
+
+
 # ----------------------------------------------------------------------------- device RNG and the stochastic / JPEG-Drop attacks (csrc/noise.hip,
 # csrc/jpeg_drop.hip).  `state` is a layer's int64[RNG_STATE_WORDS] device tensor {seed, offset, ...}; a forward returns, beside its output,
 # rec = int64[2] {seed, offset} of the call, from which the backward regenerates the same draws
