@@ -806,6 +806,42 @@ int wm_excl_finalize(const double* partials, int B, int C1, int C2, int H, int W
 int wm_excl_bwd(const float* img1, const float* img2, const double* coef, float* grad1, float* grad2, int B, int C1, int C2, int H, int W,
                 int levels, const float* gout_dev, float gscale, const float* gscale_dev, int accumulate, void* stream);
 
+/* ------------------------------------------------------------------ GAN objectives (csrc/advloss.hip)
+ * The reference's AdversarialLoss (loss.py:41-88), GANLoss and CWLoss (models/modules/loss.py:24-42, 77-109).  f32 contiguous tensors; no
+ * atomics, no host synchronisation: one streaming launch writes double partials per workgroup and, when asked, the gradient; a fixed-order
+ * one-workgroup finalise makes the device scalar.  Bitwise reproducible.  g = gscale * gscale_dev[0] (device, may be NULL) * gout_dev[0]
+ * (device, may be NULL = 1); accumulate != 0 adds into the gradient buffer.  Elements are evaluated in double and rounded once.
+ * wm_advloss_elem: x [n] (any n and alignment: 16-byte access with a scalar head and tail) -> partials [wm_advloss_nparts of n] doubles of
+ *   sum f(x_i, t_i), and with grad != NULL grad (+)= g / n * df/dx.  objective:
+ *     WM_ADV_BCE_PROB    -(t max(log x, -100) + (1 - t) max(log(1 - x), -100)), df/dx = (x - t) / max(x (1 - x), 1e-12): nn.BCELoss.
+ *                        x outside [0, 1] gives NaN
+ *     WM_ADV_BCE_LOGITS  (1 - t) x + max(-x, 0) + log(1 + exp(-|x|)): nn.BCEWithLogitsLoss, any label value
+ *     WM_ADV_MSE         (x - t)^2
+ *     WM_ADV_HINGE_DISC  relu(1 + s x) with the sign s passed in `label`: -1 (real) or +1 (fake); the subgradient at 0 is 0
+ *     WM_ADV_NEG_MEAN    -x;   WM_ADV_POS_MEAN  x   (label unused)
+ *   t = label when mask == NULL.  mask != NULL (the three objectives with a label): x is [B,C,H,W] with B*C*H*W == n, mask [B,Cm,Hm,Wm] with
+ *   Cm 1 or C, and t = real_label * (1 - m) with m the bilinear sample of the mask at the element's pixel (align_corners = False, no
+ *   antialiasing), taken inside the kernel; B, C, H, W, Cm, Hm, Wm, real_label are ignored otherwise.  No gradient goes to the mask.
+ * wm_advloss_finalize: loss_out[0] = sum of the partials / n.
+ * wm_cw_margin: logits [B,K] (K >= 2), target [B] int64 -> loss_out[0] = sum_b max(other_b - real_b, kappa) (is_targeted != 0) or
+ *   max(real_b - other_b, kappa), real = logits[b][target_b], other = max_j of (1 - onehot) logits - onehot * 10000 (the target's slot holds
+ *   -10000).  Two launches; terms = scratch [B] doubles.  grad (may be NULL) [B,K] (+)= g * d loss / d logits: -+w at the target column and
+ *   +-w at the lowest column attaining `other` (none when that is the target's own slot), w = 1 where the margin exceeds kappa, 1/2 at a tie,
+ *   0 where kappa wins.  A target outside [0, K) is never used as an index: that row's term and gradient row are NaN, so loss_out is NaN. */
+#define WM_ADV_BCE_PROB 0
+#define WM_ADV_BCE_LOGITS 1
+#define WM_ADV_MSE 2
+#define WM_ADV_HINGE_DISC 3
+#define WM_ADV_NEG_MEAN 4
+#define WM_ADV_POS_MEAN 5
+int wm_advloss_nparts(size_t n);
+int wm_advloss_elem(int objective, const float* x, size_t n, float label, const float* mask, int B, int C, int H, int W, int Cm, int Hm, int Wm,
+                    float real_label, double* partials, float* grad, const float* gout_dev, float gscale, const float* gscale_dev,
+                    int accumulate, void* stream);
+int wm_advloss_finalize(const double* partials, size_t n, float* loss_out, void* stream);
+int wm_cw_margin(const float* logits, const long long* target, int B, int K, int is_targeted, float kappa, double* terms, float* loss_out,
+                 float* grad, const float* gout_dev, float gscale, const float* gscale_dev, int accumulate, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

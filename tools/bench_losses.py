@@ -9,6 +9,10 @@ algorithmic bytes they move.  Prints one JSON line.
 Then the three image losses of csrc/imgloss.hip at 16 x 3 x 256 x 256 (forward + backward wrt every input), each against the same loss
 composed from torch ops under autograd on the same GPU: a second JSON line, {"image_losses": ...}.
 
+Then the GAN objectives of csrc/advloss.hip (loss + gradient, two launches each) at a discriminator map of batch x 1 x 30 x 30 and at
+batch x 1 x size x size, the masked labels from a size x size mask, and the Carlini-Wagner margin at batch x 1000, each against the torch
+composition under autograd: a third JSON line, {"gan_objectives": ...}.
+
     python tools/bench_losses.py [--iters 300] [--batch 16] [--size 256]
 """
 import argparse
@@ -74,6 +78,7 @@ def main():
     out["dice_algorithmic_bytes"] = 2 * n + 4 * n       # sums read pred + mask; backward reads pred, mask, the gradient and writes it
     print(json.dumps(out))
     print(json.dumps({"image_losses": image_losses(a)}))
+    print(json.dumps({"gan_objectives": gan_objectives(a)}))
 
 
 def _torch_exclusion(x, y, level=3):
@@ -140,6 +145,58 @@ def image_losses(a):
         out[k + "_us_p10_p90"] = [round(v[len(v) // 10], 2), round(v[(9 * len(v)) // 10], 2)]
     # algorithmic bytes: the forward reads both images once; the backward reads them once more and writes the gradients
     out["algorithmic_bytes"] = {"exclusion": 2 * n + 2 * n + 2 * n, "recon": 2 * n + 2 * (2 * n + n), "gradient": n + n + n}
+    return out
+
+
+def gan_objectives(a):
+    g = torch.Generator().manual_seed(3)
+    F = torch.nn.functional
+    maps = {"map30": torch.sigmoid(torch.randn((a.batch, 1, 30, 30), generator=g)).cuda(),
+            "full": torch.sigmoid(torch.randn((a.batch, 1, a.size, a.size), generator=g)).cuda()}
+    mask = (torch.rand((a.batch, 1, a.size, a.size), generator=g) < 0.15).float().cuda()
+    logits, target = (3 * torch.randn((a.batch, 1000), generator=g)).cuda(), torch.randint(0, 1000, (a.batch,), generator=g).cuda()
+    la = logits.clone().requires_grad_(True)
+    stages = {}
+    for name, x in maps.items():
+        xa = x.clone().requires_grad_(True)
+        ones = torch.ones_like(x)
+        for obj, label, ref in (("bce_prob", 1.0, lambda v, o=ones: F.binary_cross_entropy(v, o)),
+                                ("bce_logits", 0.9, lambda v, o=ones: F.binary_cross_entropy_with_logits(v, o * 0.9)),
+                                ("mse", 1.0, lambda v, o=ones: F.mse_loss(v, o)),
+                                ("hinge_disc", -1.0, lambda v: torch.relu(1 - v).mean()),
+                                ("neg_mean", None, lambda v: (-v).mean())):
+            stages["%s_%s_hip" % (obj, name)] = lambda x=x, obj=obj, label=label: ops.adv_loss(x, obj, label, want_grad=True)
+            stages["%s_%s_torch" % (obj, name)] = lambda xa=xa, ref=ref: torch.autograd.grad(ref(xa), xa)
+    x30, xa30 = maps["map30"], maps["map30"].clone().requires_grad_(True)
+    stages["masked_bce_prob_map30_hip"] = lambda: ops.adv_loss(x30, "bce_prob", mask=mask, real_label=1.0, want_grad=True)
+    stages["masked_bce_prob_map30_torch"] = lambda: torch.autograd.grad(
+        F.binary_cross_entropy(xa30, 1.0 - F.interpolate(mask, size=(30, 30), mode="bilinear", align_corners=False)), xa30)
+    stages["cw_margin_hip"] = lambda: ops.cw_margin(logits, target, True, 0.0, want_grad=True)
+
+    def torch_cw():
+        onehot = torch.eye(1000, device="cuda")[target]
+        real = (onehot * la).sum(1)
+        other = ((1 - onehot) * la - onehot * 10000).max(1)[0]
+        return torch.autograd.grad(torch.max(other - real, torch.zeros_like(other)).sum(), la)
+    stages["cw_margin_torch"] = torch_cw
+    for fn in stages.values():
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    iters = max(10, a.iters // 6)
+    times = {k: [] for k in stages}
+    for _ in range(iters):
+        for k, fn in stages.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) * 1e3)
+    out = {"shapes": {k: list(v.shape) for k, v in maps.items()}, "cw": list(logits.shape), "iters": iters,
+           "what": "loss + gradient wrt the input, device events, microseconds (median)"}
+    for k, v in times.items():
+        out[k + "_us"] = round(statistics.median(v), 2)
     return out
 
 

@@ -1,6 +1,14 @@
 """loss -- the reference's `ExclusionLoss(level=3)` and `GradientLoss()` (loss.py:309-360, 413-423) on the fused HIP kernels of
-csrc/imgloss.hip, differentiable under torch autograd for every input.  float32 [B,C,H,W] tensors on the GPU; no CPU path, no host sync,
-bit-reproducible (no atomics).
+csrc/imgloss.hip, and its `AdversarialLoss(type='nsgan')` (loss.py:41-88) on those of csrc/advloss.hip, differentiable under torch autograd
+for every input.  float32 tensors on the GPU; no CPU path, no host sync, bit-reproducible (no atomics).
+
+    AdversarialLoss(type)(outputs, is_real, is_disc=None, mask=None), the reference's branches:
+        hinge:  is_disc -> mean relu(1 - outputs) (is_real) or mean relu(1 + outputs);  otherwise (-outputs).mean(), whatever is_real says
+        nsgan:  nn.BCELoss()(outputs, labels) on probabilities;  lsgan: nn.MSELoss()(outputs, labels)
+                labels = real_label (is_real), fake_label (not is_real, no mask), or with a mask real_label * (1 - mask_down), mask_down the
+                mask resized to the outputs' H x W bilinearly (F.upsample: align_corners=False, no antialiasing).  The mask is read only when
+                not is_real, it is sampled inside the loss kernel (mask_down is never written), and NO gradient flows to it: the reference's
+                own mask is a data tensor.  is_disc is ignored outside hinge, as in the reference.
 
     GradientLoss()(a)                = mean |a[..., :-1] - a[..., 1:]| + mean |a[..., :-1, :] - a[..., 1:, :]|
     ExclusionLoss(level)(img1, img2) = (sum gradx terms + sum grady terms) / (level * 9) / 2, a term per level (the images 2 x 2
@@ -57,6 +65,73 @@ class _GradientFunction(torch.autograd.Function):
     def backward(ctx, gout):
         (x,) = ctx.saved_tensors
         return ops.gradient_loss_bwd(x, gout=gout.detach().to(torch.float32).contiguous().reshape(-1))
+
+
+class _AdvFunction(torch.autograd.Function):
+    """ops.adv_loss under autograd: the forward is the loss alone, the backward ONE launch of the same kernel with the gradient asked for"""
+    @staticmethod
+    def forward(ctx, x, objective, label, mask, real_label):
+        a = x.detach().contiguous()
+        ctx.args = (objective, label, mask, real_label)
+        ctx.save_for_backward(a)
+        return ops.adv_loss(a, objective, label, mask, real_label).reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        (a,) = ctx.saved_tensors
+        objective, label, mask, real_label = ctx.args
+        gout = gout.detach().to(torch.float32).contiguous().reshape(-1)
+        _, g = ops.adv_loss(a, objective, label, mask, real_label, want_grad=True, gout=gout)
+        return g, None, None, None, None
+
+
+def adv_objective(x, objective, label=None, mask=None, real_label=1.0):
+    """ops.adv_loss(x, objective, ...) as a differentiable scalar (the building block of AdversarialLoss and models.modules.loss.GANLoss)"""
+    need_cuda("adv_objective", x)
+    if x.dtype != torch.float32:
+        raise TypeError("adv_objective: float32 tensors expected")
+    if mask is not None:
+        need_cuda("adv_objective", mask)
+        mask = mask.detach().to(torch.float32).contiguous()
+    return _AdvFunction.apply(x, objective, label, mask, real_label)
+
+
+class AdversarialLoss(torch.nn.Module):
+    r"""
+    Adversarial loss
+    https://arxiv.org/abs/1711.10337
+    """
+
+    def __init__(self, type='nsgan', target_real_label=1.0, target_fake_label=0.0):
+        r"""
+        type = nsgan | lsgan | hinge
+        """
+        super().__init__()
+        if type not in ('nsgan', 'lsgan', 'hinge'):
+            # (the reference constructs such an object and fails at the first call, with no `criterion`)
+            raise ValueError("AdversarialLoss: type must be nsgan, lsgan or hinge, got %r" % (type,))
+        self.type = type
+        self.register_buffer('real_label', torch.tensor(target_real_label))
+        self.register_buffer('fake_label', torch.tensor(target_fake_label))
+        # the labels as host numbers: reading the buffers at call time would synchronise.  load_state_dict refreshes them
+        self._labels = (float(target_real_label), float(target_fake_label))
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        self._labels = (float(self.real_label), float(self.fake_label))
+
+    def __call__(self, outputs, is_real, is_disc=None, mask=None):
+        if self.type == 'hinge':
+            if is_disc:
+                return adv_objective(outputs, "hinge_disc", -1.0 if is_real else 1.0)
+            return adv_objective(outputs, "neg_mean")
+        objective = "bce_prob" if self.type == 'nsgan' else "mse"
+        real, fake = self._labels
+        if is_real:
+            return adv_objective(outputs, objective, real)
+        if mask is None:
+            return adv_objective(outputs, objective, fake)
+        return adv_objective(outputs, objective, None, mask, real)
 
 
 class ExclusionLoss(torch.nn.Module):

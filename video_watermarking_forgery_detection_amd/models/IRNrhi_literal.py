@@ -7,6 +7,8 @@ row 1's "literal IRNrhi step" -- on the HIP layer toolkit (glayers.py; csrc/gcon
     bayar_s, QF_s = localizer(simulated);  + 5 SmoothL1(bayar_s, bayar_ori);  CE(QF_s, label)                           :479-485
     (BCE(D(real_H), 1) + BCE(D(simulated.detach()), 0)) / 2 -> clip -> AdamW(discriminator)                             :488-501
     l_simul + 0.01 CE + 0.01 BCE(D(simulated), 1) -> clip -> AdamW(generator);  PSNR(simulated, real_H)                 :503-527
+With train.gan_type (nsgan | lsgan | hinge) the three adversarial terms are AdversarialLoss(type)(dis_real, True, True),
+(dis_fake, False, True) and (gen_fake, True, False) of loss.py (csrc/advloss.hip); absent, the step is the one above, call for call.
 
 What is not carried over: `self.netG` (a second FBCNN the reference constructs, :181, whose training lines are commented out, :465,
 :516-520), the DiffJPEG copies `self.diff_jpeg` that only feed the stitched image dump (:376-387,536-556), DistributedDataParallel
@@ -17,6 +19,7 @@ import torch
 
 from .. import glayers as G
 from .. import ops
+from ..loss import AdversarialLoss
 from .base_model import BaseModel
 from .conditional_jpeg_generator import FBCNN, QF_predictor
 from .networks import Discriminator
@@ -56,6 +59,14 @@ class IRNrhiLiteralModel(BaseModel):
         self.optimizer_discriminator = G.FlatAdamW(self.discriminator, lr_d, betas, weight_decay=wd)
         self.optimizer_localizer = G.FlatAdamW(self.localizer, lr_d, betas, weight_decay=wd)
         self.gradient_clipping = _get(train_opt, 'gradient_clipping', default=None)
+        # train.gan_type (nsgan | lsgan | hinge): the three adversarial terms go through the reference's AdversarialLoss(type=gan_type)
+        # (loss.py:41-88; IRNrhi_model.py:155 builds it with "nsgan").  Absent: the step's BCE terms as they were (glayers.bce_loss)
+        self.gan_type = _get(train_opt, 'gan_type')
+        self.adversarial_loss = None
+        if self.gan_type is not None:
+            if self.gan_type not in ('nsgan', 'lsgan', 'hinge'):
+                raise ValueError("train.gan_type must be nsgan, lsgan or hinge, got %r" % (self.gan_type,))
+            self.adversarial_loss = AdversarialLoss(type=self.gan_type).to(self.device)
         self.global_step = 0
         self.real_H = self.label = None
         self.last = {}
@@ -118,7 +129,11 @@ class IRNrhiLiteralModel(BaseModel):
         # ---- discriminator (:488-501)
         dis_real = self.discriminator(real_H)
         dis_fake = self.discriminator(simulated_jpeg.detach())
-        dis_loss = (G.bce_loss(dis_real, 1.0) + G.bce_loss(dis_fake, 0.0)) / 2
+        adv = self.adversarial_loss
+        if adv is None:
+            dis_loss = (G.bce_loss(dis_real, 1.0) + G.bce_loss(dis_fake, 0.0)) / 2
+        else:
+            dis_loss = (adv(dis_real, True, True) + adv(dis_fake, False, True)) / 2
         self.optimizer_discriminator.zero_grad()
         dis_loss.backward()
         self._clip(self.optimizer_discriminator)
@@ -127,7 +142,7 @@ class IRNrhiLiteralModel(BaseModel):
 
         # ---- generator: fidelity + quality classification + adversarial (:503-525)
         gen_fake = self.discriminator(simulated_jpeg)
-        FW_GAN = G.bce_loss(gen_fake, 1.0)
+        FW_GAN = G.bce_loss(gen_fake, 1.0) if adv is None else adv(gen_fake, True, False)
         l_simul_sum = l_simul_l1 + l_QF_simul * 0.01 + FW_GAN * 0.01
         l_simul_sum.backward()
         self._clip(self.optimizer_generator)
@@ -140,6 +155,8 @@ class IRNrhiLiteralModel(BaseModel):
         names = ['l_simul_bayar', 'FW_GAN', 'lQF', 'PSSIMU', 'qfsimu']                           # :482,506,529-532, in the order appended
         logs = list(zip(names, vals[:5]))
         self.last = {"dis_loss": vals[5], "l_simul_sum": vals[6], "simulated": simulated_jpeg.detach()}
+        if adv is not None:      # the discriminator outputs the adversarial terms were taken on
+            self.last.update(dis_real=dis_real.detach(), dis_fake=dis_fake.detach(), gen_fake=gen_fake.detach())
         return logs, []
 
     # ------------------------------------------------------------------ checkpoints (base_model.py:77-115)

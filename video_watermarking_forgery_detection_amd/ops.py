@@ -2087,6 +2087,103 @@ def exclusion_bwd(img1, img2, coef, level=3, want=(True, True), gout=None, gscal
     return g[0], g[1]
 
 
+# ----------------------------------------------------------------------------- GAN objectives (csrc/advloss.hip)
+ADV_OBJECTIVES = {"bce_prob": 0, "bce_logits": 1, "mse": 2, "hinge_disc": 3, "neg_mean": 4, "pos_mean": 5}    # WM_ADV_*
+_ADV_LABELLED = ("bce_prob", "bce_logits", "mse")
+
+
+def _adv_args(name, x, objective, label, mask):
+    if objective not in ADV_OBJECTIVES:
+        raise ValueError("%s: objective must be one of %s, got %r" % (name, ", ".join(ADV_OBJECTIVES), objective))
+    _f32_cuda(name, x, mask)
+    if x.numel() == 0:
+        raise ValueError(name + ": a non-empty tensor expected")
+    dims = (0,) * 7
+    if objective == "hinge_disc":
+        if mask is not None or label is None or float(label) not in (-1.0, 1.0):
+            raise ValueError(name + ": hinge_disc takes the sign of relu(1 + s x) as label: -1 (real) or +1 (fake), and no mask")
+    elif objective not in _ADV_LABELLED:
+        if label is not None or mask is not None:
+            raise ValueError(name + ": %s takes neither a label nor a mask" % objective)
+    elif mask is not None:
+        if label is not None:
+            raise ValueError(name + ": a scalar label or a mask, not both (the masked labels are real_label * (1 - mask))")
+        if x.dim() != 4 or mask.dim() != 4 or mask.shape[0] != x.shape[0] or mask.shape[1] not in (1, x.shape[1]) or mask.numel() == 0:
+            raise ValueError(name + ": masked labels need x [B,C,H,W] and mask [B,1,Hm,Wm] or [B,C,Hm,Wm]")
+        dims = tuple(x.shape) + tuple(mask.shape[1:])
+    elif label is None:
+        raise ValueError(name + ": %s needs a scalar label or a mask" % objective)
+    return ADV_OBJECTIVES[objective], 0.0 if label is None else float(label), dims
+
+
+def adv_loss(x, objective, label=None, mask=None, real_label=1.0, want_grad=False, gscale=1.0, gscale_dev=None, grad_out=None, gout=None):
+    """one GAN objective as a mean over every element of x (any shape) -> a [1] device tensor, or with want_grad (loss, grad) with loss
+    UNSCALED and grad = gscale * gscale_dev[0] * gout[0] * d loss / dx, both from the SAME streaming launch (two launches in all, no host
+    sync).  grad_out: an existing gradient buffer the result is ADDED into (and returned).  objective:
+        bce_prob    nn.BCELoss()(x, t) on probabilities (AdversarialLoss nsgan): logs clamped at -100, backward over max(x (1 - x), 1e-12)
+        bce_logits  nn.BCEWithLogitsLoss()(x, t) (GANLoss gan / ragan), any label value
+        mse         (x - t)^2 (lsgan)
+        hinge_disc  relu(1 + s x), s = label = -1 (real) or +1 (fake); the subgradient at 0 is 0
+        neg_mean / pos_mean   -+mean(x) (the hinge generator term, wgan-gp); no label
+    t is the scalar `label`, or with mask ([B,1,Hm,Wm] or [B,C,Hm,Wm], x [B,C,H,W]) the masked labels real_label * (1 - mask_down), mask_down
+    the mask resized to x's H x W bilinearly (align_corners=False, no antialiasing) -- sampled inside the loss kernel, never written.  No
+    gradient flows to the mask: it is data"""
+    obj, lab, dims = _adv_args("adv_loss", x, objective, label, mask)
+    L = _lib.lib()
+    n = x.numel()
+    part = torch.empty(L.wm_advloss_nparts(n), device=x.device, dtype=torch.float64)
+    loss = torch.empty(1, device=x.device, dtype=torch.float32)
+    grad = None
+    if want_grad:
+        gout, grad = _loss_bwd_args("adv_loss", x, gout, gscale_dev, grad_out, grad_out is not None)
+    elif grad_out is not None or gout is not None:
+        raise ValueError("adv_loss: grad_out / gout need want_grad=True")
+    rc = _timed("advloss_elem", None, lambda: L.wm_advloss_elem(obj, _p(x), n, lab, _p(mask), *dims, float(real_label), _p(part), _p(grad), _p(gout),
+                                                                float(gscale), _p(gscale_dev), 1 if grad_out is not None else 0, _stream()))
+    _lib.check(rc, "wm_advloss_elem")
+    rc = L.wm_advloss_finalize(_p(part), n, _p(loss), _stream())
+    _lib.check(rc, "wm_advloss_finalize")
+    if not want_grad:
+        return loss
+    _wrote(grad)
+    return loss, grad
+
+
+def cw_margin(logits, target, is_targeted, kappa=0.0, want_grad=False, gscale=1.0, gscale_dev=None, grad_out=None, gout=None, check_target=False):
+    """CWLoss()(logits, target, is_targeted, K, kappa): sum over the rows of max(other - real, kappa) (targeted) or max(real - other, kappa),
+    real = logits[b, target_b], other = the largest of the row with the target's slot replaced by -10000 -> a [1] device tensor, or with
+    want_grad (loss, grad [B,K]) as adv_loss.  Two launches, no host sync.  logits [B,K] float32, K >= 2; target [B] int64.
+    A target outside [0, K) is checked ON THE DEVICE: it is never used as an index, and it turns the loss and that row of the gradient into
+    NaN.  check_target=True validates on the host first (one synchronisation, so not inside a captured step) and raises ValueError"""
+    _f32_cuda("cw_margin", logits)
+    _need_cuda(target)
+    if logits.dim() != 2 or logits.shape[0] == 0:
+        raise ValueError("cw_margin: logits [B,K] expected")
+    B, K = logits.shape
+    if K < 2:
+        raise ValueError("cw_margin: K >= 2 classes expected (with one class there is no other logit)")
+    if target.dtype != torch.int64 or not target.is_contiguous() or target.shape != (B,):
+        raise TypeError("cw_margin: target must be a contiguous int64 tensor [B]")
+    if check_target and bool(((target < 0) | (target >= K)).any()):
+        raise ValueError("cw_margin: target outside [0, %d)" % K)
+    L = _lib.lib()
+    terms = torch.empty(B, device=logits.device, dtype=torch.float64)
+    loss = torch.empty(1, device=logits.device, dtype=torch.float32)
+    grad = None
+    if want_grad:
+        gout, grad = _loss_bwd_args("cw_margin", logits, gout, gscale_dev, grad_out, grad_out is not None)
+    elif grad_out is not None or gout is not None:
+        raise ValueError("cw_margin: grad_out / gout need want_grad=True")
+    rc = _timed("cw_margin", None, lambda: L.wm_cw_margin(_p(logits), _p(target), B, K, 1 if is_targeted else 0, float(kappa), _p(terms), _p(loss),
+                                                          _p(grad), _p(gout), float(gscale), _p(gscale_dev), 1 if grad_out is not None else 0,
+                                                          _stream()))
+    _lib.check(rc, "wm_cw_margin")
+    if not want_grad:
+        return loss
+    _wrote(grad)
+    return loss, grad
+
+
 # ----------------------------------------------------------------------------- device RNG and the stochastic / JPEG-Drop attacks (csrc/noise.hip,
 # csrc/jpeg_drop.hip).  `state` is a layer's int64[RNG_STATE_WORDS] device tensor {seed, offset, ...}; a forward returns, beside its output,
 # rec = int64[2] {seed, offset} of the call, from which the backward regenerates the same draws
