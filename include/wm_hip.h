@@ -842,6 +842,20 @@ int wm_advloss_finalize(const double* partials, size_t n, float* loss_out, void*
 int wm_cw_margin(const float* logits, const long long* target, int B, int K, int is_targeted, float kappa, double* terms, float* loss_out,
                  float* grad, const float* gout_dev, float gscale, const float* gscale_dev, int accumulate, void* stream);
 
+/* ------------------------------------------------------------------ hybrid per-frame attack mix (csrc/hybrid.hip)
+ * The "HYBRID ATTACKS" block of the reference's video model (models/IRNcrop_model.py:347-373): alpha = softmax(randn(B, T, K), dim = 2), the
+ * localiser's input = sum_k alpha[..., k] * attacked_k per frame, then clamp_with_grad + Quantization (:372-373).  (The reference's loop body
+ * :369 adds the bare weights and never multiplies them in; this is the mix it means.)  f32 contiguous tensors [N][frame], N = B*T frames, any
+ * frame >= 1 (not only multiples of 4); w [N][K] f32 on the device, used as given (not required to sum to 1); 1 <= K <= 8.
+ * wm_mix_fwd: xs_host = HOST array of K device pointers, passed to the kernel by value.  acc = 0; for k = 0..K-1: acc = fma(w[n][k], x_k[i], acc),
+ *   in that order; quant 0: y = acc; quant 1: y = exactly wm_clamp_quant_fwd of acc (the same device function).  One launch, (K+1) * 4 bytes
+ *   per element.  K outside 1..8, a null pointer, N <= 0 or frame == 0: WM_E_BADARG and nothing is launched.
+ * wm_mix_bwd: gxs_host = HOST array of K device pointers; gx_k[i] = w[n][k] * g[i]; a NULL entry = that input needs no gradient: nothing is
+ *   stored for it (all NULL: WM_OK, nothing is launched).  The clamp and the quantisation are identities backwards, so there is no quant here.
+ * 16-byte accesses when every tensor pointer is 16-byte aligned, 4-byte accesses otherwise. */
+int wm_mix_fwd(const float* const* xs_host, int K, const float* w, float* y, int N, size_t frame, int quant, void* stream);
+int wm_mix_bwd(const float* g, const float* w, float* const* gxs_host, int K, int N, size_t frame, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -10,11 +10,7 @@
 
 namespace {
 
-__device__ __forceinline__ float clamp_quant(float v) {
-    // torch.clamp(x,0,1) then (x*255).round()/255 -- rintf = round half to even like torch.round, true f32 division
-    const float c = fminf(fmaxf(v, 0.f), 1.f);
-    return rintf(c * 255.f) / 255.f;
-}
+__device__ __forceinline__ float clamp_quant(float v) { return wm_clamp_quant(v); }   // (shared with csrc/hybrid.hip: wm_common.h)
 
 inline int grid_for(size_t n, int cap = 2048) {
     const size_t g = (n + 255) / 256;

@@ -43,6 +43,14 @@ void wm_set_error(const char* fmt, ...);
 
 static inline int wm_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// ---- clamp_with_grad + Quantization of the localisation branch (IRNcrop_model.py:320-322,344-345,372-373; models/modules/Quantization.py:7-14):
+// torch.clamp(x,0,1) then (x*255).round()/255 -- rintf = round half to even like torch.round, true f32 division.  The one definition behind
+// wm_clamp_quant_fwd, wm_splice_fwd (localise.hip) and wm_mix_fwd's quant = 1 (hybrid.hip), so the three agree bit for bit.
+__device__ __forceinline__ float wm_clamp_quant(float v) {
+    const float c = fminf(fmaxf(v, 0.f), 1.f);
+    return rintf(c * 255.f) / 255.f;
+}
+
 // ---- BatchNorm+ReLU backward apply, folded (bf16 path).  With g one value per (sample, channel) -- a globally pooled layer:
 //   dy = ca*(g*[z>0] - c1 - (y-mean)*invstd*c2),  z = scale*y + shift
 //      = (z > 0 ? k3 + ca*g : k3) - k2*y,         k2 = ca*invstd*c2,  k3 = k2*mean - ca*c1

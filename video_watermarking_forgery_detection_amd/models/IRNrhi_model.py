@@ -28,7 +28,7 @@ from .. import engine, ops
 from ..hidden_models import Hidden
 from ..hidden_models.hidden import _FlatAdam
 from ..network.UNet import UNet
-from ..noise_layers import Combined, Crop, GaussianBlur, Identity, Jpeg, JpegMask, JpegSS, MiddleBlur, Resize
+from ..noise_layers import Combined, Crop, GaussianBlur, Hybrid, Identity, Jpeg, JpegMask, JpegSS, MiddleBlur, Resize
 from ..noise_layers._device_rng import call_fwd
 from ..noise_layers.dropout import Dropout
 from ..noise_layers.gaussian import Gaussian
@@ -171,6 +171,15 @@ class IRNrhiModel(BaseModel):
             q = "".join(ch for ch in a if ch.isdigit())
             layers.append(table[kind](int(q) if q else None))
         self.attack = _AttackCycle(layers)
+        # train.hybrid_attacks (default false): the localiser sees, per frame, a random convex mix of EVERY layer of the cycle but Crop, clamped and
+        # quantised in the same launch (the reference's "HYBRID ATTACKS" block, IRNcrop_model.py:347-373), instead of the step's one layer; the
+        # embed -> attack -> extract chain keeps cycling one attack per step
+        self.hybrid = None
+        if bool(_get(train_opt, 'hybrid_attacks', default=False)):
+            usable = [l for l in layers if not isinstance(l, Crop)]
+            if not usable:
+                raise ValueError("train.hybrid_attacks needs at least one attack other than Crop in train.attacks")
+            self.hybrid = Hybrid(usable, quantize=True)
         self.Quantization = Quantization()
 
         # ---- networks: HiDDeN embedder / extractor / discriminator (+ UNet localiser)
@@ -305,8 +314,11 @@ class IRNrhiModel(BaseModel):
             self._gate(encoded, images)
         (tampered, mask), self._loc = self._loc, None
         kind = self.attack.name                                     # the step's attack (set by the embed -> attack -> extract pass)
-        attacked, cA = self.attack.fwd(tampered, exclude=(Crop,), cover=images)   # the reference's localiser sees no geometric attack (:362-366)
-        attacked_q = ops.clamp_quant(attacked)                      # clamp_with_grad + Quantization (:372-373)
+        if self.hybrid is not None:
+            attacked_q, cA = self.hybrid.fwd(tampered, cover=images)    # every layer, mixed per frame, clamped and quantised (:347-373)
+        else:
+            attacked, cA = self.attack.fwd(tampered, exclude=(Crop,), cover=images)   # the reference's localiser sees no geometric attack (:362-366)
+            attacked_q = ops.clamp_quant(attacked)                  # clamp_with_grad + Quantization (:372-373)
         if self.keep_outputs:
             self.last_outputs.update(tampered=tampered, attacked=attacked_q)
         net.refresh_packs()   # all conv weights of the localiser packed in one launch, valid until its optimiser step
@@ -337,9 +349,10 @@ class IRNrhiModel(BaseModel):
                 gscale = 1.0
         self._clip([net.flat_grads])
         self.optimizer_localizer.step(grad_scale=gscale)
-        g_tamp = self.attack.bwd(cA, g_att)
+        g_tamp = self.hybrid.bwd(cA, g_att) if self.hybrid is not None else self.attack.bwd(cA, g_att)
         ops.masked_axpy_(g_enc, g_tamp.contiguous(), mask)
-        return [('lB', loss), ('CE', loss)] + ([('Dice', dice)] if dice is not None else []) + [('Kind', kind), ('LocKind', self.attack.name)]
+        loc_kind = self.hybrid.name if self.hybrid is not None else self.attack.name
+        return [('lB', loss), ('CE', loss)] + ([('Dice', dice)] if dice is not None else []) + [('Kind', kind), ('LocKind', loc_kind)]
 
     def _clip(self, flats):
         if self.gradient_clipping:

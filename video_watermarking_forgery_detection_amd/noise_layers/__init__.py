@@ -1,6 +1,7 @@
 """Differentiable attack layers on the MI355X kernels -- mirror of the reference's noise_layers/
 package: the layers the models instantiate and the stochastic / JPEG-Drop attacks the
-reference's trainers construct and its __init__ exports (Dropout = crop.py's, GN, SaltPepper)."""
+reference's trainers construct and its __init__ exports (Dropout = crop.py's, GN, SaltPepper); Hybrid is the per-frame mix of several
+of them that the reference's video model feeds its localiser (models/IRNcrop_model.py:347-373)."""
 import random
 
 
@@ -24,3 +25,4 @@ from .salt_pepper_noise import SaltPepper  # noqa: E402
 from .gaussian import Gaussian  # noqa: E402
 from .jpeg_compression import JpegCompression  # noqa: E402
 from .noiser import Noiser  # noqa: E402
+from .hybrid import Hybrid  # noqa: E402

@@ -967,6 +967,63 @@ def clamp_quant(x):
     return y
 
 
+MIX_MAX_K = 8
+
+
+def _mix_args(name, ts, w, K):
+    """the checks shared by mix_fwd / mix_bwd: `ts` f32 tensors [N, ...] of one shape, w [N, K] f32, 1 <= K <= 8 (ValueError), all on the GPU
+    (RuntimeError: there is no CPU path) -> (contiguous ts, contiguous w, N, frame)"""
+    if not 1 <= K <= MIX_MAX_K:
+        raise ValueError(f"{name}: K = {K} inputs (1..{MIX_MAX_K})")
+    t0 = ts[0]
+    if t0.dim() < 1 or t0.numel() == 0:
+        raise ValueError(f"{name}: tensors must be [N, ...] and not empty, got {tuple(t0.shape)}")
+    for t in ts:
+        if t.shape != t0.shape:
+            raise ValueError(f"{name}: tensors of different shapes {tuple(t.shape)} and {tuple(t0.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: float32 tensors only, got {t.dtype}")
+    N = t0.shape[0]
+    if tuple(w.shape) != (N, K) or w.dtype != torch.float32:
+        raise ValueError(f"{name}: weights must be float32 [{N}, {K}], got {w.dtype} {tuple(w.shape)}")
+    for t in list(ts) + [w]:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on the HIP path only: move the tensors to cuda")
+    return [t.contiguous() for t in ts], w.contiguous(), N, t0.numel() // N
+
+
+def mix_fwd(xs, w, quant=False):
+    """y[n] = sum_k w[n, k] * xs[k][n] per frame n, accumulated with fma in the order k = 0..K-1 from 0 (IRNcrop_model.py:347-371, the hybrid
+    attack mix); quant: then clamp_quant, in the same launch.  xs: 1..8 f32 tensors [N, ...] of one shape; w [N, K] f32, used as given."""
+    xs = list(xs)
+    xs, w, N, frame = _mix_args("mix_fwd", xs, w, len(xs))
+    y = torch.empty_like(xs[0])
+    ptrs = (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+    rc = _lib.lib().wm_mix_fwd(ptrs, len(xs), _p(w), _p(y), N, frame, 1 if quant else 0, _stream())
+    _lib.check(rc, "wm_mix_fwd")
+    return y
+
+
+def mix_bwd(g, w, K, needs=None, out=None):
+    """the mix's backward in one launch: [w[:, k] * g per frame for k < K], None where needs[k] is false (that input's gradient is not
+    stored).  out: K tensors like g to write into instead of fresh ones (a slot whose needs[k] is false is left untouched)."""
+    needs = [True] * K if needs is None else [bool(v) for v in needs]
+    if len(needs) != K or (out is not None and len(out) != K):
+        raise ValueError(f"mix_bwd: needs / out must have K = {K} entries")
+    outs_in = [o for o, nd in zip(out, needs) if nd] if out is not None else []
+    for o in outs_in:
+        if not o.is_contiguous():
+            raise ValueError("mix_bwd: out tensors must be contiguous")
+    ts, w, N, frame = _mix_args("mix_bwd", [g] + outs_in, w, K)
+    g = ts[0]
+    gxs = [(out[k] if out is not None else torch.empty_like(g)) if needs[k] else None for k in range(K)]
+    ptrs = (ctypes.c_void_p * K)(*[_p(t) for t in gxs])
+    rc = _lib.lib().wm_mix_bwd(_p(g), _p(w), ptrs, K, N, frame, _stream())
+    _lib.check(rc, "wm_mix_bwd")
+    _wrote(*outs_in)
+    return gxs
+
+
 def splice_fwd(enc, real=None, prev=None, mask=None, want_fwd=False):
     """q = clamp_quant(enc); tampered = q*(1-mask) + prev*mask (IRNcrop_model.py:344-348); with `real`, also the partial sums of
     the squared difference of the int-truncated images for the PSNR.  Returns (fwd_q or None, tampered or None, psnr partials or None)."""
