@@ -53,26 +53,33 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ y, 
 #pragma unroll
                 for (int co = 0; co < COUT; ++co) part[co] += __shfl_xor(part[co], o, 64);
             }
-            if (valid[u] && vv < COUT) {
-                float v = 0.f;
+            if (valid[u]) {   // lane vv of the pixel's group writes output channel vv (a group of fewer lanes than COUT walks the rest too)
+                for (int oc = vv; oc < COUT; oc += VPP) {
+                    float v = 0.f;
 #pragma unroll
-                for (int co = 0; co < COUT; ++co) v = (vv == co) ? part[co] + bias[co] : v;
-                if (act == 1) v = 1.f / (1.f + __expf(-v));
-                const size_t b = p / hw, q = p - b * hw;
-                out[(b * COUT + vv) * hw + q] = v;
+                    for (int co = 0; co < COUT; ++co) v = (oc == co) ? part[co] + bias[co] : v;
+                    if (act == 1) v = 1.f / (1.f + __expf(-v));
+                    const size_t b = p / hw, q = p - b * hw;
+                    out[(b * COUT + oc) * hw + q] = v;
+                }
             }
             // act16 (round 4): the same pixel once more as the 16-channel NHWC pixel the image-fed first layers read (channels 0..COUT-1,
             // zero tail) -- what wm_nchw_to_nhwc would make of `out` in a launch of its own; every lane of the pixel's group holds all sums
-            if (act16 && valid[u] && vv < 16 / VE) {   // lane vv of the pixel's group writes the pixel's vv-th 16-byte piece: one store
-                vec16<T> o;                            // instruction covers the wave's 8 adjacent pixels (256 contiguous bytes at 16 bits)
+            // lane vv of the pixel's group writes the pixel's vv-th 16-byte piece: one store instruction covers the wave's 8 adjacent
+            // pixels (256 contiguous bytes at 16 bits).  A group of fewer lanes than pieces (Cin = 8 at 16 bits, Cin <= 12 in f32) walks
+            // the remaining pieces too, so the zero tail is always written
+            if (act16 && valid[u]) {
+                for (int pc = vv; pc < 16 / VE; pc += VPP) {
+                    vec16<T> o;
 #pragma unroll
-                for (int e = 0; e < VE; ++e) {
-                    float val = 0.f;
+                    for (int e = 0; e < VE; ++e) {
+                        float val = 0.f;
 #pragma unroll
-                    for (int co = 0; co < COUT; ++co) val = (vv * VE + e == co) ? part[co] + bias[co] : val;
-                    o.set(e, val);
+                        for (int co = 0; co < COUT; ++co) val = (pc * VE + e == co) ? part[co] + bias[co] : val;
+                        o.set(e, val);
+                    }
+                    *reinterpret_cast<vec16<T>*>(act16 + p * 16 + pc * VE) = o;
                 }
-                *reinterpret_cast<vec16<T>*>(act16 + p * 16 + vv * VE) = o;
             }
         }
     }
