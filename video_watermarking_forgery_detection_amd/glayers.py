@@ -720,7 +720,33 @@ class FlatAdamW:
                 p.grad = self.grad[o:o + k].view(p.shape)
                 _FLAT_GRADS[p.data_ptr()] = (weakref.ref(self.flat), weakref.ref(self.grad), o, k)
                 o += k
-        self.lr, self.betas, self.eps, self.weight_decay, self.t = lr, betas, eps, weight_decay, 0
+        # one param group, torch's keys: what BaseModel's learning-rate handling and the schedulers (models/lr_scheduler.py) read and write
+        self.param_groups = [{"lr": lr, "initial_lr": lr, "betas": betas, "eps": eps, "weight_decay": weight_decay}]
+        self.t = 0
+
+    lr = property(lambda self: self.param_groups[0]["lr"], lambda self, x: self.param_groups[0].__setitem__("lr", x))
+    betas = property(lambda self: self.param_groups[0]["betas"], lambda self, x: self.param_groups[0].__setitem__("betas", x))
+    eps = property(lambda self: self.param_groups[0]["eps"], lambda self, x: self.param_groups[0].__setitem__("eps", x))
+    weight_decay = property(lambda self: self.param_groups[0]["weight_decay"], lambda self, x: self.param_groups[0].__setitem__("weight_decay", x))
+
+    def reset_state(self):
+        """AdamW from the start again (zero moments, step 0): a scheduler's restart with clear_state.  Two memsets in stream order."""
+        self.m.zero_()
+        self.v.zero_()
+        self.t = 0
+
+    def state_dict(self):
+        """the training state BaseModel.save_training_state stores: step count, the param group, the two flat moment buffers (on the CPU)"""
+        return {"step": self.t, "param_groups": [dict(self.param_groups[0])], "exp_avg": self.m.detach().cpu().clone(),
+                "exp_avg_sq": self.v.detach().cpu().clone()}
+
+    def load_state_dict(self, sd):
+        if sd["exp_avg"].numel() != self.m.numel():
+            raise ValueError(f"optimizer state holds {sd['exp_avg'].numel()} values, the module has {self.m.numel()}")
+        self.t = int(sd["step"])
+        self.param_groups[0].update(sd["param_groups"][0])
+        self.m.copy_(sd["exp_avg"])
+        self.v.copy_(sd["exp_avg_sq"])
 
     def zero_grad(self):
         self.grad.zero_()

@@ -124,6 +124,19 @@ class _FlatAdam:
             ops.adam_step(mod.flat_params, mod.flat_grads, m, v, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
                           g["weight_decay"], self.step_count, decoupled=self.decoupled, grad_scale=grad_scale)
 
+    def reset_state(self):
+        """Adam from the start again: zero moments, step 0 -- what the reference's schedulers do to a torch optimiser at a restart with
+        clear_state (lr_scheduler.py:22-23: `optimizer.state = defaultdict(dict)`).  Memsets on the current stream in the existing buffers,
+        no host synchronisation; a captured step needs no recapture (it reads the moments through the same pointers and takes its
+        bias corrections from the host's step count at each replay, _StepGraph._hyper_refresh -- under a scaler from the scaler's device-side
+        count, zeroed here too)."""
+        if self._m is not None:
+            for t in self._m + self._v:
+                t.zero_()
+        self.step_count = 0
+        if getattr(self, "amp", None) is not None:
+            self.amp.state[12 + self.amp_slot:13 + self.amp_slot].zero_()
+
     def hyper(self, step):
         """the current param group and the constants adam_step derives from the step count (host arithmetic): what a captured step's
         replay needs in hyper_dev"""

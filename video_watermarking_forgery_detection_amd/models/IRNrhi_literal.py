@@ -22,6 +22,7 @@ from .. import ops
 from ..loss import AdversarialLoss
 from .base_model import BaseModel
 from .conditional_jpeg_generator import FBCNN, QF_predictor
+from .lr_scheduler import build_schedulers
 from .networks import Discriminator
 
 
@@ -58,6 +59,10 @@ class IRNrhiLiteralModel(BaseModel):
         self.optimizer_generator = G.FlatAdamW(self.generator, lr_d, betas, weight_decay=wd)
         self.optimizer_discriminator = G.FlatAdamW(self.discriminator, lr_d, betas, weight_decay=wd)
         self.optimizer_localizer = G.FlatAdamW(self.localizer, lr_d, betas, weight_decay=wd)
+        self.optimizers = [self.optimizer_generator, self.optimizer_discriminator, self.optimizer_localizer]   # :286,325,338, in that order
+        # :340-356 -- train.lr_scheme (MultiStepLR | CosineAnnealingLR_Restart; absent: none): one scheduler per optimiser, stepped by
+        # update_learning_rate(step, warmup_iter) before each optimize_parameters
+        self.schedulers = build_schedulers(self.optimizers, train_opt)
         self.gradient_clipping = _get(train_opt, 'gradient_clipping', default=None)
         # train.gan_type (nsgan | lsgan | hinge): the three adversarial terms go through the reference's AdversarialLoss(type=gan_type)
         # (loss.py:41-88; IRNrhi_model.py:155 builds it with "nsgan").  Absent: the step's BCE terms as they were (glayers.bce_loss)

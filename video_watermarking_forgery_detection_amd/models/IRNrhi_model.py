@@ -36,6 +36,7 @@ from ..noise_layers.jpeg_compression import JpegCompression
 from ..noise_layers.salt_pepper_noise import SaltPepper
 from ..options import HiDDenConfiguration
 from .base_model import BaseModel
+from .lr_scheduler import build_schedulers
 from .modules.Quantization import Quantization
 
 
@@ -229,6 +230,11 @@ class IRNrhiModel(BaseModel):
             # train.dice_weight (default 0 = off): w * BinaryDiceLoss()(pred, mask) next to the BCE term (the reference's dice_loss.py, the
             # mask-head loss of its tianchi_model.py:48,101); its gradient is added into the BCE gradient by the Dice backward itself; logged as Dice
             self.dice_weight = float(_get(train_opt, 'dice_weight', default=0.0) or 0.0)
+        # train.lr_scheme (MultiStepLR | CosineAnnealingLR_Restart, the reference's keys: lr_steps, lr_gamma, restarts, restart_weights,
+        # clear_state, T_period, eta_min; IRNrhi_model.py:340-356): one scheduler per optimiser, stepped by update_learning_rate(step,
+        # warmup_iter) before each optimize_parameters (train.py).  Absent: no scheduler, lr_G throughout.  A replayed step follows: it reads
+        # the param group at every replay, and a clear_state restart zeroes the moments in place (_FlatAdam.reset_state)
+        self.schedulers = build_schedulers(self.optimizers, train_opt)
         self.psnr_gate = bool(_get(train_opt, 'psnr_gate', default=True))   # IRNcrop_model.py:379-388
         # log side (IRNcrop_model.py:78,399-400: SummaryWriter scalars; :421-437: an image sheet every 500 steps at step % 500 == 10)
         tb_dir = _get(train_opt, 'tensorboard_dir', default=None)

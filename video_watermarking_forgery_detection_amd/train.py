@@ -89,6 +89,10 @@ def main():
         current_step += 1
         if current_step > total_iters:
             break
+        # the step's learning rate: every scheduler one step on (train.lr_scheme), then the linear warm-up over the first warmup_iter steps
+        if args.val == 0.0:
+            warmup_iter = opt['train']['warmup_iter']
+            model.update_learning_rate(current_step, warmup_iter=-1 if warmup_iter is None else warmup_iter)
         model.feed_data(train_data)
         if args.val == 0.0:
             logs, debug_logs = model.optimize_parameters(current_step, latest_values)
