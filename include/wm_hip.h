@@ -806,6 +806,43 @@ int wm_excl_finalize(const double* partials, int B, int C1, int C2, int H, int W
 int wm_excl_bwd(const float* img1, const float* img2, const double* coef, float* grad1, float* grad2, int B, int C1, int C2, int H, int W,
                 int levels, const float* gout_dev, float gscale, const float* gscale_dev, int accumulate, void* stream);
 
+/* ------------------------------------------------------------------ local structure loss, mask and gray losses (csrc/ssim3.hip)
+ * replaces loss.py:9-39 = models/modules/loss.py:44-74 (SSIM_Loss: a per-pixel MAP), loss.py:363-376 (ExtendedL1Loss), :379-388
+ * (NonBlurryLoss), :403-410 (GrayLoss) and the autograd backward of each.  f32 contiguous tensors; no atomics, no host synchronisation: double
+ * partials per workgroup and a fixed-order one-workgroup finalise, bitwise reproducible.  In every backward the scalar weight is
+ * s = gscale * gscale_dev[0] (device, may be NULL) * gout_dev[0] (device, may be NULL = 1) and accumulate != 0 adds into the gradient buffers.
+ * wm_ssim3_fwd: x, y = N = B*C planes [H, W], H, W >= 2, N <= 65535 (WM_E_BADARG otherwise: ReflectionPad2d(1) needs two pixels).  Both are
+ *   padded by 1 with reflection (index -1 -> 1, H -> H-2); nine-tap means mu_x, mu_y, E[x^2], E[y^2], E[xy] (row by row, / 9);
+ *   n = (2 mu_x mu_y + C1)(2 (E[xy] - mu_x mu_y) + C2), d = (mu_x^2 + mu_y^2 + C1)(E[x^2] - mu_x^2 + E[y^2] - mu_y^2 + C2), C1 = 0.01^2,
+ *   C2 = 0.03^2; out_map (may be NULL) [N,H,W] = clamp((1 - n/d) / 2, 0, 1); partials (may be NULL) [wm_ssim3_nparts(N,H,W)] doubles = the
+ *   sum of the map over each 16 x 64 tile.  One launch: 8 B read, 4 B written per element.  x == y gives exactly 0.
+ * wm_ssim3_finalize: loss_out[0] = sum of the partials / (N H W) = mean(map).
+ * wm_ssim3_bwd: gather form, one launch; gx / gy (either may be NULL) (+)= d/dx, d/dy of sum(g * map) * s with g [N,H,W] the upstream map, or
+ *   with g == NULL of mean(map) * s (every pixel's weight is (float)s * (1.f / (float)(N H W)): a g filled with that value gives the same
+ *   bits).  The clamp passes the gradient where 0 <= (1 - n/d)/2 <= 1, bounds included, as torch.clamp; the reflection's adjoint is exact (a
+ *   border pixel is counted once per tap that maps to it, also at H = 2 or W = 2).
+ * wm_pixloss_sums: a (and with WM_PIXLOSS_MASKL1 b, mask) [n] (any n and alignment: 16-byte access with a scalar head and tail) ->
+ *   partials [wm_pixloss_nparts(n) * 2] doubles: MASKL1 {sum |mask*a - mask*b|, sum |mask|} (the products exact in double, the difference rounded
+ *   once), NONBLURRY {sum (a - 1/2)^2, 0}, GRAY {sum |a - 1/2|, 0}; b and mask are ignored for the last two.
+ * wm_pixloss_finalize: coef [2] doubles = the two sums / n (what the backward reads); loss_out[0] = coef0 / coef1 (MASKL1; a zero mask gives
+ *   0/0 = NaN as the reference, unguarded), 1 - coef0 (NONBLURRY), 1 / coef0 (GRAY).
+ * wm_pixloss_bwd: MASKL1: ga / gb (either may be NULL) (+)= +- s sign(mask*a - mask*b) mask / (n coef1), sign(0) = 0 as torch's L1Loss; no
+ *   gradient goes to the mask.  NONBLURRY: ga (+)= -2 s (a - 1/2) / n.  GRAY: ga (+)= -s sign(a - 1/2) / (n coef0^2).  gb must be NULL for
+ *   the last two. */
+#define WM_PIXLOSS_MASKL1 0
+#define WM_PIXLOSS_NONBLURRY 1
+#define WM_PIXLOSS_GRAY 2
+int wm_ssim3_nparts(int N, int H, int W);
+int wm_ssim3_fwd(const float* x, const float* y, float* out_map, double* partials, int N, int H, int W, void* stream);
+int wm_ssim3_finalize(const double* partials, int N, int H, int W, float* loss_out, void* stream);
+int wm_ssim3_bwd(const float* x, const float* y, const float* g, float* gx, float* gy, int N, int H, int W, const float* gout_dev,
+                 float gscale, const float* gscale_dev, int accumulate, void* stream);
+int wm_pixloss_nparts(size_t n);
+int wm_pixloss_sums(int kind, const float* a, const float* b, const float* mask, size_t n, double* partials, void* stream);
+int wm_pixloss_finalize(int kind, const double* partials, size_t n, double* coef, float* loss_out, void* stream);
+int wm_pixloss_bwd(int kind, const float* a, const float* b, const float* mask, const double* coef, float* ga, float* gb, size_t n,
+                   const float* gout_dev, float gscale, const float* gscale_dev, int accumulate, void* stream);
+
 /* ------------------------------------------------------------------ GAN objectives (csrc/advloss.hip)
  * The reference's AdversarialLoss (loss.py:41-88), GANLoss and CWLoss (models/modules/loss.py:24-42, 77-109).  f32 contiguous tensors; no
  * atomics, no host synchronisation: one streaming launch writes double partials per workgroup and, when asked, the gradient; a fixed-order

@@ -370,10 +370,11 @@ class _StepGraph:
 
 class Hidden:
     recon_weight, recon_type = 0.0, 'l2'   # (class-level defaults: the graph key and _recon_term read them on any instance)
+    ssim3_weight = 0.0                     # (likewise, for _ssim3_term)
 
     def __init__(self, configuration: HiDDenConfiguration, device: torch.device, noiser, tb_logger=None,
                  compute_dtype=torch.bfloat16, grad_sync=None, amp=None, keep_dead_discriminator_grads=True, ssim_weight=0.0,
-                 recon_weight=0.0, recon_type='l2'):
+                 recon_weight=0.0, recon_type='l2', ssim3_weight=0.0):
         """
         :param configuration: sizes / loss weights (options.HiDDenConfiguration)
         :param device: must be a cuda (ROCm) device -- the step has no CPU path
@@ -403,6 +404,10 @@ class Hidden:
                     leaves the step bit for bit; > 0 adds the term's gradient into the encoded image's gradient and logs ('RecFW', value).
                     The term is a per-sample SUM over C*H*W values (196,608 x an MSE at 3 x 256 x 256): size the weight for that
         :param recon_type: 'l2' | 'l1' | 'l_char' (eps 1e-6), the reference's pixel_criterion_forw
+        :param ssim3_weight: weight w of the local structure term w * mean(SSIM_Loss()(encoded, cover)) (loss.py:9-39 of the reference: the
+                    3 x 3 reflect-padded SSIM map), wired exactly as ssim_weight: 0 (default) launches nothing and leaves the step bit for
+                    bit; > 0 adds the term's gradient into the encoded image's gradient and logs ('SS3FW', mean of the map).  Also settable
+                    afterwards as `hidden.ssim3_weight`
         """
         device = torch.device(device)
         if device.type != "cuda":
@@ -432,6 +437,7 @@ class Hidden:
             raise ValueError("recon_type must be one of %s, got %r" % (", ".join(ops.RECON_KINDS), recon_type))
         self.recon_weight = float(recon_weight)
         self.recon_type = recon_type
+        self.ssim3_weight = float(ssim3_weight)
         self.amp = amp
         self.amp_owner = True   # this object calls amp.update() at the end of a step (a wrapping model may take that over)
         if amp is not None:
@@ -518,7 +524,8 @@ class Hidden:
         """what a captured step depends on beside the tensors' contents: shapes, the attack variant and every switch that selects launches"""
         return (tuple(images.shape), tuple(messages.shape), self.noise_id, self.keep_dead_discriminator_grads, self.lazy_losses, self.two_streams,
                 self.skip_zero_attack_gradient, self.encoder_decoder.encoder.compute_dtype, ck, self.optimizer_discrim.decoupled,
-                self.optimizer_enc_dec.decoupled, float(self.ssim_weight), float(self.recon_weight), self.recon_type)
+                self.optimizer_enc_dec.decoupled, float(self.ssim_weight), float(self.recon_weight), self.recon_type,
+                float(self.ssim3_weight))
 
     def _ssim_term(self, encoded, images):
         """the structural-similarity fidelity term ssim_weight * (-SSIM(encoded, cover)): (SSIM value, its gradient wrt encoded in a buffer of
@@ -534,6 +541,13 @@ class Hidden:
         if not self.recon_weight > 0:
             return None, None
         return ops.recon_loss(encoded, images, self.recon_type, 1e-6, want_grad=True, gscale=self.recon_weight, gscale_dev=self._gsd())
+
+    def _ssim3_term(self, encoded, images):
+        """the local structure term ssim3_weight * mean(SSIM_Loss()(encoded, cover)): (the mean of the map, its gradient wrt encoded in a buffer
+        of its own, times the AMP scale) -- two launches and a finalise, the map itself is never written; (None, None) at weight 0"""
+        if not self.ssim3_weight > 0:
+            return None, None
+        return ops.ssim3_mean(encoded, images, want_grad=True, gscale=self.ssim3_weight, gscale_dev=self._gsd())
 
     def _step_eager(self, images, messages, extra_encoded_grad=None, clip=None, enc_gate=None):
         vals, extra_logs, outs = self._step_launches(images, messages, extra_encoded_grad, clip, enc_gate)
@@ -582,6 +596,7 @@ class Hidden:
         encoded, cE = enc_net.fwd(images, messages)
         ssim_val, g_ssim = self._ssim_term(encoded, images)   # (before the attack: the order of the two-chain schedule)
         rec_val, g_rec = self._recon_term(encoded, images)
+        s3_val, g_s3 = self._ssim3_term(encoded, images)
         noised, cN = self._run_noiser(encoded, images)
 
         d_on_encoded, d_loss_on_encoded, c = D.fwd_loss(encoded, self.encoded_label, 1.0, gD, accumulate=True, gscale_dev=self._gsd())   # encoded.detach()
@@ -624,6 +639,8 @@ class Hidden:
             ops.axpy_(g_enc, g_ssim)
         if g_rec is not None:
             ops.axpy_(g_enc, g_rec)
+        if g_s3 is not None:
+            ops.axpy_(g_enc, g_s3)
         zero_attack = self.skip_zero_attack_gradient and _noise_bwd_is_zero(ed.noiser, cN)
         g_noised = dec_net.bwd(cDec, None, gDec, accumulate=False, need_input_grad=not zero_attack)
         # data parallel: the decoder's bucket goes out now and travels while the attack and the encoder run their backward
@@ -640,6 +657,8 @@ class Hidden:
             extra_logs = list(extra_logs) + [('SSFW', ssim_val.reshape(1))]
         if rec_val is not None:
             extra_logs = list(extra_logs) + [('RecFW', rec_val.reshape(1))]
+        if s3_val is not None:
+            extra_logs = list(extra_logs) + [('SS3FW', s3_val.reshape(1))]
         if gs is not None:
             # the encoder in two reverse-order buckets: [after_concat, final] leaves under the body layers' backward
             cut = enc_net.body_param_count()
@@ -704,7 +723,8 @@ class Hidden:
             # chain A runs the discriminator; chain A waits for ev_ssim before it adds the term's gradient
             ssim_val, g_ssim = self._ssim_term(encoded, images)
             rec_val, g_rec = self._recon_term(encoded, images)    # (the reconstruction term likewise, right behind it)
-            if g_ssim is not None or g_rec is not None:
+            s3_val, g_s3 = self._ssim3_term(encoded, images)      # (and the 3 x 3 structure term)
+            if g_ssim is not None or g_rec is not None or g_s3 is not None:
                 ev_ssim = torch.cuda.Event()
                 ev_ssim.record(sB)
             noised, cN = self._run_noiser(encoded, images)
@@ -724,12 +744,14 @@ class Hidden:
             g_img = D.bwd(c, g, gD, accumulate=True, need_input_grad=True, weight_grads=self.keep_dead_discriminator_grads, raw_input_grad=True)
             n_img = encoded.numel()
             g_enc, enc_part = ops.image_grad_mse(g_img, encoded, images, 2.0 * cfg.encoder_loss / n_img, gscale_dev=self._gsd())
-            if g_ssim is not None or g_rec is not None:   # before the encoder's backward wherever that runs (zero_attack: right below, on this chain)
+            if g_ssim is not None or g_rec is not None or g_s3 is not None:   # before the encoder's backward wherever that runs (zero_attack: right below, on this chain)
                 sA.wait_event(ev_ssim)
             if g_ssim is not None:
                 ops.axpy_(g_enc, g_ssim)
             if g_rec is not None:
                 ops.axpy_(g_enc, g_rec)
+            if g_s3 is not None:
+                ops.axpy_(g_enc, g_s3)
             if zero_attack:
                 # nothing of chain B reaches the encoder's gradient (the attack passes back zeros): the encoder's backward continues chain A,
                 # beside the decoder's backward on chain B, and the chains meet only at the optimiser step
@@ -748,6 +770,7 @@ class Hidden:
         # referenced until this function returns, and a side stream is given work only between a fork (wait_stream(main)) and the join
         # above -- so a block that returns to a side stream's pool is not handed out again before main's readers of it are ordered ahead
         extra_logs = ([('SSFW', ssim_val.reshape(1))] if ssim_val is not None else []) + ([('RecFW', rec_val.reshape(1))] if rec_val is not None else [])
+        extra_logs += [('SS3FW', s3_val.reshape(1))] if s3_val is not None else []
         return vals, extra_logs, (encoded, noised, decoded)
 
     def _chain_streams(self):

@@ -21,7 +21,16 @@ get_gradients are NOT carried over: they exist to build those intermediate tenso
 Two deliberate differences: (1) a term whose mean is exactly 0 (a constant image) contributes a zero gradient where the reference's autograd
 returns NaN (0 * inf); its forward value is 0 either way.  (2) channel counts may differ (the reference's pair loop then indexes the wrong
 image and raises): term i2 * C1 + i1 pairs img1's channel i1 with img2's i2, the reference's order when the counts agree.
-Not carried over from that file: StdLoss, ExtendedL1Loss, NonBlurryLoss and the gray losses."""
+
+    SSIM_Loss()(x, y)               = clamp((1 - SSIM_n / SSIM_d) / 2, 0, 1), a [B,C,H,W] MAP (loss.py:9-39): both images reflect-padded by 1,
+        3 x 3 box means mu, E[x^2], E[y^2], E[xy], C1 = 0.01^2, C2 = 0.03^2.  H, W >= 2.  One launch forwards, one backwards (csrc/ssim3.hip);
+        the clamp passes the gradient on its bounds, as torch.clamp.  x is y gives exactly 0.
+    ExtendedL1Loss()(a, b, mask)    = mean |mask*a - mask*b| / mean |mask| (loss.py:363-376).  Gradients wrt a and b (sign(0) = 0, as torch's
+        L1Loss), none wrt the mask.  A zero mask gives NaN as the reference does: it is not guarded.  The mask broadcasts to a's shape.
+    NonBlurryLoss()(x)              = 1 - mean (x - 1/2)^2 (loss.py:379-388)
+    GrayLoss()(x)                   = 1 / mean |x - 1/2| (loss.py:403-410)
+Not carried over from that file: StdLoss and GrayscaleLoss -- both raise NameError in the reference as written, its `from layers import ...
+GrayscaleLayer` being commented out."""
 import torch
 
 from . import ops
@@ -150,3 +159,95 @@ class GradientLoss(torch.nn.Module):
     def forward(self, a):
         _check("GradientLoss", a)
         return _GradientFunction.apply(a)
+
+
+class _SSIM3Function(torch.autograd.Function):
+    """ops.ssim3_map_fwd under autograd: the backward is ONE launch for the gradients the graph asks for"""
+    @staticmethod
+    def forward(ctx, x, y):
+        a, b = x.detach().contiguous(), y.detach().contiguous()
+        ctx.save_for_backward(a, b)
+        return ops.ssim3_map_fwd(a, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        return ops.ssim3_map_bwd(a, b, g.detach().to(torch.float32).contiguous(), want=ctx.needs_input_grad[:2])
+
+
+class SSIM_Loss(torch.nn.Module):
+    """Layer to compute the SSIM loss between a pair of images
+    """
+    def __init__(self):
+        super().__init__()
+        self.C1 = 0.01 ** 2
+        self.C2 = 0.03 ** 2
+
+    def forward(self, x, y):
+        _check("SSIM_Loss", x, y)
+        if x.shape != y.shape:
+            raise ValueError("SSIM_Loss: x and y must have one shape")
+        if x.shape[2] < 2 or x.shape[3] < 2:
+            raise ValueError("SSIM_Loss: H and W must be at least 2 (ReflectionPad2d(1) needs two pixels)")
+        return _SSIM3Function.apply(x, y)
+
+
+class _PixLossFunction(torch.autograd.Function):
+    """the three reductions of csrc/ssim3.hip under autograd: sums + finalise forwards, one launch backwards"""
+    @staticmethod
+    def forward(ctx, kind, a, b, mask):
+        ts = [t.detach().contiguous() for t in (a, b, mask) if t is not None]
+        loss, coef = {"masked_l1": ops.extended_l1_fwd, "non_blurry": ops.non_blurry_fwd, "gray": ops.gray_loss_fwd}[kind](*ts)
+        ctx.kind = kind
+        ctx.save_for_backward(coef, *ts)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        coef, *ts = ctx.saved_tensors
+        gout = gout.detach().to(torch.float32).contiguous().reshape(-1)
+        if ctx.kind == "masked_l1":
+            ga, gb = ops.extended_l1_bwd(*ts, coef, want=ctx.needs_input_grad[1:3], gout=gout)
+            return None, ga, gb, None
+        bwd = ops.non_blurry_bwd if ctx.kind == "non_blurry" else ops.gray_loss_bwd
+        return None, bwd(ts[0], coef, gout=gout), None, None
+
+
+def _check_any(name, *ts):
+    need_cuda(name, *ts)
+    for t in ts:
+        if t.dtype != torch.float32:
+            raise TypeError(name + ": float32 tensors expected")
+        if t.numel() == 0:
+            raise ValueError(name + ": non-empty tensors expected")
+
+
+class ExtendedL1Loss(torch.nn.Module):
+    """
+    also pays attention to the mask, to be relative to its size
+    """
+    def forward(self, a, b, mask):
+        _check_any("ExtendedL1Loss", a, b, mask)
+        if a.shape != b.shape:
+            raise ValueError("ExtendedL1Loss: a and b must have one shape")
+        if mask.shape != a.shape:
+            mask = mask.expand_as(a)      # (mean |mask| over the expanded mask is the mean over the mask)
+        return _PixLossFunction.apply("masked_l1", a, b, mask.detach())
+
+
+class NonBlurryLoss(torch.nn.Module):
+    def __init__(self):
+        """
+        Loss on the distance to 0.5
+        """
+        super().__init__()
+
+    def forward(self, x):
+        _check_any("NonBlurryLoss", x)
+        return _PixLossFunction.apply("non_blurry", x, None, None)
+
+
+class GrayLoss(torch.nn.Module):
+    def forward(self, x):
+        _check_any("GrayLoss", x)
+        return _PixLossFunction.apply("gray", x, None, None)

@@ -194,10 +194,13 @@ class IRNrhiModel(BaseModel):
         # train.lambda_fit_forw (default 0 = off) and train.pixel_criterion_forw (l2 | l1 | l_char, default l2), the reference's own keys
         # (models/IRNrhi_model.py:102,153-155): lambda_fit_forw * ReconstructionLoss(encoded, cover, pixel_criterion_forw), logged as RecFW.
         # The term is a per-sample SUM, 196,608 x an MSE at 3 x 256 x 256
+        # train.ssim3_weight (default 0 = off): w * mean(SSIM_Loss()(encoded, cover)), the reference's 3 x 3 reflect-padded structure map
+        # (loss.py:9-39), logged as SS3FW
         self.hidden = Hidden(cfg, self.device, self.attack, None, compute_dtype=dtype, grad_sync=grad_sync, amp=self.amp,
                              ssim_weight=float(_get(train_opt, 'ssim_weight', default=0.0) or 0.0),
                              recon_weight=float(_get(train_opt, 'lambda_fit_forw', default=0.0) or 0.0),
-                             recon_type=_get(train_opt, 'pixel_criterion_forw', default='l2') or 'l2')
+                             recon_type=_get(train_opt, 'pixel_criterion_forw', default='l2') or 'l2',
+                             ssim3_weight=float(_get(train_opt, 'ssim3_weight', default=0.0) or 0.0))
         # train.eval_metrics (default false): evaluate() appends robustness_report() to its logs
         self.eval_metrics = bool(_get(train_opt, 'eval_metrics', default=False))
         # train.two_streams (default true): the step's two independent chains on two streams wherever a step has them to itself (one GPU, no

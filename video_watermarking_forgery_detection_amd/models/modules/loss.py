@@ -18,11 +18,13 @@ It is a sum per sample, not a mean: at 3 x 256 x 256 the l2 form is 196,608 x an
         host, which here would cost a synchronisation per call (ops.cw_margin(check_target=True) does that check).
     GANLoss(gan_type)(input, target_is_real): gan / ragan = BCE-with-logits against real_label_val / fake_label_val, lsgan = MSE against
         them, wgan-gp = -mean(input) (real) or mean(input).
-Not carried over from that file: GradientPenaltyLoss (a second-order backward through the convolutions) and SSIM_Loss."""
+    SSIM_Loss()(x, y) (:44-74, the same text as loss.py:9-39): the [B,C,H,W] map clamp((1 - SSIM_n / SSIM_d) / 2, 0, 1) of reflect-padded 3 x 3
+        box statistics on the kernels of csrc/ssim3.hip -- the one class of the package's loss module, re-exported here.
+Not carried over from that file: GradientPenaltyLoss, which needs a second-order backward through the convolutions."""
 import torch
 
 from ... import ops
-from ...loss import adv_objective
+from ...loss import SSIM_Loss, adv_objective  # noqa: F401  (SSIM_Loss: this module exports it too, as the reference's does)
 from ...noise_layers._device_rng import need_cuda
 
 

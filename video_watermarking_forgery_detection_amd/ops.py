@@ -2144,6 +2144,144 @@ def exclusion_bwd(img1, img2, coef, level=3, want=(True, True), gout=None, gscal
     return g[0], g[1]
 
 
+# ----------------------------------------------------------------------------- local structure loss, mask and gray losses (csrc/ssim3.hip)
+def _ssim3_args(name, x, y):
+    _f32_cuda(name, x, y)
+    if x.dim() != 4 or x.shape != y.shape or x.numel() == 0:
+        raise ValueError(name + ": two non-empty [B,C,H,W] tensors of one shape expected")
+    if x.shape[2] < 2 or x.shape[3] < 2:
+        raise ValueError(name + ": H and W must be at least 2 (the reflection padding needs two pixels)")
+    return x.shape[0] * x.shape[1], x.shape[2], x.shape[3]
+
+
+def ssim3_map_fwd(x, y):
+    """SSIM_Loss()(x, y): the [B,C,H,W] map clamp((1 - SSIM_n / SSIM_d) / 2, 0, 1) from reflect-padded 3 x 3 box statistics.  One launch"""
+    N, H, W = _ssim3_args("ssim3_map_fwd", x, y)
+    out = torch.empty_like(x)
+    rc = _timed("ssim3_fwd", None, lambda: _lib.lib().wm_ssim3_fwd(_p(x), _p(y), _p(out), None, N, H, W, _stream()))
+    _lib.check(rc, "wm_ssim3_fwd")
+    return out
+
+
+def _ssim3_bwd(name, x, y, g, want, gout, gscale, gscale_dev, out, accumulate):
+    N, H, W = _ssim3_args(name, x, y)
+    if not (want[0] or want[1]):
+        return None, None
+    res = []
+    for t, w, o in zip((x, y), want, out):
+        if w:
+            gout, o = _loss_bwd_args(name, t, gout, gscale_dev, o, accumulate)
+        res.append(o if w else None)
+    rc = _timed("ssim3_bwd", None, lambda: _lib.lib().wm_ssim3_bwd(_p(x), _p(y), _p(g), _p(res[0]), _p(res[1]), N, H, W, _p(gout), gscale,
+                                                                   _p(gscale_dev), 1 if accumulate else 0, _stream()))
+    _lib.check(rc, "wm_ssim3_bwd")
+    _wrote(*res)
+    return res[0], res[1]
+
+
+def ssim3_map_bwd(x, y, g, want=(True, True), gscale=1.0, gscale_dev=None, out=(None, None), accumulate=False):
+    """gradients wrt x and y of gscale * gscale_dev[0] * sum(g * ssim3_map_fwd(x, y)) for an upstream map g of x's shape -> (gx, gy), None where
+    want[i] is false.  The clamp passes the gradient where the unclamped value lies in [0, 1], bounds included (torch.clamp).  One launch"""
+    _f32_cuda("ssim3_map_bwd", g)
+    if g.shape != x.shape:
+        raise ValueError("ssim3_map_bwd: the upstream gradient must have the inputs' shape")
+    return _ssim3_bwd("ssim3_map_bwd", x, y, g, want, None, gscale, gscale_dev, out, accumulate)
+
+
+def ssim3_mean_fwd(x, y):
+    """mean(SSIM_Loss()(x, y)) -> a [1] device tensor; the map is never written.  Two launches, no host sync"""
+    N, H, W = _ssim3_args("ssim3_mean", x, y)
+    L = _lib.lib()
+    part = torch.empty(max(1, L.wm_ssim3_nparts(N, H, W)), device=x.device, dtype=torch.float64)
+    loss = torch.empty(1, device=x.device, dtype=torch.float32)
+    rc = _timed("ssim3_fwd", None, lambda: L.wm_ssim3_fwd(_p(x), _p(y), None, _p(part), N, H, W, _stream()))
+    _lib.check(rc, "wm_ssim3_fwd")
+    rc = L.wm_ssim3_finalize(_p(part), N, H, W, _p(loss), _stream())
+    _lib.check(rc, "wm_ssim3_finalize")
+    return loss
+
+
+def ssim3_mean_bwd(x, y, want=(True, False), gout=None, gscale=1.0, gscale_dev=None, out=(None, None), accumulate=False):
+    """gradients wrt x and y of gscale * gscale_dev[0] * gout[0] * mean(SSIM_Loss()(x, y)) -> (gx, gy).  One launch, the kernel of
+    ssim3_map_bwd with one weight for every pixel"""
+    return _ssim3_bwd("ssim3_mean_bwd", x, y, None, want, gout, gscale, gscale_dev, out, accumulate)
+
+
+def ssim3_mean(x, y, want_grad=False, gscale=1.0, gscale_dev=None, grad_out=None):
+    """mean(SSIM_Loss()(x, y)) as a [1] device tensor, and with want_grad its gradient wrt x: (loss, grad) with loss UNSCALED and
+    grad = gscale * gscale_dev[0] * d loss / dx.  grad_out: an existing gradient buffer the result is ADDED into (and returned)"""
+    loss = ssim3_mean_fwd(x, y)
+    if not want_grad:
+        return loss
+    return loss, ssim3_mean_bwd(x, y, (True, False), None, gscale, gscale_dev, (grad_out, None), grad_out is not None)[0]
+
+
+PIXLOSS_KINDS = {"masked_l1": 0, "non_blurry": 1, "gray": 2}    # WM_PIXLOSS_MASKL1 / NONBLURRY / GRAY
+
+
+def _pixloss_fwd(name, kind, a, b=None, mask=None):
+    _f32_cuda(name, a, b, mask)
+    if a.numel() == 0 or any(t is not None and t.shape != a.shape for t in (b, mask)):
+        raise ValueError(name + ": non-empty tensors of one shape expected")
+    L, n = _lib.lib(), a.numel()
+    part = torch.empty(2 * L.wm_pixloss_nparts(n), device=a.device, dtype=torch.float64)
+    coef = torch.empty(2, device=a.device, dtype=torch.float64)
+    loss = torch.empty(1, device=a.device, dtype=torch.float32)
+    k = PIXLOSS_KINDS[kind]
+    rc = _timed("pixloss_sums", None, lambda: L.wm_pixloss_sums(k, _p(a), _p(b), _p(mask), n, _p(part), _stream()))
+    _lib.check(rc, "wm_pixloss_sums")
+    rc = L.wm_pixloss_finalize(k, _p(part), n, _p(coef), _p(loss), _stream())
+    _lib.check(rc, "wm_pixloss_finalize")
+    return loss, coef
+
+
+def _pixloss_bwd(name, kind, a, b, mask, coef, want, gout, gscale, gscale_dev, accumulate, out):
+    _f32_cuda(name, a, b, mask)
+    _need_cuda(coef)
+    assert coef.dtype == torch.float64 and coef.is_contiguous() and coef.numel() == 2
+    res = []
+    for w, o in zip(want, out):
+        if w:
+            gout, o = _loss_bwd_args(name, a, gout, gscale_dev, o, accumulate)
+        res.append(o if w else None)
+    if res[0] is None and res[1] is None:
+        return None, None
+    rc = _timed("pixloss_bwd", None, lambda: _lib.lib().wm_pixloss_bwd(PIXLOSS_KINDS[kind], _p(a), _p(b), _p(mask), _p(coef), _p(res[0]), _p(res[1]),
+                                                                       a.numel(), _p(gout), gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
+    _lib.check(rc, "wm_pixloss_bwd")
+    _wrote(*res)
+    return res[0], res[1]
+
+
+def extended_l1_fwd(a, b, mask):
+    """ExtendedL1Loss()(a, b, mask) = mean |mask*a - mask*b| / mean |mask| -> (loss [1] f32, coef [2] f64 -- what extended_l1_bwd reads).
+    Three tensors of one shape.  A zero mask gives NaN (0 / 0), as the reference: unguarded.  Two launches, no host sync"""
+    return _pixloss_fwd("extended_l1", "masked_l1", a, b, mask)
+
+
+def extended_l1_bwd(a, b, mask, coef, want=(True, True), gout=None, gscale=1.0, gscale_dev=None, out=(None, None), accumulate=False):
+    """gradients wrt a and b of gscale * gscale_dev[0] * gout[0] * extended_l1 -> (ga, gb); sign(0) = 0, as torch's L1Loss.  One launch"""
+    return _pixloss_bwd("extended_l1_bwd", "masked_l1", a, b, mask, coef, want, gout, gscale, gscale_dev, accumulate, out)
+
+
+def non_blurry_fwd(x):
+    """NonBlurryLoss()(x) = 1 - mean (x - 1/2)^2 -> (loss [1] f32, coef [2] f64)"""
+    return _pixloss_fwd("non_blurry", "non_blurry", x)
+
+
+def non_blurry_bwd(x, coef, gout=None, gscale=1.0, gscale_dev=None, out=None, accumulate=False):
+    return _pixloss_bwd("non_blurry_bwd", "non_blurry", x, None, None, coef, (True, False), gout, gscale, gscale_dev, accumulate, (out, None))[0]
+
+
+def gray_loss_fwd(x):
+    """GrayLoss()(x) = 1 / mean |x - 1/2| -> (loss [1] f32, coef [2] f64 -- coef[0] is the mean gray_loss_bwd reads)"""
+    return _pixloss_fwd("gray_loss", "gray", x)
+
+
+def gray_loss_bwd(x, coef, gout=None, gscale=1.0, gscale_dev=None, out=None, accumulate=False):
+    return _pixloss_bwd("gray_loss_bwd", "gray", x, None, None, coef, (True, False), gout, gscale, gscale_dev, accumulate, (out, None))[0]
+
+
 # ----------------------------------------------------------------------------- GAN objectives (csrc/advloss.hip)
 ADV_OBJECTIVES = {"bce_prob": 0, "bce_logits": 1, "mse": 2, "hinge_disc": 3, "neg_mean": 4, "pos_mean": 5}    # WM_ADV_*
 _ADV_LABELLED = ("bce_prob", "bce_logits", "mse")
