@@ -15,46 +15,12 @@
 // CW margin: one wave per row.  The row's `other` is the maximum of (1 - onehot) * logits - onehot * 10000 restated literally (the target's
 // slot holds -10000, not -inf) together with the lowest column that attains it, which is where torch.max(x, 1) sends its gradient.
 #include "wm_common.h"
+#include "wm_reduce.h"
 
 namespace {
 
 constexpr int BCE_PROB = WM_ADV_BCE_PROB, BCE_LOGITS = WM_ADV_BCE_LOGITS, MSE = WM_ADV_MSE, HINGE_DISC = WM_ADV_HINGE_DISC,
               NEG_MEAN = WM_ADV_NEG_MEAN, POS_MEAN = WM_ADV_POS_MEAN;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// 256 threads -> the sum in thread 0 (fixed order); s: 4 doubles of LDS
-__device__ __forceinline__ double block_sum_f64(double v, double* s) {
-    v = wave_sum_f64(v);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s[0] + s[1]) + (s[2] + s[3]);
-}
-
-// [0, n) split for 16-byte access, as csrc/imgloss.hip: a scalar head up to the first 16-byte boundary of `a`, nv float4s, a scalar tail;
-// `b` shares the split only when it reaches a boundary at the same element (otherwise everything is scalar)
-struct Split { size_t head, nv, tail0; };
-__device__ __forceinline__ Split split16(const void* a, const void* b, size_t n) {
-    Split s;
-    s.head = ((16 - ((uintptr_t)a & 15)) & 15) >> 2;
-    if (s.head > n) s.head = n;
-    const bool same = b == nullptr || (((uintptr_t)a ^ (uintptr_t)b) & 15) == 0;
-    s.nv = same ? (n - s.head) / 4 : 0;
-    if (s.nv == 0) s.head = 0;
-    s.tail0 = s.head + s.nv * 4;
-    return s;
-}
-
-// the upstream weight of a scalar loss: gscale * gscale_dev[0] * gout[0]
-__device__ __forceinline__ double upstream(float gscale, const float* __restrict__ gscale_dev, const float* __restrict__ gout) {
-    double g = (double)gscale;
-    if (gscale_dev) g *= (double)gscale_dev[0];
-    if (gout) g *= (double)gout[0];
-    return g;
-}
 
 // the label of element i: the scalar, or real * (1 - the bilinear sample of the mask at i's pixel)
 struct Labels {
@@ -128,55 +94,31 @@ __global__ __launch_bounds__(256) void advloss_elem_kernel(const float* __restri
                                                            float* __restrict__ grad, const float* __restrict__ gout, float gscale,
                                                            const float* __restrict__ gscale_dev, int accumulate) {
     const double k = GRAD ? upstream(gscale, gscale_dev, gout) / (double)n : 0.0;
-    const Split sp = split16(x, GRAD ? grad : nullptr, n);
-    const size_t stride = (size_t)gridDim.x * 256, first = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const Split sp = split16(n, x, GRAD ? grad : nullptr);
     double a = 0.0;
-    for (size_t q = first; q < sp.nv; q += stride) {
-        const size_t i = sp.head + 4 * q;
-        const float4 p = *reinterpret_cast<const float4*>(x + i);
-        double v0, v1, v2, v3, d0, d1, d2, d3;
-        elem<OBJ, GRAD>(p.x, label_at(L, i), v0, d0);
-        elem<OBJ, GRAD>(p.y, label_at(L, i + 1), v1, d1);
-        elem<OBJ, GRAD>(p.z, label_at(L, i + 2), v2, d2);
-        elem<OBJ, GRAD>(p.w, label_at(L, i + 3), v3, d3);
-        a += v0; a += v1; a += v2; a += v3;
-        if (GRAD) {
-            float4* o = reinterpret_cast<float4*>(grad + i);
-            d0 *= k; d1 *= k; d2 *= k; d3 *= k;
-            if (accumulate) { const float4 old = *o; d0 += (double)old.x; d1 += (double)old.y; d2 += (double)old.z; d3 += (double)old.w; }
-            *o = make_float4((float)d0, (float)d1, (float)d2, (float)d3);
-        }
-    }
-    const size_t nscalar = sp.head + (n - sp.tail0);
-    for (size_t j = first; j < nscalar; j += stride) {
-        const size_t i = j < sp.head ? j : sp.tail0 + (j - sp.head);
-        double v, d;
-        elem<OBJ, GRAD>(x[i], label_at(L, i), v, d);
-        a += v;
-        if (GRAD) {
-            d *= k;
-            if (accumulate) d += (double)grad[i];
-            grad[i] = (float)d;
-        }
-    }
+    stream16(sp, n,
+             [&](size_t i) {
+                 const float4 p = ld16(x + i);
+                 double v0, v1, v2, v3, d0, d1, d2, d3;
+                 elem<OBJ, GRAD>(p.x, label_at(L, i), v0, d0);
+                 elem<OBJ, GRAD>(p.y, label_at(L, i + 1), v1, d1);
+                 elem<OBJ, GRAD>(p.z, label_at(L, i + 2), v2, d2);
+                 elem<OBJ, GRAD>(p.w, label_at(L, i + 3), v3, d3);
+                 a += v0; a += v1; a += v2; a += v3;
+                 if (GRAD) store4<double>(grad + i, d0 * k, d1 * k, d2 * k, d3 * k, accumulate);
+             },
+             [&](size_t i) {
+                 double v, d;
+                 elem<OBJ, GRAD>(x[i], label_at(L, i), v, d);
+                 a += v;
+                 if (GRAD) store1<double>(grad + i, d * k, accumulate);
+             });
     __shared__ double s[4];
     a = block_sum_f64(a, s);
     if (threadIdx.x == 0) partials[blockIdx.x] = a;
 }
 
-// one workgroup: out[0] = scale * sum of the n partials (thread i adds partials i, i+256, ...; then the fixed tree)
-__global__ __launch_bounds__(256) void advloss_finalize_kernel(const double* __restrict__ partials, size_t n, double scale, float* __restrict__ out) {
-    __shared__ double s[4];
-    double a = 0.0;
-    for (size_t i = threadIdx.x; i < n; i += 256) a += partials[i];
-    a = block_sum_f64(a, s);
-    if (threadIdx.x == 0) out[0] = (float)(a * scale);
-}
-
-inline int elem_parts(size_t n) {
-    const size_t g = (n + 4095) / 4096;
-    return (int)(g > 256 ? 256 : (g < 1 ? 1 : g));
-}
+inline int elem_parts(size_t n) { return wm_groups(n, 4096, 256); }
 inline bool obj_ok(int o) { return o >= BCE_PROB && o <= POS_MEAN; }
 inline bool obj_has_label(int o) { return o == BCE_PROB || o == BCE_LOGITS || o == MSE; }
 
@@ -278,8 +220,7 @@ extern "C" int wm_advloss_elem(int objective, const float* x, size_t n, float la
 
 extern "C" int wm_advloss_finalize(const double* partials, size_t n, float* loss_out, void* stream) {
     WM_REQUIRE(partials && loss_out && n > 0, WM_E_BADARG, "wm_advloss_finalize: bad arguments");
-    hipLaunchKernelGGL(advloss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (size_t)elem_parts(n), 1.0 / (double)n,
-                       loss_out);
+    wm_sum_finalize(partials, (size_t)elem_parts(n), 1.0 / (double)n, loss_out, (hipStream_t)stream);
     WM_LAUNCH_CHECK("wm_advloss_finalize");
     return WM_OK;
 }
@@ -292,7 +233,7 @@ extern "C" int wm_cw_margin(const float* logits, const long long* target, int B,
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(cw_margin_kernel, dim3((unsigned)(((size_t)B + 3) / 4)), dim3(256), 0, s, logits, target, B, K, is_targeted ? 1 : 0, kappa,
                        terms, grad, gout_dev, gscale, gscale_dev, accumulate);
-    hipLaunchKernelGGL(advloss_finalize_kernel, dim3(1), dim3(256), 0, s, terms, (size_t)B, 1.0, loss_out);
+    wm_sum_finalize(terms, (size_t)B, 1.0, loss_out, s);
     WM_LAUNCH_CHECK("wm_cw_margin");
     return WM_OK;
 }

@@ -12,6 +12,7 @@
 // Elements are multiplied in f32 (as the reference's f32 run does) and added in double.  pw = 1 and pw = 2 are compile-time paths without
 // powf; any other positive exponent goes through powf.
 #include "wm_common.h"
+#include "wm_reduce.h"
 
 namespace {
 
@@ -31,55 +32,31 @@ template <int PW> __device__ __forceinline__ float pow_pm1(float x, float pw) {
     return powf(x, pw - 1.f);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// One sample's [0, per) split for 16-byte access: a scalar head up to the first 16-byte boundary of `a`, nv float4s, a scalar tail.  The
-// second pointer shares the split only when it reaches a boundary at the same element; otherwise (nv = 0) everything is scalar.
-struct Split { size_t head, nv, tail0; };
-__device__ __forceinline__ Split split16(const void* a, const void* b, const void* c, size_t per) {
-    Split s;
-    s.head = ((16 - ((uintptr_t)a & 15)) & 15) >> 2;
-    if (s.head > per) s.head = per;
-    const bool same = (((uintptr_t)a ^ (uintptr_t)b) & 15) == 0 && (c == nullptr || (((uintptr_t)a ^ (uintptr_t)c) & 15) == 0);
-    s.nv = same ? (per - s.head) / 4 : 0;
-    if (s.nv == 0) s.head = 0;
-    s.tail0 = s.head + s.nv * 4;
-    return s;
-}
-
 // grid (P, B): block (j, b) takes its grid-stride share of sample b -> partials[(b*P + j)*3 + {sum p*t, sum p^pw, sum t^pw}]
 template <int PW>
 __global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict__ p, const float* __restrict__ t, size_t per, float pw,
                                                         double* __restrict__ partials) {
     const float* pb = p + (size_t)blockIdx.y * per;
     const float* tb = t + (size_t)blockIdx.y * per;
-    const Split sp = split16(pb, tb, nullptr, per);
-    const size_t stride = (size_t)gridDim.x * 256, first = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const Split sp = split16(per, pb, tb);
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    for (size_t v = first; v < sp.nv; v += stride) {
-        const float4 x = *reinterpret_cast<const float4*>(pb + sp.head + 4 * v);
-        const float4 y = *reinterpret_cast<const float4*>(tb + sp.head + 4 * v);
-        a0 += (double)(x.x * y.x); a0 += (double)(x.y * y.y); a0 += (double)(x.z * y.z); a0 += (double)(x.w * y.w);
-        a1 += (double)pow_p<PW>(x.x, pw); a1 += (double)pow_p<PW>(x.y, pw); a1 += (double)pow_p<PW>(x.z, pw); a1 += (double)pow_p<PW>(x.w, pw);
-        a2 += (double)pow_p<PW>(y.x, pw); a2 += (double)pow_p<PW>(y.y, pw); a2 += (double)pow_p<PW>(y.z, pw); a2 += (double)pow_p<PW>(y.w, pw);
+    stream16(sp, per,
+             [&](size_t at) {
+                 const float4 x = ld16(pb + at), y = ld16(tb + at);
+                 a0 += (double)(x.x * y.x); a0 += (double)(x.y * y.y); a0 += (double)(x.z * y.z); a0 += (double)(x.w * y.w);
+                 a1 += (double)pow_p<PW>(x.x, pw); a1 += (double)pow_p<PW>(x.y, pw); a1 += (double)pow_p<PW>(x.z, pw); a1 += (double)pow_p<PW>(x.w, pw);
+                 a2 += (double)pow_p<PW>(y.x, pw); a2 += (double)pow_p<PW>(y.y, pw); a2 += (double)pow_p<PW>(y.z, pw); a2 += (double)pow_p<PW>(y.w, pw);
+             },
+             [&](size_t idx) {
+                 const float x = pb[idx], y = tb[idx];
+                 a0 += (double)(x * y); a1 += (double)pow_p<PW>(x, pw); a2 += (double)pow_p<PW>(y, pw);
+             });
+    __shared__ double s[3][4];
+    a0 = block_sum_f64(a0, s[0]); a1 = block_sum_f64(a1, s[1]); a2 = block_sum_f64(a2, s[2]);
+    if (threadIdx.x == 0) {
+        double* q = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
+        q[0] = a0; q[1] = a1; q[2] = a2;
     }
-    const size_t nscalar = sp.head + (per - sp.tail0);
-    for (size_t i = first; i < nscalar; i += stride) {
-        const size_t idx = i < sp.head ? i : sp.tail0 + (i - sp.head);
-        const float x = pb[idx], y = tb[idx];
-        a0 += (double)(x * y); a1 += (double)pow_p<PW>(x, pw); a2 += (double)pow_p<PW>(y, pw);
-    }
-    __shared__ double s[4][3];
-    a0 = wave_sum_f64(a0); a1 = wave_sum_f64(a1); a2 = wave_sum_f64(a2);
-    if ((threadIdx.x & 63) == 0) { s[threadIdx.x >> 6][0] = a0; s[threadIdx.x >> 6][1] = a1; s[threadIdx.x >> 6][2] = a2; }
-    __syncthreads();
-    if (threadIdx.x < 3)
-        partials[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 + threadIdx.x] =
-            (s[0][threadIdx.x] + s[1][threadIdx.x]) + (s[2][threadIdx.x] + s[3][threadIdx.x]);
 }
 
 // ---- the softmax form: a thread owns 4 pixels of a 1024-pixel tile.  VEC (HW % 4 == 0, 16-byte aligned bases): pixels pix0 .. pix0+3 as one
@@ -216,12 +193,9 @@ __global__ __launch_bounds__(256) void dice_finalize_kernel(const double* __rest
 }
 
 // the upstream weight of sample b's loss: gscale * gscale_dev[0] * gout[none ? b : 0], / B for the mean
-__device__ __forceinline__ double upstream(int b, int B, int reduction, float gscale, const float* __restrict__ gscale_dev, const float* __restrict__ gout) {
-    double g = (double)gscale;
-    if (gscale_dev) g *= (double)gscale_dev[0];
-    if (gout) g *= (double)gout[reduction == RED_NONE ? b : 0];
-    if (reduction == RED_MEAN) g /= (double)B;
-    return g;
+__device__ __forceinline__ double upstream_b(int b, int B, int reduction, float gscale, const float* __restrict__ gscale_dev, const float* __restrict__ gout) {
+    const double g = upstream(gscale, gscale_dev, gout, reduction == RED_NONE ? b : 0);
+    return reduction == RED_MEAN ? g / (double)B : g;
 }
 
 // grid (G, B).  d (1 - num/den) / d p_i = (num * pw * p_i^(pw-1) - t_i * den) / den^2 = kp * p_i^(pw-1) - kt * t_i
@@ -231,32 +205,23 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
                                                        const float* __restrict__ gout, float gscale, const float* __restrict__ gscale_dev,
                                                        int chain_sigmoid, int accumulate) {
     const int b = blockIdx.y;
-    const double g = upstream(b, B, reduction, gscale, gscale_dev, gout), num = coef[2 * b], den = coef[2 * b + 1];
+    const double g = upstream_b(b, B, reduction, gscale, gscale_dev, gout), num = coef[2 * b], den = coef[2 * b + 1];
     const float kt = (float)(g / den), kp = (float)(g * num * (double)pw / (den * den));
     const float* pb = p + (size_t)b * per;
     const float* tb = t + (size_t)b * per;
     float* gb = grad + (size_t)b * per;
-    const Split sp = split16(pb, tb, gb, per);
-    const size_t stride = (size_t)gridDim.x * 256, first = (size_t)blockIdx.x * 256 + threadIdx.x;
-    auto one = [&](float x, float y, float old) {
+    const Split sp = split16(per, pb, tb, gb);
+    auto one = [&](float x, float y) {
         float v = kp * pow_pm1<PW>(x, pw) - kt * y;
         if (chain_sigmoid) v *= x * (1.f - x);
-        return accumulate ? old + v : v;
+        return v;
     };
-    for (size_t v = first; v < sp.nv; v += stride) {
-        const float4 x = *reinterpret_cast<const float4*>(pb + sp.head + 4 * v);
-        const float4 y = *reinterpret_cast<const float4*>(tb + sp.head + 4 * v);
-        float4* q = reinterpret_cast<float4*>(gb + sp.head + 4 * v);
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (accumulate) o = *q;
-        o.x = one(x.x, y.x, o.x); o.y = one(x.y, y.y, o.y); o.z = one(x.z, y.z, o.z); o.w = one(x.w, y.w, o.w);
-        *q = o;
-    }
-    const size_t nscalar = sp.head + (per - sp.tail0);
-    for (size_t i = first; i < nscalar; i += stride) {
-        const size_t idx = i < sp.head ? i : sp.tail0 + (i - sp.head);
-        gb[idx] = one(pb[idx], tb[idx], accumulate ? gb[idx] : 0.f);
-    }
+    stream16(sp, per,
+             [&](size_t at) {
+                 const float4 x = ld16(pb + at), y = ld16(tb + at);
+                 store4<float>(gb + at, one(x.x, y.x), one(x.y, y.y), one(x.z, y.z), one(x.w, y.w), accumulate);
+             },
+             [&](size_t idx) { store1<float>(gb + idx, one(pb[idx], tb[idx]), accumulate); });
 }
 
 // grid (G, B).  g_c = d L / d s_c = kp[c] * s_c^(pw-1) - kt[c] * t_c with the class weight and the upstream weight folded into kp, kt
@@ -270,7 +235,7 @@ __global__ __launch_bounds__(256) void dice_softmax_bwd_kernel(const float* __re
     const int b = blockIdx.y;
     if ((int)threadIdx.x < C) {
         const int c = threadIdx.x;
-        const double g = upstream(b, B, reduction, gscale, gscale_dev, gout) * class_weight(c, C, ignore_index, weight);
+        const double g = upstream_b(b, B, reduction, gscale, gscale_dev, gout) * class_weight(c, C, ignore_index, weight);
         const double num = coef[2 * ((size_t)b * C + c)], den = coef[2 * ((size_t)b * C + c) + 1];
         kt[c] = (float)(g / den);
         kp[c] = (float)(g * num * (double)pw / (den * den));
@@ -307,15 +272,9 @@ __global__ __launch_bounds__(256) void dice_softmax_bwd_kernel(const float* __re
     }
 }
 
-inline int dice_parts(size_t per_sample) {
-    const size_t g = (per_sample + 4095) / 4096;
-    return (int)(g > 64 ? 64 : (g < 1 ? 1 : g));
-}
+inline int dice_parts(size_t per_sample) { return wm_groups(per_sample, 4096, 64); }
 // workgroups per sample of an elementwise pass with `unit` elements per workgroup and iteration
-inline int bwd_groups(size_t per_sample, size_t unit) {
-    const size_t g = (per_sample + unit - 1) / unit;
-    return (int)(g > 256 ? 256 : (g < 1 ? 1 : g));
-}
+inline int bwd_groups(size_t per_sample, size_t unit) { return wm_groups(per_sample, unit, 256); }
 inline bool planes_vec(const void* a, const void* b, const void* c, size_t HW) {
     return HW % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }

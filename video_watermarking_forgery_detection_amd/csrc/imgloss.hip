@@ -15,6 +15,7 @@
 // FIRST pixel lies in its tile: tile origins are multiples of 4, so a pooled pixel of any level belongs to exactly one tile, and the second
 // pixel of a difference is at most 4 level-0 pixels further.  Pooled images and difference maps exist in LDS only.
 #include "wm_common.h"
+#include "wm_reduce.h"
 
 namespace {
 
@@ -22,41 +23,6 @@ constexpr int L2 = WM_RECON_L2, LCHAR = WM_RECON_LCHAR, L1 = WM_RECON_L1;
 constexpr int TH = 16, TW = 32;        // the exclusion tile (level-0 pixels)
 constexpr int HALO = 4;                // = one pixel of level 2
 constexpr int MAXC = 4, MAXL = 3, MAXSLOTS = MAXL * 2 * MAXC * MAXC;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// 256 threads -> the sum in thread 0 (fixed order); s: 4 doubles of LDS
-__device__ __forceinline__ double block_sum_f64(double v, double* s) {
-    v = wave_sum_f64(v);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s[0] + s[1]) + (s[2] + s[3]);
-}
-
-// One sample's [0, per) split for 16-byte access, as csrc/dice.hip: a scalar head up to the first 16-byte boundary of `a`, nv float4s, a
-// scalar tail; the other pointers share the split only when they reach a boundary at the same element (otherwise everything is scalar)
-struct Split { size_t head, nv, tail0; };
-__device__ __forceinline__ Split split16(const void* a, const void* b, const void* c, size_t per) {
-    Split s;
-    s.head = ((16 - ((uintptr_t)a & 15)) & 15) >> 2;
-    if (s.head > per) s.head = per;
-    const bool same = (((uintptr_t)a ^ (uintptr_t)b) & 15) == 0 && (c == nullptr || (((uintptr_t)a ^ (uintptr_t)c) & 15) == 0);
-    s.nv = same ? (per - s.head) / 4 : 0;
-    if (s.nv == 0) s.head = 0;
-    s.tail0 = s.head + s.nv * 4;
-    return s;
-}
-
-// the upstream weight of a scalar loss: gscale * gscale_dev[0] * gout[0]
-__device__ __forceinline__ double upstream(float gscale, const float* __restrict__ gscale_dev, const float* __restrict__ gout) {
-    double g = (double)gscale;
-    if (gscale_dev) g *= (double)gscale_dev[0];
-    if (gout) g *= (double)gout[0];
-    return g;
-}
 
 // ------------------------------------------------------------------------------------------------ reconstruction
 template <int KIND> __device__ __forceinline__ double recon_f(float x, float t, double eps) {
@@ -79,31 +45,17 @@ __global__ __launch_bounds__(256) void recon_sums_kernel(const float* __restrict
                                                          double* __restrict__ partials) {
     const float* xb = x + (size_t)blockIdx.y * per;
     const float* tb = t + (size_t)blockIdx.y * per;
-    const Split sp = split16(xb, tb, nullptr, per);
-    const size_t stride = (size_t)gridDim.x * 256, first = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const Split sp = split16(per, xb, tb);
     double a = 0.0;
-    for (size_t v = first; v < sp.nv; v += stride) {
-        const float4 p = *reinterpret_cast<const float4*>(xb + sp.head + 4 * v);
-        const float4 q = *reinterpret_cast<const float4*>(tb + sp.head + 4 * v);
-        a += recon_f<KIND>(p.x, q.x, eps); a += recon_f<KIND>(p.y, q.y, eps); a += recon_f<KIND>(p.z, q.z, eps); a += recon_f<KIND>(p.w, q.w, eps);
-    }
-    const size_t nscalar = sp.head + (per - sp.tail0);
-    for (size_t i = first; i < nscalar; i += stride) {
-        const size_t idx = i < sp.head ? i : sp.tail0 + (i - sp.head);
-        a += recon_f<KIND>(xb[idx], tb[idx], eps);
-    }
+    stream16(sp, per,
+             [&](size_t at) {
+                 const float4 p = ld16(xb + at), q = ld16(tb + at);
+                 a += recon_f<KIND>(p.x, q.x, eps); a += recon_f<KIND>(p.y, q.y, eps); a += recon_f<KIND>(p.z, q.z, eps); a += recon_f<KIND>(p.w, q.w, eps);
+             },
+             [&](size_t idx) { a += recon_f<KIND>(xb[idx], tb[idx], eps); });
     __shared__ double s[4];
     a = block_sum_f64(a, s);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = a;
-}
-
-// one workgroup: out[0] = scale * sum of the n partials (thread i adds partials i, i+256, ...; then the fixed tree)
-__global__ __launch_bounds__(256) void sum_finalize_kernel(const double* __restrict__ partials, size_t n, double scale, float* __restrict__ out) {
-    __shared__ double s[4];
-    double a = 0.0;
-    for (size_t i = threadIdx.x; i < n; i += 256) a += partials[i];
-    a = block_sum_f64(a, s);
-    if (threadIdx.x == 0) out[0] = (float)(a * scale);
 }
 
 // grid (G, B): grad (+)= g / B * f'(x - t)
@@ -115,33 +67,18 @@ __global__ __launch_bounds__(256) void recon_bwd_kernel(const float* __restrict_
     const float* xb = x + (size_t)blockIdx.y * per;
     const float* tb = t + (size_t)blockIdx.y * per;
     float* gb = grad + (size_t)blockIdx.y * per;
-    const Split sp = split16(xb, tb, gb, per);
-    const size_t stride = (size_t)gridDim.x * 256, first = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (size_t v = first; v < sp.nv; v += stride) {
-        const float4 p = *reinterpret_cast<const float4*>(xb + sp.head + 4 * v);
-        const float4 q = *reinterpret_cast<const float4*>(tb + sp.head + 4 * v);
-        float4* o = reinterpret_cast<float4*>(gb + sp.head + 4 * v);
-        float4 r = make_float4(recon_df<KIND>(p.x, q.x, eps, k), recon_df<KIND>(p.y, q.y, eps, k), recon_df<KIND>(p.z, q.z, eps, k),
-                               recon_df<KIND>(p.w, q.w, eps, k));
-        if (accumulate) { const float4 old = *o; r.x += old.x; r.y += old.y; r.z += old.z; r.w += old.w; }
-        *o = r;
-    }
-    const size_t nscalar = sp.head + (per - sp.tail0);
-    for (size_t i = first; i < nscalar; i += stride) {
-        const size_t idx = i < sp.head ? i : sp.tail0 + (i - sp.head);
-        const float r = recon_df<KIND>(xb[idx], tb[idx], eps, k);
-        gb[idx] = accumulate ? gb[idx] + r : r;
-    }
+    const Split sp = split16(per, xb, tb, gb);
+    stream16(sp, per,
+             [&](size_t at) {
+                 const float4 p = ld16(xb + at), q = ld16(tb + at);
+                 store4<float>(gb + at, recon_df<KIND>(p.x, q.x, eps, k), recon_df<KIND>(p.y, q.y, eps, k), recon_df<KIND>(p.z, q.z, eps, k),
+                               recon_df<KIND>(p.w, q.w, eps, k), accumulate);
+             },
+             [&](size_t idx) { store1<float>(gb + idx, recon_df<KIND>(xb[idx], tb[idx], eps, k), accumulate); });
 }
 
-inline int stream_parts(size_t per_sample) {
-    const size_t g = (per_sample + 4095) / 4096;
-    return (int)(g > 64 ? 64 : (g < 1 ? 1 : g));
-}
-inline int bwd_groups(size_t per_sample) {
-    const size_t g = (per_sample + 1023) / 1024;
-    return (int)(g > 256 ? 256 : (g < 1 ? 1 : g));
-}
+inline int stream_parts(size_t per_sample) { return wm_groups(per_sample, 4096, 64); }
+inline int bwd_groups(size_t per_sample) { return wm_groups(per_sample, 1024, 256); }
 inline bool kind_ok(int k) { return k == L2 || k == LCHAR || k == L1; }
 
 // ------------------------------------------------------------------------------------------------ gradient loss
@@ -493,8 +430,7 @@ extern "C" int wm_recon_sums(const float* x, const float* target, int B, size_t 
 
 extern "C" int wm_recon_finalize(const double* partials, int B, size_t per_sample, float* loss_out, void* stream) {
     WM_REQUIRE(partials && loss_out && B > 0 && per_sample > 0, WM_E_BADARG, "wm_recon_finalize: bad arguments");
-    hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (size_t)B * stream_parts(per_sample),
-                       1.0 / (double)B, loss_out);
+    wm_sum_finalize(partials, (size_t)B * stream_parts(per_sample), 1.0 / (double)B, loss_out, (hipStream_t)stream);
     WM_LAUNCH_CHECK("wm_recon_finalize");
     return WM_OK;
 }

@@ -17,6 +17,7 @@
 //   grad = g * (w*Dp + 2x . w*Dq + y . w*Dr)
 // with g the upstream weight of the pixel's image (constant per image, so it multiplies after the convolution).  44,928 B of LDS.
 #include "wm_common.h"
+#include "wm_reduce.h"
 
 namespace {
 
@@ -120,12 +121,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        partials[((size_t)n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    sum = block_sum_f64(sum, red);
+    if (threadIdx.x == 0) partials[((size_t)n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = sum;
 }
 
 // block b < B: out[1 + b] = mean of image b (its per_image partials are contiguous); block B: out[0] = mean of everything

@@ -21,31 +21,11 @@
 #include "wm_common.h"
 
 #pragma clang fp contract(off)   // x = y must give n == d bit for bit: the two sides are the same operations only while none is fused
+#include "wm_reduce.h"          // (below the pragma: it holds for the shared helpers as well)
 
 namespace {
 
 constexpr int TW = 64, TH = 16;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// 256 threads -> the sum in thread 0 (fixed order); s: 4 doubles of LDS
-__device__ __forceinline__ double block_sum_f64(double v, double* s) {
-    v = wave_sum_f64(v);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s[0] + s[1]) + (s[2] + s[3]);
-}
-
-// the upstream weight of a loss: gscale * gscale_dev[0] * gout[0]
-__device__ __forceinline__ double upstream(float gscale, const float* __restrict__ gscale_dev, const float* __restrict__ gout) {
-    double g = (double)gscale;
-    if (gscale_dev) g *= (double)gscale_dev[0];
-    if (gout) g *= (double)gout[0];
-    return g;
-}
 
 // ------------------------------------------------------------------------------------------------ SSIM_Loss
 // ReflectionPad2d(1): padded index -1 -> 1, n -> n - 2 (n >= 2); only called for -1 <= i <= n
@@ -118,15 +98,6 @@ __global__ __launch_bounds__(256) void ssim3_fwd_kernel(const float* __restrict_
         sum = block_sum_f64(sum, red);
         if (threadIdx.x == 0) partials[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = sum;
     }
-}
-
-// one workgroup: out[0] = scale * sum of the n partials (thread i adds partials i, i+256, ...; then the fixed tree)
-__global__ __launch_bounds__(256) void sum_finalize_kernel(const double* __restrict__ partials, size_t n, double scale, float* __restrict__ out) {
-    __shared__ double s[4];
-    double a = 0.0;
-    for (size_t i = threadIdx.x; i < n; i += 256) a += partials[i];
-    a = block_sum_f64(a, s);
-    if (threadIdx.x == 0) out[0] = (float)(a * scale);
 }
 
 // grid (tiles_x, tiles_y, N).  g != NULL: the upstream map, times the scalar weight; g == NULL: the mean's weight, scalar * (1 / count)
@@ -204,20 +175,6 @@ inline dim3 ssim3_grid(int N, int H, int W) { return dim3(wm_cdiv(W, TW), wm_cdi
 // ------------------------------------------------------------------------------------------------ the three reductions
 constexpr int MASKL1 = WM_PIXLOSS_MASKL1, NONBLURRY = WM_PIXLOSS_NONBLURRY, GRAY = WM_PIXLOSS_GRAY;
 
-// [0, n) split for 16-byte access, as csrc/imgloss.hip: a scalar head up to the first 16-byte boundary of `a`, nv float4s, a scalar tail;
-// the other pointers (NULL = absent) share the split only when they reach a boundary at the same element (otherwise everything is scalar)
-struct Split { size_t head, nv, tail0; };
-__device__ __forceinline__ bool same16(const void* a, const void* b) { return b == nullptr || (((uintptr_t)a ^ (uintptr_t)b) & 15) == 0; }
-__device__ __forceinline__ Split split16(const void* a, const void* b, const void* c, const void* d, const void* e, size_t n) {
-    Split s;
-    s.head = ((16 - ((uintptr_t)a & 15)) & 15) >> 2;
-    if (s.head > n) s.head = n;
-    s.nv = same16(a, b) && same16(a, c) && same16(a, d) && same16(a, e) ? (n - s.head) / 4 : 0;
-    if (s.nv == 0) s.head = 0;
-    s.tail0 = s.head + s.nv * 4;
-    return s;
-}
-
 __device__ __forceinline__ int sgn(double d) { return (d > 0.0) - (d < 0.0); }   // 0 at 0, as torch's abs / L1 backward
 
 // one element's terms: s0 += |m a - m b| (the two products are exact in double, their difference is rounded once), s1 += |m|;  or s0 += (x - 1/2)^2;  or s0 += |x - 1/2|
@@ -230,21 +187,17 @@ template <int KIND> __device__ __forceinline__ void pix_acc(float a, float b, fl
 template <int KIND>
 __global__ __launch_bounds__(256) void pix_sums_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ m, size_t n,
                                                        double* __restrict__ partials) {
-    const Split sp = split16(a, b, m, nullptr, nullptr, n);
-    const size_t stride = (size_t)gridDim.x * 256, first = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const Split sp = split16(n, a, b, m);
     double s0 = 0.0, s1 = 0.0;
-    for (size_t v = first; v < sp.nv; v += stride) {
-        const float4 p = *reinterpret_cast<const float4*>(a + sp.head + 4 * v);
-        float4 q = p, w = p;
-        if (KIND == MASKL1) { q = *reinterpret_cast<const float4*>(b + sp.head + 4 * v); w = *reinterpret_cast<const float4*>(m + sp.head + 4 * v); }
-        pix_acc<KIND>(p.x, q.x, w.x, s0, s1); pix_acc<KIND>(p.y, q.y, w.y, s0, s1);
-        pix_acc<KIND>(p.z, q.z, w.z, s0, s1); pix_acc<KIND>(p.w, q.w, w.w, s0, s1);
-    }
-    const size_t nscalar = sp.head + (n - sp.tail0);
-    for (size_t i = first; i < nscalar; i += stride) {
-        const size_t idx = i < sp.head ? i : sp.tail0 + (i - sp.head);
-        pix_acc<KIND>(a[idx], KIND == MASKL1 ? b[idx] : 0.f, KIND == MASKL1 ? m[idx] : 0.f, s0, s1);
-    }
+    stream16(sp, n,
+             [&](size_t at) {
+                 const float4 p = ld16(a + at);
+                 float4 q = p, w = p;
+                 if (KIND == MASKL1) { q = ld16(b + at); w = ld16(m + at); }
+                 pix_acc<KIND>(p.x, q.x, w.x, s0, s1); pix_acc<KIND>(p.y, q.y, w.y, s0, s1);
+                 pix_acc<KIND>(p.z, q.z, w.z, s0, s1); pix_acc<KIND>(p.w, q.w, w.w, s0, s1);
+             },
+             [&](size_t idx) { pix_acc<KIND>(a[idx], KIND == MASKL1 ? b[idx] : 0.f, KIND == MASKL1 ? m[idx] : 0.f, s0, s1); });
     __shared__ double s[2][4];
     s0 = block_sum_f64(s0, s[0]);
     s1 = block_sum_f64(s1, s[1]);
@@ -282,43 +235,26 @@ __global__ __launch_bounds__(256) void pix_bwd_kernel(const float* __restrict__ 
                                                       int accumulate) {
     const double g = upstream(gscale, gscale_dev, gout);
     const double k = KIND == MASKL1 ? g / ((double)n * coef[1]) : (KIND == NONBLURRY ? -2.0 * g / (double)n : -g / ((double)n * coef[0] * coef[0]));
-    const Split sp = split16(a, b, m, ga, gb, n);
-    const size_t stride = (size_t)gridDim.x * 256, first = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (size_t v = first; v < sp.nv; v += stride) {
-        const size_t at = sp.head + 4 * v;
-        const float4 p = *reinterpret_cast<const float4*>(a + at);
-        float4 q = p, w = p;
-        if (KIND == MASKL1) { q = *reinterpret_cast<const float4*>(b + at); w = *reinterpret_cast<const float4*>(m + at); }
-        const float4 r = make_float4(pix_d<KIND>(p.x, q.x, w.x, k), pix_d<KIND>(p.y, q.y, w.y, k), pix_d<KIND>(p.z, q.z, w.z, k),
-                                     pix_d<KIND>(p.w, q.w, w.w, k));
-        if (ga) {
-            float4 t = r;
-            if (accumulate) { const float4 old = *reinterpret_cast<const float4*>(ga + at); t.x += old.x; t.y += old.y; t.z += old.z; t.w += old.w; }
-            *reinterpret_cast<float4*>(ga + at) = t;
-        }
-        if (gb) {
-            float4 t = make_float4(-r.x, -r.y, -r.z, -r.w);
-            if (accumulate) { const float4 old = *reinterpret_cast<const float4*>(gb + at); t.x += old.x; t.y += old.y; t.z += old.z; t.w += old.w; }
-            *reinterpret_cast<float4*>(gb + at) = t;
-        }
-    }
-    const size_t nscalar = sp.head + (n - sp.tail0);
-    for (size_t i = first; i < nscalar; i += stride) {
-        const size_t idx = i < sp.head ? i : sp.tail0 + (i - sp.head);
-        const float r = pix_d<KIND>(a[idx], KIND == MASKL1 ? b[idx] : 0.f, KIND == MASKL1 ? m[idx] : 0.f, k);
-        if (ga) ga[idx] = accumulate ? ga[idx] + r : r;
-        if (gb) gb[idx] = accumulate ? gb[idx] - r : -r;
-    }
+    const Split sp = split16(n, a, b, m, ga, gb);
+    stream16(sp, n,
+             [&](size_t at) {
+                 const float4 p = ld16(a + at);
+                 float4 q = p, w = p;
+                 if (KIND == MASKL1) { q = ld16(b + at); w = ld16(m + at); }
+                 const float4 r = make_float4(pix_d<KIND>(p.x, q.x, w.x, k), pix_d<KIND>(p.y, q.y, w.y, k), pix_d<KIND>(p.z, q.z, w.z, k),
+                                              pix_d<KIND>(p.w, q.w, w.w, k));
+                 if (ga) store4<float>(ga + at, r.x, r.y, r.z, r.w, accumulate);
+                 if (gb) store4<float>(gb + at, -r.x, -r.y, -r.z, -r.w, accumulate);
+             },
+             [&](size_t idx) {
+                 const float r = pix_d<KIND>(a[idx], KIND == MASKL1 ? b[idx] : 0.f, KIND == MASKL1 ? m[idx] : 0.f, k);
+                 if (ga) store1<float>(ga + idx, r, accumulate);
+                 if (gb) store1<float>(gb + idx, -r, accumulate);
+             });
 }
 
-inline int pix_parts(size_t n) {
-    const size_t g = (n + 4095) / 4096;
-    return (int)(g > 256 ? 256 : (g < 1 ? 1 : g));
-}
-inline int pix_bwd_groups(size_t n) {
-    const size_t g = (n + 1023) / 1024;
-    return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
-}
+inline int pix_parts(size_t n) { return wm_groups(n, 4096, 256); }
+inline int pix_bwd_groups(size_t n) { return wm_groups(n, 1024, 2048); }
 inline bool pix_kind_ok(int k) { return k == MASKL1 || k == NONBLURRY || k == GRAY; }
 
 }  // namespace
@@ -346,8 +282,7 @@ extern "C" int wm_ssim3_fwd(const float* x, const float* y, float* out_map, doub
 
 extern "C" int wm_ssim3_finalize(const double* partials, int N, int H, int W, float* loss_out, void* stream) {
     WM_REQUIRE(partials && loss_out && ssim3_dims_ok(N, H, W), WM_E_BADARG, "wm_ssim3_finalize: bad arguments");
-    hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (size_t)wm_ssim3_nparts(N, H, W),
-                       1.0 / ((double)N * H * W), loss_out);
+    wm_sum_finalize(partials, (size_t)wm_ssim3_nparts(N, H, W), 1.0 / ((double)N * H * W), loss_out, (hipStream_t)stream);
     WM_LAUNCH_CHECK("wm_ssim3_finalize");
     return WM_OK;
 }

@@ -1799,17 +1799,10 @@ def ssim_bwd(dplanes, a, b, gout=None, per_image=False, gscale=1.0, gscale_dev=N
     f32, one element (the mean's upstream gradient) or [B] with per_image (size_average=False); None = 1.  out: the buffer to write, or
     with accumulate to add into (one launch, no axpy)"""
     a, b = _ssim_args(a, b)
-    _need_cuda(dplanes, gout, gscale_dev, out)
+    _need_cuda(dplanes)
     B, C, H, W = a.shape
     assert dplanes.shape == (3,) + tuple(a.shape) and dplanes.is_contiguous() and dplanes.dtype == torch.float32
-    if gout is not None:
-        gout = gout.contiguous()
-        assert gout.dtype == torch.float32 and gout.numel() == (B if per_image else 1)
-    if out is None:
-        if accumulate:
-            raise ValueError("ssim_bwd: accumulate needs the buffer to add into (out=)")
-        out = torch.empty_like(a)
-    assert out.shape == a.shape and out.is_contiguous() and out.dtype == torch.float32
+    gout, out = _loss_bwd_args("ssim_bwd", a, gout, gscale_dev, out, accumulate, B if per_image else 1)
     rc = _timed("ssim_bwd", None, lambda: _lib.lib().wm_ssim_bwd(_p(dplanes), _p(a), _p(b), _p(out), B, C, H, W, ssim_window(), _p(gout),
                                                                  1 if per_image else 0, gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
     _lib.check(rc, "wm_ssim_bwd")
@@ -1865,6 +1858,21 @@ def scale_dev_(x, scale_dev):
     return x
 
 
+def _loss_bwd_args(name, x, gout, gscale_dev, out, accumulate, n_gout=1, same_shape=True):
+    """(gout contiguous, the gradient buffer) of a loss backward.  n_gout: the elements gout must have; same_shape: a given buffer must have
+    x's shape (False: x's size -- the Dice backwards take any view of it)"""
+    _need_cuda(gout, gscale_dev, out)
+    if gout is not None:
+        gout = gout.contiguous()
+        assert gout.dtype == torch.float32 and gout.numel() == n_gout
+    if out is None:
+        if accumulate:
+            raise ValueError(name + ": accumulate needs the buffer to add into (out=)")
+        out = torch.empty_like(x)
+    assert (out.shape == x.shape if same_shape else out.numel() == x.numel()) and out.is_contiguous() and out.dtype == torch.float32
+    return gout, out
+
+
 # ----------------------------------------------------------------------------- Dice loss (csrc/dice.hip)
 DICE_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}    # WM_DICE_MEAN / WM_DICE_SUM / WM_DICE_NONE
 
@@ -1892,19 +1900,6 @@ def _dice_finalize(L, part, B, C, per, smooth, red, ignore_index, weight, device
     return loss, coef
 
 
-def _dice_bwd_args(name, x, gout, B, red, gscale_dev, out, accumulate):
-    _need_cuda(gout, gscale_dev, out)
-    if gout is not None:
-        gout = gout.contiguous()
-        assert gout.dtype == torch.float32 and gout.numel() == (B if red == DICE_REDUCTIONS["none"] else 1)
-    if out is None:
-        if accumulate:
-            raise ValueError(name + ": accumulate needs the buffer to add into (out=)")
-        out = torch.empty_like(x)
-    assert out.numel() == x.numel() and out.is_contiguous() and out.dtype == torch.float32
-    return gout, out
-
-
 def dice_binary_fwd(p, target, smooth=1.0, pw=2.0, reduction="mean"):
     """BinaryDiceLoss(smooth, pw, reduction)(p, target) for float32 [B, ...] tensors -> (loss, coef): loss a [1] device tensor (mean, sum) or
     [B] (none); coef [B,2] float64 = (num, den) per sample, what dice_binary_bwd reads.  Two launches, no host sync"""
@@ -1929,7 +1924,7 @@ def dice_binary_bwd(p, target, coef, pw=2.0, reduction="mean", gout=None, gscale
     red = _dice_reduction(reduction)
     p, target = _dice_pair("dice_binary_bwd", p, target)
     B = p.shape[0]
-    gout, out = _dice_bwd_args("dice_binary_bwd", p, gout, B, red, gscale_dev, out, accumulate)
+    gout, out = _loss_bwd_args("dice_binary_bwd", p, gout, gscale_dev, out, accumulate, B if red == DICE_REDUCTIONS["none"] else 1, same_shape=False)
     rc = _timed("dice_bwd", None, lambda: _lib.lib().wm_dice_bwd(_p(p), _p(target), _p(coef), _p(out), B, p.numel() // B, float(pw), red, _p(gout),
                                                                  gscale, _p(gscale_dev), 1 if chain_sigmoid else 0, 1 if accumulate else 0, _stream()))
     _lib.check(rc, "wm_dice_bwd")
@@ -1975,7 +1970,7 @@ def dice_softmax_bwd(logits, target, coef, pw=2.0, reduction="mean", ignore_inde
     """gradient wrt the logits of gscale * gscale_dev[0] * sum(gout * loss), from the coef dice_softmax_fwd wrote (same ignore_index, weight)"""
     red = _dice_reduction(reduction)
     logits, target, weight, B, C, HW = _dice_softmax_args(logits, target, weight)
-    gout, out = _dice_bwd_args("dice_softmax_bwd", logits, gout, B, red, gscale_dev, out, accumulate)
+    gout, out = _loss_bwd_args("dice_softmax_bwd", logits, gout, gscale_dev, out, accumulate, B if red == DICE_REDUCTIONS["none"] else 1, same_shape=False)
     rc = _timed("dice_softmax_bwd", None, lambda: _lib.lib().wm_dice_softmax_bwd(
         _p(logits), _p(target), _p(coef), _p(out), B, C, HW, float(pw), red, -1 if ignore_index is None else int(ignore_index), _p(weight), _p(gout),
         gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
@@ -2002,19 +1997,6 @@ def _f32_cuda(name, *ts):
     for t in ts:
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
             raise TypeError(name + ": contiguous float32 tensors expected")
-
-
-def _loss_bwd_args(name, x, gout, gscale_dev, out, accumulate):
-    _need_cuda(gout, gscale_dev, out)
-    if gout is not None:
-        gout = gout.contiguous()
-        assert gout.dtype == torch.float32 and gout.numel() == 1
-    if out is None:
-        if accumulate:
-            raise ValueError(name + ": accumulate needs the buffer to add into (out=)")
-        out = torch.empty_like(x)
-    assert out.shape == x.shape and out.is_contiguous() and out.dtype == torch.float32
-    return gout, out
 
 
 def _recon_args(name, x, t, kind):
