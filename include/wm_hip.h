@@ -577,6 +577,8 @@ int wm_scale_dev(float* x, size_t n, const float* scale_dev, void* stream);
  * wm_gconv_wgrad: dw [Cout][Cin][KH][KW] (+)= sum_pixels dout x in; dbias [Cout] (+)= column sums of dout (may be NULL);
  *                 partial = f32 scratch of wm_gconv_wgrad_scratch_floats(..) floats.  IH/IW/KC describe `in`, OH/OW/NC `dout`.
  * wm_gcolsum    : out [Creal] (+)= column sums of x [npix][C]; scratch: wm_gcolsum_scratch_floats(npix, C) floats.
+ * wm_gcolsum_f64: the same sums accumulated in double in a fixed order and rounded to f32 once (no scratch): the bias gradient of a
+ *                 network's output convolution, a sum over every pixel of the loss gradient.
  * wm_unary_fwd / _bwd: kind 0 ReLU, 1 LeakyReLU(0.2), 2 GELU (erf), 3 ELU, 4 Sigmoid, 5 Tanh; the backward reads the INPUT x --
  *                 except kind 6 (backward only): the ELU derivative from the layer's OUTPUT, out > 0 ? 1 : out + 1 (wm_conv3x3_fwd_elu keeps no input).
  * wm_add_scaled : out = a + alpha * b.
@@ -591,7 +593,18 @@ int wm_scale_dev(float* x, size_t n, const float* scale_dev, void* stream);
  *                 in place (eps 1e-12); sigma = u.(W v); Wsn = W / sigma; scratch: wm_spectral_norm_scratch_floats(M, N) floats.
  *                 wm_spectral_norm_bwd: gW (+)= (G - <G,Wsn> u v^T)/sigma
  *                 (u, v detached, as torch computes them under no_grad); partial = f32[256] scratch.
- * wm_bayar_constrain: every 5x5 filter of w [nfilters][25] in place: centre := 0, filter /= its sum, centre := -1. */
+ * wm_bayar_constrain: every 5x5 filter of w [nfilters][25] in place: centre := 0, filter *= 1 / its sum, centre := -1; the sum is
+ *                 a left-to-right f32 sum of the 25 taps, a zero sum gives inf / nan as in the reference.
+ *                 wm_bayar_constrain_torch_order (networks.py:1059-1061): the same with the f32 sum in the order torch.sum over the
+ *                 last two axes takes on the CPU, l_j = (x[j] + x[j+8]) + x[j+16] for j < 8, then x[24] + l_0 + ... + l_7: the reference's
+ *                 float32 result bit for bit.
+ * wm_gconv_dil_fwd / wm_gconv_dil_wgrad: wm_gconv_fwd / wm_gconv_wgrad with a dilation `dil` (1..8; dil > 1 needs stride 1, else
+ *                 WM_E_BADARG): forward source pixel oy*stride - pad + ky*dil, input-gradient source pixel oy + pad - ky*dil
+ *                 (networks.py:1387-1421 ResnetBlock).  Same packed filters, same scratch (wm_gconv_wgrad_scratch_floats); with dil > 1 the
+ *                 output grid must be the one the geometry gives.  dil = 1 is wm_gconv_fwd / wm_gconv_wgrad bit for bit.
+ * wm_reflect_pad_fwd / _bwd: nn.ReflectionPad2d(pad) on x [B,H,W,CP] -> out [B,H+2pad,W+2pad,CP] (pad <= min(H,W) - 1, else
+ *                 WM_E_SHAPE) and its adjoint g [B,H+2pad,W+2pad,CP] -> gx [B,H,W,CP]; both gather 16-byte channel vectors, the adjoint
+ *                 adds its <= 9 terms in f32 in a fixed order (no atomics). */
 int wm_gconv_pack(const float* w, void* wp, int Cout, int Cin, int KH, int KW, int RP, int CP, int transpose, int dtype, void* stream);
 int wm_gconv_fwd(const void* in, const void* w, const float* bias, void* out, int B, int IH, int IW, int KC, int OH, int OW, int NC,
                  int KH, int KW, int stride, int pad, int dgrad, int dtype, void* stream);
@@ -601,6 +614,7 @@ int wm_gconv_wgrad(const void* dout, const void* in, float* partial, float* dw, 
 size_t wm_gconv_wgrad_scratch_floats(int B, int OH, int OW, int KC, int NC, int KH, int KW);
 size_t wm_gcolsum_scratch_floats(size_t npix, int C);
 int wm_gcolsum(const void* x, size_t npix, int C, float* out, int Creal, int accumulate, float* scratch, int dtype, void* stream);
+int wm_gcolsum_f64(const void* x, size_t npix, int C, float* out, int Creal, int accumulate, int dtype, void* stream);
 int wm_unary_fwd(const void* x, void* y, size_t n, int kind, int dtype, void* stream);
 int wm_unary_bwd(const void* x, const void* gy, void* gx, size_t n, int kind, int dtype, void* stream);
 /* gx = gy * act'(x) over x [npix][C] AND out [Creal] (+)= the column sums of gx as stored -- the bias gradient of the nn.Conv2d whose
@@ -628,6 +642,13 @@ int wm_spectral_norm_fwd(const float* W, float* u, float* v, float* sigma, float
 int wm_spectral_norm_bwd(const float* G, const float* Wsn, const float* u, const float* v, const float* sigma, float* partial,
                          float* gW, int M, int N, int accumulate, void* stream);
 int wm_bayar_constrain(float* w, int nfilters, void* stream);
+int wm_bayar_constrain_torch_order(float* w, int nfilters, void* stream);
+int wm_gconv_dil_fwd(const void* in, const void* w, const float* bias, void* out, int B, int IH, int IW, int KC, int OH, int OW, int NC,
+                     int KH, int KW, int stride, int pad, int dil, int dgrad, int dtype, void* stream);
+int wm_gconv_dil_wgrad(const void* dout, const void* in, float* partial, float* dw, float* dbias, int accumulate, int B, int IH, int IW,
+                       int KC, int OH, int OW, int NC, int KH, int KW, int stride, int pad, int dil, int Cout, int Cin, int dtype, void* stream);
+int wm_reflect_pad_fwd(const void* x, void* out, int B, int H, int W, int CP, int pad, int dtype, void* stream);
+int wm_reflect_pad_bwd(const void* g, void* gx, int B, int H, int W, int CP, int pad, int dtype, void* stream);
 
 /* ------------------------------------------------------------------ invertible embedder pieces
  * replaces, for models/invertible_net.py: HaarDownsampling / HaarUpsampling (:178-292: F.conv2d / F.conv_transpose2d with the fixed

@@ -1,6 +1,8 @@
 // General convolution family for the networks either side of the HiDDeN path (models/networks.py:631-749
 // Discriminator, models/conditional_jpeg_generator.py:185-374 FBCNN, :697-826 QF_predictor): any kernel size up to 5x5, stride 1 or 2,
 // zero padding, bias; forward, input gradient (also = ConvTranspose2d forward) and weight gradient, NHWC, f32 / bf16 / f16.
+// The wm_gconv_dil_* entry points add a dilation (stride 1 only: networks.py:1387-1421 ResnetBlock's 3x3 dilation-2 convolution on a
+// reflection-padded input): tap (ky, kx) reads the source pixel ky * dil, kx * dil away; the wm_gconv_* ones run the same code with 1.
 //
 // These layers are outside the benchmarked step, so the kernels are DIRECT implicit GEMMs on MFMA without an LDS stage: a wave owns 16
 // output pixels x 64 output channels; per filter tap and 32-channel chunk every lane loads its 16 bytes of the pixel fragment and of the
@@ -13,6 +15,7 @@
 //   wgrad   : dw[tap][n][k] = sum_{b,oy,ox} dout[b,oy,ox,n] * in[b, oy*s - p + ky, ox*s - p + kx, k], pixels as the MFMA K dimension
 #include <algorithm>
 #include "wm_common.h"
+#include "wm_reduce.h"
 
 namespace {
 
@@ -22,18 +25,18 @@ struct GArgs {
     const void* in; const void* w; const float* bias; void* out;
     int B, IH, IW, KC;     // input tensor [B,IH,IW,KC] (KC = its channel stride)
     int OH, OW, NC;        // output tensor [B,OH,OW,NC]
-    int KH, KW, stride, pad;
+    int KH, KW, stride, pad, dil;
     int dgrad;             // 0: forward geometry, 1: transposed geometry (in = dout [B,IH,IW,KC] of the forward conv whose INPUT is `out`)
 };
 
 // source pixel of output pixel (oy, ox) for tap (ky, kx); returns false if it contributes nothing
 __device__ __forceinline__ bool src_of(const GArgs& a, int oy, int ox, int ky, int kx, int& sy, int& sx) {
     if (!a.dgrad) {
-        sy = oy * a.stride - a.pad + ky;
-        sx = ox * a.stride - a.pad + kx;
+        sy = oy * a.stride - a.pad + ky * a.dil;
+        sx = ox * a.stride - a.pad + kx * a.dil;
         return sy >= 0 && sy < a.IH && sx >= 0 && sx < a.IW;
     }
-    const int ty = oy + a.pad - ky, tx = ox + a.pad - kx;
+    const int ty = oy + a.pad - ky * a.dil, tx = ox + a.pad - kx * a.dil;
     if (ty < 0 || tx < 0) return false;
     if (a.stride == 2) {
         if ((ty | tx) & 1) return false;
@@ -166,7 +169,7 @@ __global__ __launch_bounds__(256) void gconv_kernel(GArgs a) {
 // interleaved 32-pixel (f32: 4-pixel) steps of the split and are summed through LDS.  partial: [nsplit][taps][NC][KC] f32.
 struct GWArgs {
     const void* dout; const void* in; float* partial;
-    int B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, nsplit;
+    int B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, dil, nsplit;
 };
 template <typename T> struct GLd { static __device__ __forceinline__ float f(const T* p) { return to_f32(*p); } };
 
@@ -197,7 +200,7 @@ __global__ __launch_bounds__(256) void gconv_wgrad_kernel(GWArgs a) {
             if (pix < p1) {
                 av[e] = to_f32(dout[pix * a.NC + n]);
                 const int ox = (int)(pix % a.OW), oy = (int)((pix / a.OW) % a.OH), b = (int)(pix / ((size_t)a.OW * a.OH));
-                const int sy = oy * a.stride - a.pad + ky, sx = ox * a.stride - a.pad + kx;
+                const int sy = oy * a.stride - a.pad + ky * a.dil, sx = ox * a.stride - a.pad + kx * a.dil;
                 if (kok && sy >= 0 && sy < a.IH && sx >= 0 && sx < a.IW) bv[e] = to_f32(in[(((size_t)b * a.IH + sy) * a.IW + sx) * a.KC + k]);
             }
         }
@@ -300,7 +303,7 @@ __global__ __launch_bounds__(256) void gconv_wgrad16_kernel(GWArgs a, int tapgro
             const int ky = tap / a.KW, kx = tap - ky * a.KW;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const int sy = oys[h] * a.stride - a.pad + ky, sx = oxs[h] * a.stride - a.pad + kx;
+                const int sy = oys[h] * a.stride - a.pad + ky * a.dil, sx = oxs[h] * a.stride - a.pad + kx * a.dil;
                 const int k = kblk * 64 + vec * 8;
                 u32x4v v = {0u, 0u, 0u, 0u};
                 if (pok[h] && k < a.KC && sy >= 0 && sy < a.IH && sx >= 0 && sx < a.IW)
@@ -530,6 +533,30 @@ __global__ __launch_bounds__(1024) void gcolsum_reduce_kernel(const float* __res
         out[c] = (accumulate ? out[c] : 0.f) + r;
     }
 }
+// column sums of x [npix][C] accumulated in DOUBLE and rounded to f32 once: the bias gradient of a network's output convolution, whose dout is
+// the loss gradient itself -- with one output channel a single sum over every pixel of terms of both signs, where f32 partial sums lose
+// several ulp to cancellation (the loss kernels sum in double for the same reason, wm_reduce.h).  A workgroup owns one 16-byte vector of
+// channels and all the pixels: thread t adds pixels t, t + 256, ...; the 256 partial sums meet through block_sum_f64 in a fixed order
+template <typename T>
+__global__ __launch_bounds__(256) void gcolsum_f64_kernel(const T* __restrict__ x, size_t npix, int C, float* __restrict__ out, int Creal, int accumulate) {
+    constexpr int VE = 16 / sizeof(T);
+    const int c0 = blockIdx.x * VE;
+    double acc[VE];
+#pragma unroll
+    for (int e = 0; e < VE; ++e) acc[e] = 0.0;
+    for (size_t p = threadIdx.x; p < npix; p += 256) {
+        const vec16<T> t = *reinterpret_cast<const vec16<T>*>(x + p * C + c0);
+#pragma unroll
+        for (int e = 0; e < VE; ++e) acc[e] += (double)t.get(e);
+    }
+    __shared__ double s[4];
+#pragma unroll
+    for (int e = 0; e < VE; ++e) {
+        const double r = block_sum_f64(acc[e], s);
+        if (threadIdx.x == 0 && c0 + e < Creal) out[c0 + e] = (float)((accumulate ? (double)out[c0 + e] : 0.0) + r);
+        __syncthreads();   // s is reused by the next channel
+    }
+}
 inline int colsum_nsplit(size_t npix) {   // >= 256 pixels per split, at most 512 splits (2 workgroups per CU; the reduce reads them all from one)
     const size_t n = (npix + 255) / 256;
     return (int)(n < 1 ? 1 : (n > 512 ? 512 : n));
@@ -540,8 +567,9 @@ inline int grid1(size_t n, int cap = 4096) {
     return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g));
 }
 
-int check_geo(const char* name, int B, int IH, int IW, int KC, int OH, int OW, int NC, int KH, int KW, int stride, int pad, int dtype) {
+int check_geo(const char* name, int B, int IH, int IW, int KC, int OH, int OW, int NC, int KH, int KW, int stride, int pad, int dil, int dtype) {
     WM_REQUIRE(B > 0 && IH > 0 && IW > 0 && OH > 0 && OW > 0 && KC > 0 && NC > 0, WM_E_BADARG, "%s: bad shape", name);
+    WM_REQUIRE(dil >= 1 && dil <= 8 && (dil == 1 || stride == 1), WM_E_BADARG, "%s: dilation %d with stride %d unsupported (1..8, stride 1 only)", name, dil, stride);
     WM_REQUIRE(KH >= 1 && KH <= 5 && KW >= 1 && KW <= 5 && (stride == 1 || stride == 2) && pad >= 0 && pad <= 4, WM_E_SHAPE,
                "%s: kernel %dx%d stride %d pad %d unsupported (<= 5x5, stride 1 or 2)", name, KH, KW, stride, pad);
     WM_REQUIRE(dtype == WM_F32 || dtype == WM_BF16 || dtype == WM_F16, WM_E_BADARG, "%s: unsupported dtype %d", name, dtype);
@@ -593,27 +621,41 @@ __global__ __launch_bounds__(256) void glinear_small_kernel(const T* __restrict_
     }
 }
 
-extern "C" int wm_gconv_fwd(const void* in, const void* w, const float* bias, void* out, int B, int IH, int IW, int KC, int OH, int OW, int NC,
-                            int KH, int KW, int stride, int pad, int dgrad, int dtype, void* stream) {
-    WM_REQUIRE(in && w && out, WM_E_BADARG, "wm_gconv_fwd: null pointer");
-    int rc = check_geo("wm_gconv_fwd", B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, dtype);
+static int gconv_fwd_impl(const char* name, const void* in, const void* w, const float* bias, void* out, int B, int IH, int IW, int KC, int OH, int OW,
+                          int NC, int KH, int KW, int stride, int pad, int dil, int dgrad, int dtype, void* stream) {
+    WM_REQUIRE(in && w && out, WM_E_BADARG, "%s: null pointer", name);
+    int rc = check_geo(name, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, dil, dtype);
     if (rc) return rc;
-    WM_REQUIRE((((uintptr_t)in | (uintptr_t)w | (uintptr_t)out) & 15) == 0, WM_E_SHAPE, "wm_gconv_fwd: pointers must be 16-byte aligned");
+    WM_REQUIRE((((uintptr_t)in | (uintptr_t)w | (uintptr_t)out) & 15) == 0, WM_E_SHAPE, "%s: pointers must be 16-byte aligned", name);
+    {   // every source pixel the kernel may read lies inside `in`: the output grid must be the one the geometry gives
+        const int ext_h = (KH - 1) * dil + 1, ext_w = (KW - 1) * dil + 1;
+        const bool fits = dgrad ? (OH == (IH - 1) * stride - 2 * pad + ext_h || dil == 1) : (OH == (IH + 2 * pad - ext_h) / stride + 1 || dil == 1);
+        const bool fitsw = dgrad ? (OW == (IW - 1) * stride - 2 * pad + ext_w || dil == 1) : (OW == (IW + 2 * pad - ext_w) / stride + 1 || dil == 1);
+        WM_REQUIRE(fits && fitsw, WM_E_SHAPE, "%s: output grid %dx%d does not belong to input %dx%d, kernel %dx%d, pad %d, dilation %d", name, OH, OW, IH, IW, KH, KW, pad, dil);
+    }
     GArgs a;
     a.in = in; a.w = w; a.bias = bias; a.out = out; a.B = B; a.IH = IH; a.IW = IW; a.KC = KC; a.OH = OH; a.OW = OW; a.NC = NC;
-    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dgrad = dgrad ? 1 : 0;
+    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dil = dil; a.dgrad = dgrad ? 1 : 0;
     const size_t npix = (size_t)B * OH * OW;
     const dim3 grid((unsigned)((npix + 63) / 64), (unsigned)((NC + 63) / 64));
     hipStream_t s = (hipStream_t)stream;
     if (KH == 1 && KW == 1 && stride == 1 && pad == 0 && npix <= 32 && IH == OH && IW == OW) {   // a Linear layer on a few rows (either direction)
-        WM_DISPATCH_DTYPE(dtype, "wm_gconv_fwd",
+        WM_DISPATCH_DTYPE(dtype, name,
             hipLaunchKernelGGL((glinear_small_kernel<T, 32>), dim3((unsigned)((NC + 3) / 4)), dim3(256), 0, s, (const T*)in, (const T*)w, bias, (T*)out, (int)npix, KC, NC));
-        WM_LAUNCH_CHECK("wm_gconv_fwd(linear)");
+        WM_LAUNCH_CHECK(name);
         return WM_OK;
     }
-    WM_DISPATCH_DTYPE(dtype, "wm_gconv_fwd", hipLaunchKernelGGL(gconv_kernel<T>, grid, dim3(256), 0, s, a));
-    WM_LAUNCH_CHECK("wm_gconv_fwd");
+    WM_DISPATCH_DTYPE(dtype, name, hipLaunchKernelGGL(gconv_kernel<T>, grid, dim3(256), 0, s, a));
+    WM_LAUNCH_CHECK(name);
     return WM_OK;
+}
+extern "C" int wm_gconv_fwd(const void* in, const void* w, const float* bias, void* out, int B, int IH, int IW, int KC, int OH, int OW, int NC,
+                            int KH, int KW, int stride, int pad, int dgrad, int dtype, void* stream) {
+    return gconv_fwd_impl("wm_gconv_fwd", in, w, bias, out, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, 1, dgrad, dtype, stream);
+}
+extern "C" int wm_gconv_dil_fwd(const void* in, const void* w, const float* bias, void* out, int B, int IH, int IW, int KC, int OH, int OW, int NC,
+                                int KH, int KW, int stride, int pad, int dil, int dgrad, int dtype, void* stream) {
+    return gconv_fwd_impl("wm_gconv_dil_fwd", in, w, bias, out, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, dil, dgrad, dtype, stream);
 }
 
 // pixel splits of the 16-bit kernel: enough workgroups to fill the chip, at most 64 slabs
@@ -656,21 +698,21 @@ extern "C" size_t wm_gcolsum_scratch_floats(size_t npix, int C) { return (size_t
 
 // dw [Cout][Cin][KH][KW] f32 (+)= the weight gradient; dbias [Cout] (+)= column sums of dout (may be NULL).
 // partial: f32 scratch of wm_gconv_wgrad_scratch_floats(..) floats.
-extern "C" int wm_gconv_wgrad(const void* dout, const void* in, float* partial, float* dw, float* dbias, int accumulate, int B, int IH, int IW,
-                              int KC, int OH, int OW, int NC, int KH, int KW, int stride, int pad, int Cout, int Cin, int dtype, void* stream) {
-    WM_REQUIRE(dout && in && partial && dw, WM_E_BADARG, "wm_gconv_wgrad: null pointer");
-    int rc = check_geo("wm_gconv_wgrad", B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, dtype);
+static int gconv_wgrad_impl(const char* name, const void* dout, const void* in, float* partial, float* dw, float* dbias, int accumulate, int B, int IH,
+                            int IW, int KC, int OH, int OW, int NC, int KH, int KW, int stride, int pad, int dil, int Cout, int Cin, int dtype, void* stream) {
+    WM_REQUIRE(dout && in && partial && dw, WM_E_BADARG, "%s: null pointer", name);
+    int rc = check_geo(name, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, dil, dtype);
     if (rc) return rc;
-    WM_REQUIRE(Cout > 0 && Cout <= NC && Cin > 0 && Cin <= KC, WM_E_BADARG, "wm_gconv_wgrad: Cout / Cin exceed the tensors' channel strides");
+    WM_REQUIRE(Cout > 0 && Cout <= NC && Cin > 0 && Cin <= KC, WM_E_BADARG, "%s: Cout / Cin exceed the tensors' channel strides", name);
     GWArgs a;
     a.dout = dout; a.in = in; a.partial = partial; a.B = B; a.IH = IH; a.IW = IW; a.KC = KC; a.OH = OH; a.OW = OW; a.NC = NC;
-    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
+    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dil = dil;
     hipStream_t s = (hipStream_t)stream;
     if (dtype == WM_F32) {
         a.nsplit = wm_gconv_wgrad_nsplit(B, OH, OW, KC, NC, KH, KW);
         const int jobs = KH * KW * (NC / 16) * ((KC + 15) / 16);
         hipLaunchKernelGGL(gconv_wgrad_kernel<float>, dim3((unsigned)jobs, (unsigned)a.nsplit), dim3(256), 0, s, a);
-    } else if (thin_ok(KC, NC, KH, KW, stride)) {
+    } else if (dil == 1 && thin_ok(KC, NC, KH, KW, stride)) {   // (the thin kernel's staged window is dense: undilated layers only)
         a.nsplit = thin_nsplit(B, OH, OW);
         const int winw = 63 * stride + KW;
         const size_t lds = 64 * 32 + (size_t)KH * winw * 32;
@@ -684,7 +726,7 @@ extern "C" int wm_gconv_wgrad(const void* dout, const void* in, float* partial, 
         if (dtype == WM_BF16) hipLaunchKernelGGL(gconv_wgrad16_kernel<bf16_t>, grid, dim3(256), 0, s, a, tapgroups);
         else hipLaunchKernelGGL(gconv_wgrad16_kernel<f16_t>, grid, dim3(256), 0, s, a, tapgroups);
     }
-    WM_LAUNCH_CHECK("wm_gconv_wgrad");
+    WM_LAUNCH_CHECK(name);
     {
         const int SL = a.nsplit >= 64 ? 16 : a.nsplit >= 8 ? 4 : 1;
         const size_t outs = (size_t)Cout * Cin * KH * KW, per = 256 / SL;
@@ -692,15 +734,36 @@ extern "C" int wm_gconv_wgrad(const void* dout, const void* in, float* partial, 
         hipLaunchKernelGGL(gconv_wreduce_kernel, dim3((unsigned)(g > 16384 ? 16384 : g)), dim3(256), 0, s, partial, a.nsplit, KH * KW, NC, KC, dw, Cout, Cin,
                            accumulate, SL);
     }
-    WM_LAUNCH_CHECK("wm_gconv_wgrad(reduce)");
+    WM_LAUNCH_CHECK(name);
     if (dbias) {   // (the slab partials have been consumed by the reduce above: the scratch is free again)
         const size_t npix = (size_t)B * OH * OW;
         const int ns = colsum_nsplit(npix);
-        WM_DISPATCH_DTYPE(dtype, "wm_gconv_wgrad(bias)",
+        WM_DISPATCH_DTYPE(dtype, name,
             hipLaunchKernelGGL(gcolsum_kernel<T>, dim3((unsigned)((NC + 63) / 64), (unsigned)ns), dim3(256), 0, s, (const T*)dout, npix, NC, partial));
         hipLaunchKernelGGL(gcolsum_reduce_kernel, dim3((unsigned)((Cout + 63) / 64)), dim3(1024), 0, s, partial, ns, NC, dbias, Cout, accumulate);
-        WM_LAUNCH_CHECK("wm_gconv_wgrad(bias)");
+        WM_LAUNCH_CHECK(name);
     }
+    return WM_OK;
+}
+extern "C" int wm_gconv_wgrad(const void* dout, const void* in, float* partial, float* dw, float* dbias, int accumulate, int B, int IH, int IW,
+                              int KC, int OH, int OW, int NC, int KH, int KW, int stride, int pad, int Cout, int Cin, int dtype, void* stream) {
+    return gconv_wgrad_impl("wm_gconv_wgrad", dout, in, partial, dw, dbias, accumulate, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, 1, Cout, Cin, dtype, stream);
+}
+// the same scratch as the undilated layer (wm_gconv_wgrad_scratch_floats: the splits depend on the output grid and the channels only)
+extern "C" int wm_gconv_dil_wgrad(const void* dout, const void* in, float* partial, float* dw, float* dbias, int accumulate, int B, int IH, int IW,
+                                  int KC, int OH, int OW, int NC, int KH, int KW, int stride, int pad, int dil, int Cout, int Cin, int dtype, void* stream) {
+    return gconv_wgrad_impl("wm_gconv_dil_wgrad", dout, in, partial, dw, dbias, accumulate, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, dil, Cout, Cin, dtype, stream);
+}
+
+// out [Creal] f32 (+)= column sums of x [npix][C] summed in double, one rounding (no scratch); C a multiple of 16
+extern "C" int wm_gcolsum_f64(const void* x, size_t npix, int C, float* out, int Creal, int accumulate, int dtype, void* stream) {
+    WM_REQUIRE(x && out && npix > 0 && C > 0 && C % 16 == 0 && Creal > 0 && Creal <= C, WM_E_BADARG, "wm_gcolsum_f64: bad arguments");
+    WM_REQUIRE(((uintptr_t)x & 15) == 0, WM_E_SHAPE, "wm_gcolsum_f64: x must be 16-byte aligned");
+    WM_DISPATCH_DTYPE(dtype, "wm_gcolsum_f64", {
+        constexpr int VE = 16 / sizeof(T);
+        hipLaunchKernelGGL(gcolsum_f64_kernel<T>, dim3((unsigned)((Creal + VE - 1) / VE)), dim3(256), 0, (hipStream_t)stream, (const T*)x, npix, C, out, Creal, accumulate);
+    });
+    WM_LAUNCH_CHECK("wm_gcolsum_f64");
     return WM_OK;
 }
 

@@ -456,14 +456,25 @@ __global__ __launch_bounds__(256) void sn_bwd_kernel(const float* __restrict__ G
 }
 
 // Bayar constraint on w [Co][Ci][5][5] in place (conditional_jpeg_generator.py:814-817): centre := 0, every 5x5 filter divided by its
-// sum, centre := -1
+// sum, centre := -1 -- the three statements of networks.py:1059-1061 as well: w *= mask; w *= pow(sum(w), -1); w += final.  The scale is a
+// multiplication by the rounded reciprocal, as pow(., -1) makes it; a zero sum is not guarded (0 * inf = nan at the centre, inf elsewhere,
+// as in the reference).  One thread per plane.  The plane sum in f32, TORCH_ORDER false: plain left to right (wm_bayar_constrain, as ever);
+// true (wm_bayar_constrain_torch_order): NOT left to right but the order torch.sum over the last two axes gives for 25 contiguous floats on
+// the CPU (ATen's vectorized_inner_sum with 8-float vectors): eight lane sums l_j = (x[j] + x[j+8]) + x[j+16], then x[24] + l_0 + ... + l_7
+// from the left.  tests/test_cpu_unetd.py shows on the fixture that this order equals torch's bit for bit and that left to right does not.
+template <bool TORCH_ORDER>
 __global__ void bayar_kernel(float* __restrict__ w, int nfilters) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nfilters) return;
     float* p = w + (size_t)f * 25;
     p[12] = 0.f;
     float s = 0.f;
-    for (int i = 0; i < 25; ++i) s += p[i];
+    if constexpr (TORCH_ORDER) {
+        s = p[24];
+        for (int j = 0; j < 8; ++j) s += (p[j] + p[j + 8]) + p[j + 16];
+    } else {
+        for (int i = 0; i < 25; ++i) s += p[i];
+    }
     const float inv = 1.f / s;
     for (int i = 0; i < 25; ++i) p[i] *= inv;
     p[12] += -1.f;
@@ -644,7 +655,13 @@ extern "C" int wm_spectral_norm_bwd(const float* G, const float* Wsn, const floa
 }
 extern "C" int wm_bayar_constrain(float* w, int nfilters, void* stream) {
     WM_REQUIRE(w && nfilters > 0, WM_E_BADARG, "wm_bayar_constrain: bad arguments");
-    hipLaunchKernelGGL(bayar_kernel, dim3((nfilters + 63) / 64), dim3(64), 0, (hipStream_t)stream, w, nfilters);
+    hipLaunchKernelGGL(bayar_kernel<false>, dim3((nfilters + 63) / 64), dim3(64), 0, (hipStream_t)stream, w, nfilters);
     WM_LAUNCH_CHECK("wm_bayar_constrain");
+    return WM_OK;
+}
+extern "C" int wm_bayar_constrain_torch_order(float* w, int nfilters, void* stream) {
+    WM_REQUIRE(w && nfilters > 0, WM_E_BADARG, "wm_bayar_constrain_torch_order: bad arguments");
+    hipLaunchKernelGGL(bayar_kernel<true>, dim3((nfilters + 63) / 64), dim3(64), 0, (hipStream_t)stream, w, nfilters);
+    WM_LAUNCH_CHECK("wm_bayar_constrain_torch_order");
     return WM_OK;
 }

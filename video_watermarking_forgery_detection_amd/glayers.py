@@ -1,6 +1,6 @@
 """General HIP layer toolkit for the networks either side of the HiDDeN path: nn.Conv2d / nn.ConvTranspose2d /
-nn.Linear / the activations / residual and QF-attention combines / global average pooling / symmetric and replication padding /
-spectral norm, each an autograd Function over the C ABI's wm_gconv_* / wm_unary_* / ... entry points (include/wm_hip.h, "general
+nn.Linear / the activations / residual and QF-attention combines / global average pooling / symmetric, replication and reflection
+padding / spectral norm (of a convolution and of a transposed one), each an autograd Function over the C ABI's wm_gconv_* / wm_unary_* / ... entry points (include/wm_hip.h, "general
 layer family").  Parameters keep torch's layouts and names, so a reference state_dict loads unchanged
 (models/networks.py:631-749, models/conditional_jpeg_generator.py:40-374,697-826).
 
@@ -66,38 +66,40 @@ def _pack3(weight, rows, cols, dtype, transpose, plan_ok):
     return ops.pack_w3x3(w, rows, cols, dtype, transpose=transpose)
 
 
-def _fast3x3(weight, stride, pad, dtype, out_stride):
-    """3x3 stride-1 pad-1 convolutions on 16-bit activations whose output stride is a multiple of 32 run on the hot path's
+def _fast3x3(weight, stride, pad, dtype, out_stride, dil=1):
+    """3x3 stride-1 pad-1 undilated convolutions on 16-bit activations whose output stride is a multiple of 32 run on the hot path's
     wave-specialised / streamed-filter kernels (csrc/conv3x3*.hip, wgrad_ws.hip) instead of the general direct kernel"""
-    return (dtype in (torch.bfloat16, torch.float16) and tuple(weight.shape[2:]) == (3, 3) and stride == 1 and pad == 1 and out_stride % 32 == 0)
+    return (dil == 1 and dtype in (torch.bfloat16, torch.float16) and tuple(weight.shape[2:]) == (3, 3) and stride == 1 and pad == 1 and out_stride % 32 == 0)
 
 
-def _conv_forward(ctx, x, weight, bias, stride, pad):
+def _conv_forward(ctx, x, weight, bias, stride, pad, dil=1):
     """the convolution itself + what both autograd nodes below keep for their backward (everything but the saved tensors)"""
     Cout, Cin, KH, KW = weight.shape
     B, IH, IW, KC = x.shape
     if KC != cpad(Cin):
         raise ValueError(f"conv expects {Cin} input channels (stride {cpad(Cin)}), the activation has stride {KC}")
     NC = cpad(Cout)
-    OH, OW = (IH + 2 * pad - KH) // stride + 1, (IW + 2 * pad - KW) // stride + 1
+    OH, OW = (IH + 2 * pad - dil * (KH - 1) - 1) // stride + 1, (IW + 2 * pad - dil * (KW - 1) - 1) // stride + 1
     ctx.geo = (stride, pad, bias is not None)
+    ctx.dil = dil
     ctx.plan_ok = isinstance(weight, nn.Parameter)       # (a computed weight -- spectral norm -- is a new tensor every call: never planned)
     ctx.bias_ptr = bias.data_ptr() if bias is not None else 0
-    if _fast3x3(weight, stride, pad, x.dtype, NC):
+    if _fast3x3(weight, stride, pad, x.dtype, NC, dil):
         wp = _pack3(weight, NC, KC, x.dtype, False, ctx.plan_ok)
         out, _ = ops.conv3x3_fwd(x, wp, _pad_bias(bias, NC), None, None, want_stats=False)
         return out
     wp = ops.gconv_pack(weight.detach(), NC, KC, False, x.dtype)
-    return ops.gconv_fwd(x, wp, _pad_bias(bias, NC), (OH, OW), KH, KW, stride, pad)
+    return ops.gconv_fwd(x, wp, _pad_bias(bias, NC), (OH, OW), KH, KW, stride, pad, dilation=dil)
 
 
 class _ConvFn(Function):
     """nn.Conv2d on NHWC: weight [Cout,Cin,KH,KW] f32"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad):
-        out = _conv_forward(ctx, x, weight, bias, stride, pad)
+    def forward(ctx, x, weight, bias, stride, pad, dil, bias_f64):
+        out = _conv_forward(ctx, x, weight, bias, stride, pad, dil)
         ctx.save_for_backward(x, weight)
+        ctx.bias_f64 = bias_f64
         return out
 
     @staticmethod
@@ -105,34 +107,37 @@ class _ConvFn(Function):
         x, weight = ctx.saved_tensors
         stride, pad, has_bias = ctx.geo
         gx, gw, gb = _conv_backward(x, weight, g.contiguous(), stride, pad, ctx.needs_input_grad[0],
-                                    ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]), has_bias, ctx.plan_ok, ctx.bias_ptr)
-        return gx, gw, gb, None, None
+                                    ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]), has_bias, ctx.plan_ok, ctx.bias_ptr, ctx.dil, ctx.bias_f64)
+        return gx, gw, gb, None, None, None, None
 
 
-def _conv_backward(x, weight, g, stride, pad, need_gx, need_gw, want_bias, plan_ok=False, bias_ptr=0):
+def _conv_backward(x, weight, g, stride, pad, need_gx, need_gw, want_bias, plan_ok=False, bias_ptr=0, dil=1, bias_f64=False):
     """(gx, gw, gb) of nn.Conv2d for the output gradient g (NHWC, contiguous); gb only if want_bias.  A parameter whose .grad is a view
     of a FlatAdamW buffer gets its gradient ADDED there by the kernel and None returned for it (autograd would otherwise launch one
     add per parameter and contribution: 3,200 a step in the invertible embedder, whose weights all serve twice)."""
     Cout, Cin, KH, KW = weight.shape
     gx = gw = gb = None
     if need_gx:
-        if _fast3x3(weight, stride, pad, g.dtype, x.shape[3]):
+        if _fast3x3(weight, stride, pad, g.dtype, x.shape[3], dil):
             wt = _pack3(weight, g.shape[3], x.shape[3], g.dtype, True, plan_ok)
             gx, _ = ops.conv3x3_fwd(g, wt, None, None, None, want_stats=False)
         else:
             wt = ops.gconv_pack(weight.detach(), x.shape[3], g.shape[3], True, g.dtype)
-            gx = ops.gconv_fwd(g, wt, None, (x.shape[1], x.shape[2]), KH, KW, stride, pad, dgrad=True)
+            gx = ops.gconv_fwd(g, wt, None, (x.shape[1], x.shape[2]), KH, KW, stride, pad, dgrad=True, dilation=dil)
     if need_gw:
         wacc = _flat_grad(weight.data_ptr(), weight.numel())
         bacc = _flat_grad(bias_ptr, Cout) if want_bias else None
         if wacc is None or (want_bias and bacc is None):
             wacc = bacc = None
-        if _fast3x3(weight, stride, pad, g.dtype, 32):      # (the weight-gradient kernels take any 8-multiple of channels)
+        if _fast3x3(weight, stride, pad, g.dtype, 32, dil):      # (the weight-gradient kernels take any 8-multiple of channels)
             gw = wacc.view(Cout, Cin, 3, 3) if wacc is not None else torch.empty(Cout, Cin, 3, 3, device=g.device, dtype=torch.float32)
             ops.conv3x3_wgrad(x, x.shape[3], None, None, g, gw, wacc is not None)
-            gb = ops.gcolsum(g, Cout, out_acc=bacc) if want_bias else None
+            gb = ops.gcolsum(g, Cout, out_acc=bacc, f64=bias_f64) if want_bias else None
+        elif want_bias and bias_f64:     # (the bias gradient summed in double: Conv2d(bias_grad_f64=True))
+            gw, _ = ops.gconv_wgrad(g, x, Cout, Cin, KH, KW, stride, pad, want_bias=False, dw_acc=wacc, dilation=dil)
+            gb = ops.gcolsum(g, Cout, out_acc=bacc, f64=True)
         else:
-            gw, gb = ops.gconv_wgrad(g, x, Cout, Cin, KH, KW, stride, pad, want_bias=want_bias, dw_acc=wacc, db_acc=bacc)
+            gw, gb = ops.gconv_wgrad(g, x, Cout, Cin, KH, KW, stride, pad, want_bias=want_bias, dw_acc=wacc, db_acc=bacc, dilation=dil)
         if wacc is not None:
             gw = gb = None
     return gx, gw, gb
@@ -141,8 +146,8 @@ def _conv_backward(x, weight, g, stride, pad, need_gx, need_gw, want_bias, plan_
 FUSE_ELU = True   # (tests switch it off to compare with the separate launches)
 
 
-def _elu_fused(kind, weight, stride, pad, x):
-    return (FUSE_ELU and kind == "elu" and tuple(weight.shape[2:]) == (3, 3) and stride == 1 and pad == 1 and weight.shape[0] == 64
+def _elu_fused(kind, weight, stride, pad, x, dil=1):
+    return (FUSE_ELU and dil == 1 and kind == "elu" and tuple(weight.shape[2:]) == (3, 3) and stride == 1 and pad == 1 and weight.shape[0] == 64
             and x.shape[3] == cpad(weight.shape[1]) and ops.conv3x3_fwd_elu_supported(x.shape[3], 64, x.dtype))
 
 
@@ -201,8 +206,8 @@ class _ConvActFn(Function):
     over the data (ops.unary_bwd_colsum: two launches instead of three, gz not read back), then the convolution's two gradients from gz"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad, kind):
-        z = _conv_forward(ctx, x, weight, bias, stride, pad)
+    def forward(ctx, x, weight, bias, stride, pad, dil, kind):
+        z = _conv_forward(ctx, x, weight, bias, stride, pad, dil)
         ctx.save_for_backward(x, weight, z)
         ctx.kind = kind
         return ops.unary_fwd(z, kind)
@@ -213,8 +218,8 @@ class _ConvActFn(Function):
         stride, pad, has_bias = ctx.geo
         bacc = _flat_grad(ctx.bias_ptr, weight.shape[0]) if (has_bias and ctx.needs_input_grad[2]) else None
         gz, gb = ops.unary_bwd_colsum(z, g, ctx.kind, weight.shape[0], db_acc=bacc)
-        gx, gw, _ = _conv_backward(x, weight, gz, stride, pad, ctx.needs_input_grad[0], ctx.needs_input_grad[1], False, ctx.plan_ok)
-        return gx, gw, (gb if has_bias and ctx.needs_input_grad[2] and bacc is None else None), None, None, None
+        gx, gw, _ = _conv_backward(x, weight, gz, stride, pad, ctx.needs_input_grad[0], ctx.needs_input_grad[1], False, ctx.plan_ok, dil=ctx.dil)
+        return gx, gw, (gb if has_bias and ctx.needs_input_grad[2] and bacc is None else None), None, None, None, None
 
 
 class _ConvTFn(Function):
@@ -340,6 +345,19 @@ class _SpectralNormFn(Function):
         return ops.spectral_norm_bwd(g, wsn, u, v, sigma), None, None, None
 
 
+class _ReflectPadFn(Function):
+    """nn.ReflectionPad2d(p) on NHWC; the backward gathers the <= 9 padded positions of every pixel (ops.reflect_pad_bwd)"""
+
+    @staticmethod
+    def forward(ctx, x, pad):
+        ctx.pad = pad
+        return ops.reflect_pad_fwd(x, pad)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.reflect_pad_bwd(g.contiguous(), ctx.pad), None
+
+
 def to_nhwc(img, dtype, pads=(0, 0, 0, 0), mode=ops.PAD_SYMMETRIC):
     """NCHW f32 image -> NHWC activation, optionally padded (left, right, top, bottom) symmetrically or by replication"""
     if not img.is_cuda:
@@ -373,12 +391,17 @@ def _kaiming_uniform_(w, fan_in):
 
 
 class Conv2d(nn.Module):
-    """nn.Conv2d(in, out, k, stride, padding, bias) on NHWC activations; parameters `weight` [out,in,k,k], `bias` [out]"""
+    """nn.Conv2d(in, out, k, stride, padding, dilation=dilation, bias=bias) on NHWC activations; parameters `weight` [out,in,k,k],
+    `bias` [out].  dilation > 1 needs stride 1.  bias_grad_f64: the bias gradient (a sum over every pixel of the output gradient) is
+    accumulated in double and rounded once -- for a network's output layer, whose few channels receive the loss gradient itself"""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, dilation=1, bias_grad_f64=False):
         super().__init__()
+        self.bias_grad_f64 = bool(bias_grad_f64)
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.kernel_size, self.stride, self.padding = int(kernel_size), int(stride), int(padding)
+        self.kernel_size, self.stride, self.padding, self.dilation = int(kernel_size), int(stride), int(padding), int(dilation)
+        if self.dilation < 1 or (self.dilation > 1 and self.stride != 1):
+            raise ValueError(f"Conv2d: dilation {dilation} with stride {stride} is not supported (dilation >= 1, and stride 1 when it is > 1)")
         self.weight = nn.Parameter(torch.empty(out_channels, in_channels, self.kernel_size, self.kernel_size))
         self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
         fan_in = in_channels * self.kernel_size ** 2
@@ -390,15 +413,15 @@ class Conv2d(nn.Module):
         return self.weight
 
     def forward(self, x):
-        return _ConvFn.apply(x, self.effective_weight(), self.bias, self.stride, self.padding)
+        return _ConvFn.apply(x, self.effective_weight(), self.bias, self.stride, self.padding, self.dilation, self.bias_grad_f64)
 
 
 class SpectralNormConv2d(Conv2d):
     """nn.utils.spectral_norm(nn.Conv2d(..)) (networks.py:1381-1385): parameters `weight_orig`, buffers `weight_u`, `weight_v`,
     one power iteration per training forward, none in eval."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True):
-        super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias)
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, dilation=1):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias, dilation)
         w = self.weight
         del self._parameters["weight"]
         self.weight_orig = nn.Parameter(w.data)
@@ -429,9 +452,9 @@ class ConvAct(nn.Module):
     def forward(self, x):
         c = self._modules["0"]
         w = c.effective_weight()
-        if _elu_fused(self.kind, w, c.stride, c.padding, x):
+        if _elu_fused(self.kind, w, c.stride, c.padding, x, c.dilation):
             return _ConvEluFn.apply(x, w, c.bias)
-        return _ConvActFn.apply(x, w, c.bias, c.stride, c.padding, self.kind)
+        return _ConvActFn.apply(x, w, c.bias, c.stride, c.padding, c.dilation, self.kind)
 
     def extra_repr(self):
         return self.kind
@@ -439,7 +462,8 @@ class ConvAct(nn.Module):
 
 class FusedSequential(nn.Sequential):
     """nn.Sequential with the same children and state_dict keys whose forward runs every (Conv2d, Act) neighbour pair as one autograd
-    node (_ConvActFn): the activation's backward and the convolution's bias gradient become one pass over the data"""
+    node (_ConvActFn): the activation's backward and the convolution's bias gradient become one pass over the data.  Any other child
+    (a ReflectionPad2d between two pairs, a transposed convolution, a convolution with no activation behind it) runs as itself"""
 
     def forward(self, x):
         mods = list(self._modules.values())
@@ -448,10 +472,10 @@ class FusedSequential(nn.Sequential):
             m = mods[i]
             if isinstance(m, Conv2d) and i + 1 < len(mods) and isinstance(mods[i + 1], Act):
                 w = m.effective_weight()
-                if _elu_fused(mods[i + 1].kind, w, m.stride, m.padding, x):
+                if _elu_fused(mods[i + 1].kind, w, m.stride, m.padding, x, m.dilation):
                     x = _ConvEluFn.apply(x, w, m.bias)
                 else:
-                    x = _ConvActFn.apply(x, w, m.bias, m.stride, m.padding, mods[i + 1].kind)
+                    x = _ConvActFn.apply(x, w, m.bias, m.stride, m.padding, m.dilation, mods[i + 1].kind)
                 i += 2
             else:
                 x = m(x)
@@ -473,8 +497,46 @@ class ConvTranspose2d(nn.Module):
         if bias:
             _kaiming_uniform_(self.bias, fan_in)
 
+    def effective_weight(self):
+        return self.weight
+
     def forward(self, x):
-        return _ConvTFn.apply(x, self.weight, self.bias, self.stride, self.padding)
+        return _ConvTFn.apply(x, self.effective_weight(), self.bias, self.stride, self.padding)
+
+
+class SpectralNormConvTranspose2d(ConvTranspose2d):
+    """nn.utils.spectral_norm(nn.ConvTranspose2d(..)) (networks.py:991,1000).  torch normalises a transposed convolution over dim 1: the
+    matrix is weight_orig.permute(1,0,2,3).reshape(out, -1), so `weight_u` has `out` elements and `weight_v` in * k * k; parameter
+    `weight_orig` [in,out,k,k]; one power iteration per training forward, none in eval (the kernels of SpectralNormConv2d on that view)"""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias)
+        w = self.weight
+        del self._parameters["weight"]
+        self.weight_orig = nn.Parameter(w.data)
+        n = in_channels * self.kernel_size ** 2
+        self.register_buffer("weight_u", nn.functional.normalize(torch.randn(out_channels), dim=0, eps=1e-12))
+        self.register_buffer("weight_v", nn.functional.normalize(torch.randn(n), dim=0, eps=1e-12))
+
+    def effective_weight(self):
+        mat = self.weight_orig.permute(1, 0, 2, 3).contiguous()          # [out, in, k, k]: rows = dim 1 of the parameter
+        return _SpectralNormFn.apply(mat, self.weight_u, self.weight_v, self.training).permute(1, 0, 2, 3)
+
+
+class ReflectionPad2d(nn.Module):
+    """nn.ReflectionPad2d(p) on NHWC activations (the same p on all four sides, p <= min(H, W) - 1)"""
+
+    def __init__(self, padding):
+        super().__init__()
+        self.padding = int(padding)
+        if self.padding < 0:
+            raise ValueError(f"ReflectionPad2d: negative padding {padding}")
+
+    def forward(self, x):
+        return _ReflectPadFn.apply(x, self.padding)
+
+    def extra_repr(self):
+        return str(self.padding)
 
 
 class Linear(nn.Module):
@@ -490,7 +552,7 @@ class Linear(nn.Module):
             _kaiming_uniform_(self.bias, in_features)
 
     def forward(self, x):
-        return _ConvFn.apply(x, self.weight.view(self.out_features, self.in_features, 1, 1), self.bias, 1, 0)
+        return _ConvFn.apply(x, self.weight.view(self.out_features, self.in_features, 1, 1), self.bias, 1, 0, 1, False)
 
 
 class Act(nn.Module):

@@ -1381,8 +1381,11 @@ def gconv_pack(w, rows, cols, transpose, dtype):
     return wp
 
 
-def gconv_fwd(x, wp, bias, out_hw, KH, KW, stride, pad, dgrad=False):
-    """x [B,IH,IW,KC]; wp [taps][NC][KC] (gconv_pack); bias f32 [NC] or None; -> [B,OH,OW,NC]"""
+def gconv_fwd(x, wp, bias, out_hw, KH, KW, stride, pad, dgrad=False, dilation=1):
+    """x [B,IH,IW,KC]; wp [taps][NC][KC] (gconv_pack); bias f32 [NC] or None; -> [B,OH,OW,NC].  dilation 1 is the undilated entry
+    point; any other value goes to wm_gconv_dil_fwd (gconv_dil_fwd below takes 1 as well)"""
+    if dilation != 1:
+        return gconv_dil_fwd(x, wp, bias, out_hw, KH, KW, stride, pad, dilation, dgrad)
     x = _nhwc(x)
     B, IH, IW, KC = x.shape
     taps, NC, KC2 = wp.shape
@@ -1398,9 +1401,27 @@ def gconv_fwd(x, wp, bias, out_hw, KH, KW, stride, pad, dgrad=False):
     return out
 
 
-def gconv_wgrad(dout, x, Cout, Cin, KH, KW, stride, pad, want_bias=True, dw_acc=None, db_acc=None):
+def gconv_dil_fwd(x, wp, bias, out_hw, KH, KW, stride, pad, dilation, dgrad=False):
+    """gconv_fwd through wm_gconv_dil_fwd: tap (ky, kx) reads ky * dilation, kx * dilation pixels away (stride 1 when dilation > 1)"""
+    x = _nhwc(x)
+    B, IH, IW, KC = x.shape
+    taps, NC, KC2 = wp.shape
+    if taps != KH * KW or KC2 != KC or wp.dtype != x.dtype:
+        raise ValueError(f"packed filter {tuple(wp.shape)} {wp.dtype} does not fit the input {tuple(x.shape)} {x.dtype} / {KH}x{KW}")
+    if bias is not None and (bias.numel() != NC or bias.dtype != torch.float32):
+        raise ValueError("bias must be f32 with one entry per (padded) output channel")
+    OH, OW = out_hw
+    out = torch.empty(B, OH, OW, NC, device=x.device, dtype=x.dtype)
+    rc = _lib.lib().wm_gconv_dil_fwd(_p(x), _p(wp), _p(bias), _p(out), B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, int(dilation),
+                                     1 if dgrad else 0, dt_id(x.dtype), _stream())
+    _lib.check(rc, "wm_gconv_dil_fwd")
+    return out
+
+
+def gconv_wgrad(dout, x, Cout, Cin, KH, KW, stride, pad, want_bias=True, dw_acc=None, db_acc=None, dilation=1, dil_entry=False):
     """dw [Cout,Cin,KH,KW] f32, dbias [Cout] f32 (or None) of the conv x [B,IH,IW,KC] -> dout [B,OH,OW,NC].
-    dw_acc (and db_acc when a bias gradient is wanted): contiguous f32 tensors of those shapes the results are ADDED to instead"""
+    dw_acc (and db_acc when a bias gradient is wanted): contiguous f32 tensors of those shapes the results are ADDED to instead.
+    dilation != 1 (or dil_entry, which sends dilation 1 there too) runs wm_gconv_dil_wgrad"""
     dout, x = _nhwc(dout), _nhwc(x)
     B, OH, OW, NC = dout.shape
     _, IH, IW, KC = x.shape
@@ -1415,20 +1436,30 @@ def gconv_wgrad(dout, x, Cout, Cin, KH, KW, stride, pad, want_bias=True, dw_acc=
         raise ValueError("gconv_wgrad: accumulation targets do not match the gradients")
     dw = dw_acc if acc else torch.empty(Cout, Cin, KH, KW, device=x.device, dtype=torch.float32)
     db = (db_acc if acc else torch.empty(Cout, device=x.device, dtype=torch.float32)) if want_bias else None
+    if dilation != 1 or dil_entry:
+        rc = L.wm_gconv_dil_wgrad(_p(dout), _p(x), _p(partial), _p(dw), _p(db), 1 if acc else 0, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad,
+                                  int(dilation), Cout, Cin, dt_id(x.dtype), _stream())
+        _lib.check(rc, "wm_gconv_dil_wgrad")
+        return dw, db
     rc = _lib.lib().wm_gconv_wgrad(_p(dout), _p(x), _p(partial), _p(dw), _p(db), 1 if acc else 0, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad,
                                    Cout, Cin, dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_gconv_wgrad")
     return dw, db
 
 
-def gcolsum(x, creal, out_acc=None):
-    """column sums [creal] f32 of x [.., C]; out_acc: a contiguous f32 [creal] tensor they are ADDED to instead"""
+def gcolsum(x, creal, out_acc=None, f64=False):
+    """column sums [creal] f32 of x [.., C]; out_acc: a contiguous f32 [creal] tensor they are ADDED to instead.  f64: accumulated in
+    double and rounded once (wm_gcolsum_f64)"""
     x = _nhwc(x)
     C = x.shape[3]
     if out_acc is not None and (not out_acc.is_contiguous() or out_acc.numel() != creal or out_acc.dtype != torch.float32):
         raise ValueError("gcolsum: accumulation target does not match")
     out = out_acc if out_acc is not None else torch.empty(creal, device=x.device, dtype=torch.float32)
     L = _lib.lib()
+    if f64:
+        rc = L.wm_gcolsum_f64(_p(x), x.numel() // C, C, _p(out), creal, 0 if out_acc is None else 1, dt_id(x.dtype), _stream())
+        _lib.check(rc, "wm_gcolsum_f64")
+        return out
     scratch = torch.empty(L.wm_gcolsum_scratch_floats(x.numel() // C, C), device=x.device, dtype=torch.float32)
     rc = L.wm_gcolsum(_p(x), x.numel() // C, C, _p(out), creal, 0 if out_acc is None else 1, _p(scratch), dt_id(x.dtype), _stream())
     _lib.check(rc, "wm_gcolsum")
@@ -1599,13 +1630,49 @@ def spectral_norm_bwd(g, wsn, u, v, sigma):
     return gw
 
 
-def bayar_constrain_(w):
-    """the Bayar constraint on w [Co,Ci,5,5] in place (conditional_jpeg_generator.py:814-817)"""
+def bayar_constrain_(w, torch_order=False):
+    """the Bayar constraint on w [Co,Ci,5,5] in place (conditional_jpeg_generator.py:814-817, networks.py:1059-1061).  torch_order: the
+    plane sums in the order torch.sum takes on the CPU instead of left to right (the reference's float32 result bit for bit)"""
     _need_cuda(w)
     assert w.dtype == torch.float32 and w.is_contiguous() and w.shape[-2:] == (5, 5)
-    rc = _lib.lib().wm_bayar_constrain(_p(w), w.shape[0] * w.shape[1], _stream())
+    L = _lib.lib()
+    rc = (L.wm_bayar_constrain_torch_order if torch_order else L.wm_bayar_constrain)(_p(w), w.shape[0] * w.shape[1], _stream())
     _lib.check(rc, "wm_bayar_constrain")
     return w
+
+
+def _nhwc16b(x):
+    _need_cuda(x)
+    if x.dim() != 4 or not x.is_contiguous() or (x.shape[3] * x.element_size()) % 16:
+        raise ValueError(f"expected a contiguous NHWC tensor whose channel stride is a multiple of 16 bytes, got {tuple(x.shape)} {x.dtype}")
+    return x
+
+
+def reflect_pad_fwd(x, pad):
+    """nn.ReflectionPad2d(pad) on NHWC: x [B,H,W,CP] -> [B,H+2pad,W+2pad,CP]; pad <= min(H, W) - 1; CP a multiple of 16 bytes"""
+    x = _nhwc16b(x)
+    B, H, W, CP = x.shape
+    pad = int(pad)
+    if pad < 0 or pad > min(H, W) - 1:
+        raise ValueError(f"reflect_pad_fwd: pad {pad} needs min(H, W) - 1 >= pad, got {tuple(x.shape)}")
+    out = torch.empty(B, H + 2 * pad, W + 2 * pad, CP, device=x.device, dtype=x.dtype)
+    rc = _lib.lib().wm_reflect_pad_fwd(_p(x), _p(out), B, H, W, CP, pad, dt_id(x.dtype), _stream())
+    _lib.check(rc, "wm_reflect_pad_fwd")
+    return out
+
+
+def reflect_pad_bwd(g, pad):
+    """the adjoint of reflect_pad_fwd: g [B,H+2pad,W+2pad,CP] -> [B,H,W,CP], every padded position added onto the pixel it mirrors"""
+    g = _nhwc16b(g)
+    B, PH, PW, CP = g.shape
+    pad = int(pad)
+    H, W = PH - 2 * pad, PW - 2 * pad
+    if pad < 0 or H < 1 or W < 1 or pad > min(H, W) - 1:
+        raise ValueError(f"reflect_pad_bwd: {tuple(g.shape)} is no reflection-padded tensor of pad {pad}")
+    gx = torch.empty(B, H, W, CP, device=g.device, dtype=g.dtype)
+    rc = _lib.lib().wm_reflect_pad_bwd(_p(g), _p(gx), B, H, W, CP, pad, dt_id(g.dtype), _stream())
+    _lib.check(rc, "wm_reflect_pad_bwd")
+    return gx
 
 
 # ----------------------------------------------------------------------------- invertible embedder pieces (SURVEY 8f row 2)
