@@ -914,6 +914,28 @@ int wm_cw_margin(const float* logits, const long long* target, int B, int K, int
 int wm_mix_fwd(const float* const* xs_host, int K, const float* w, float* y, int N, size_t frame, int quant, void* stream);
 int wm_mix_bwd(const float* g, const float* w, float* const* gxs_host, int K, int N, size_t frame, void* stream);
 
+/* ------------------------------------------------------------------ two-source mask head (csrc/mask_head.hip)
+ * The full-resolution tail of the tamper localiser UNetDiscriminator (the reference's models/networks.py:1005-1013,1100-1110): decoder_0 =
+ * nn.Conv2d(na + nb, Cout, 1) on torch.cat((a, b), 1), optionally the sigmoid, as NCHW f32 -- in one pass that reads both sources in place:
+ *   out[b,co,p] = act(bias[co] + sum_c w[co,c] a[b,p,c] + sum_c w[co,na+c] b[b,p,c])
+ * a [B*hw][lda], b [B*hw][ldb]: NHWC activations of `dtype`, na <= lda and nb <= ldb real channels, the padding channels ignored whatever they
+ * hold; lda and ldb multiples of the 16-byte vector (4 f32 / 8 16-bit values) and at most 16 vectors, 16-byte aligned bases (WM_E_SHAPE
+ * otherwise).  w f32 [Cout][na+nb] (torch's decoder_0.0.weight), bias f32 [Cout] (NULL = 0), 1 <= Cout <= 4, accumulated in f32; out f32
+ * [B][Cout][hw]; act 0 = none, 1 = sigmoid.  (na + nb) * sizeof(dtype) + 4 Cout bytes per pixel, nothing else.
+ * wm_head2_bwd: gout f32 [B][Cout][hw]; chain_sigmoid != 0: gout is the gradient wrt the sigmoid OUTPUT and is multiplied by out (1 - out) of
+ *   the saved forward result `out`; 0: gout is the gradient wrt the logits (out may be NULL).  Writes ga [B*hw][ldga = lda], gb [B*hw][ldgb =
+ *   ldb] of `dtype` (padding channels exactly 0) and partials [wm_head2_nparts(B*hw)][Cout*(na+nb) + Cout] doubles: each workgroup's sums of
+ *   gz x (a | b) and of gz.
+ * wm_head2_finalize: dw [Cout][nab = na+nb], dbias [Cout] (+)= the partials added in double in a fixed order, rounded to f32 once (accumulate
+ *   != 0: the old value joins that sum before the rounding).  No floating-point atomics: every result is bitwise reproducible.
+ * The caller owns every buffer; the calls are asynchronous on `stream`. */
+int wm_head2_fwd(const void* a, int lda, int na, const void* b, int ldb, int nb, const float* w, const float* bias, float* out, int B, size_t hw,
+                 int Cout, int act, int dtype, void* stream);
+int wm_head2_nparts(size_t npix);
+int wm_head2_bwd(const void* a, int lda, int na, const void* b, int ldb, int nb, const float* w, const float* gout, const float* out,
+                 int chain_sigmoid, void* ga, int ldga, void* gb, int ldgb, double* partials, int B, size_t hw, int Cout, int dtype, void* stream);
+int wm_head2_finalize(const double* partials, int nparts, int Cout, int nab, float* dw, float* dbias, int accumulate, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

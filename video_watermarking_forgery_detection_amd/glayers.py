@@ -222,6 +222,36 @@ class _ConvActFn(Function):
         return gx, gw, (gb if has_bias and ctx.needs_input_grad[2] and bacc is None else None), None, None, None, None
 
 
+class _Head2Fn(Function):
+    """act(nn.Conv2d(na + nb, Cout, 1)(torch.cat((a[..., :na], b[..., :nb]), channels))) -> NCHW f32 [B,Cout,H,W] as ONE node and one launch
+    each way (+ the partial sums' finalise backwards): both NHWC sources are read in place (ops.head2_fwd / head2_bwd), act 0 none, 1 sigmoid;
+    weight [Cout, na+nb, 1, 1] f32, Cout <= 4.  The parameter gradients are summed in double and rounded once (Conv2d(bias_grad_f64=True)'s
+    convention) and, like _conv_backward's, ADDED into a live FlatAdamW's buffer when both parameters are registered there."""
+
+    @staticmethod
+    def forward(ctx, a, na, b, nb, weight, bias, act):
+        out = ops.head2_fwd(a, na, b, nb, weight.detach(), bias.detach() if bias is not None else None, act)
+        ctx.save_for_backward(a, b, weight, out)
+        ctx.meta = (na, nb, act, bias is not None, bias.data_ptr() if bias is not None else 0)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, weight, out = ctx.saved_tensors
+        na, nb, act, has_bias, bias_ptr = ctx.meta
+        wacc = _flat_grad(weight.data_ptr(), weight.numel()) if ctx.needs_input_grad[4] else None
+        bacc = _flat_grad(bias_ptr, weight.shape[0]) if (has_bias and ctx.needs_input_grad[5]) else None
+        if wacc is None or bacc is None:
+            wacc = bacc = None
+        ga, gb, gw, gbias = ops.head2_bwd(a, na, b, nb, weight.detach(), g.contiguous(), out if act == 1 else None, wacc, bacc)
+        if wacc is not None:
+            gw = gbias = None
+        else:
+            gw = gw.view_as(weight) if ctx.needs_input_grad[4] else None
+            gbias = gbias if (has_bias and ctx.needs_input_grad[5]) else None
+        return (ga if ctx.needs_input_grad[0] else None), None, (gb if ctx.needs_input_grad[2] else None), None, gw, gbias, None
+
+
 class _ConvTFn(Function):
     """nn.ConvTranspose2d on NHWC: weight [Cin,Cout,KH,KW] f32 -- the input gradient of the conv Cout -> Cin with the same filter"""
 
@@ -756,6 +786,39 @@ def clamp01(x):
     return _Clamp01Fn.apply(x)
 
 
+class FlatParameters:
+    """The trainable parameters of an nn.Module of this toolkit in ONE flat f32 buffer (`flat_params`; each nn.Parameter becomes a view of
+    it) with their gradients in a second (`flat_grads`; each .grad a view of it, autograd accumulates in place), registered so that the
+    convolution backward kernels ADD a parameter's gradient straight into the buffer (_flat_grad).  Frozen parameters (requires_grad False:
+    UNetDiscriminator's SRMConv2D.weight) stay where they are.  `flat_params`, `flat_grads` and parameters() are what the flat optimisers
+    (FlatAdamW here, hidden_models.hidden._FlatAdam), gradient clipping and distributed.GradSync drive; zero_grad() is one memset."""
+
+    def __init__(self, module, who="FlatParameters"):
+        ps = [p for p in module.parameters() if p.requires_grad]
+        if not ps or not all(p.is_cuda and p.dtype == torch.float32 for p in ps):
+            raise RuntimeError(f"{who}: parameters must be float32 CUDA tensors (move the module to the GPU first)")
+        n = sum(p.numel() for p in ps)
+        dev = ps[0].device
+        self.module = module
+        self.flat_params = torch.empty(n, device=dev, dtype=torch.float32)
+        self.flat_grads = torch.zeros(n, device=dev, dtype=torch.float32)
+        self.params, o = ps, 0
+        with torch.no_grad():
+            for p in ps:
+                k = p.numel()
+                self.flat_params[o:o + k].copy_(p.detach().reshape(-1))
+                p.data = self.flat_params[o:o + k].view(p.shape)
+                p.grad = self.flat_grads[o:o + k].view(p.shape)
+                _FLAT_GRADS[p.data_ptr()] = (weakref.ref(self.flat_params), weakref.ref(self.flat_grads), o, k)
+                o += k
+
+    def parameters(self):
+        return iter(self.params)
+
+    def zero_grad(self):
+        self.flat_grads.zero_()
+
+
 class FlatAdamW:
     """torch.optim.AdamW over ONE flat f32 buffer holding every trainable parameter of `module` (each nn.Parameter becomes a view of
     it, each .grad a view of a flat gradient buffer autograd accumulates into): zero_grad = one memset, clip_grad_norm_ = one norm,
@@ -764,24 +827,11 @@ class FlatAdamW:
     loss.backward(); torch.autograd.grad(loss, parameters) would see None for those parameters and still change the buffer."""
 
     def __init__(self, module, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
-        ps = [p for p in module.parameters() if p.requires_grad]
-        if not ps or not all(p.is_cuda and p.dtype == torch.float32 for p in ps):
-            raise RuntimeError("FlatAdamW: parameters must be float32 CUDA tensors (move the module to the GPU first)")
-        n = sum(p.numel() for p in ps)
-        dev = ps[0].device
-        self.flat = torch.empty(n, device=dev, dtype=torch.float32)
-        self.grad = torch.zeros(n, device=dev, dtype=torch.float32)
+        fp = FlatParameters(module, "FlatAdamW")
+        self.flat, self.grad, self.params = fp.flat_params, fp.flat_grads, fp.params
+        n, dev = self.flat.numel(), self.flat.device
         self.m = torch.zeros(n, device=dev, dtype=torch.float32)
         self.v = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.params, o = ps, 0
-        with torch.no_grad():
-            for p in ps:
-                k = p.numel()
-                self.flat[o:o + k].copy_(p.detach().reshape(-1))
-                p.data = self.flat[o:o + k].view(p.shape)
-                p.grad = self.grad[o:o + k].view(p.shape)
-                _FLAT_GRADS[p.data_ptr()] = (weakref.ref(self.flat), weakref.ref(self.grad), o, k)
-                o += k
         # one param group, torch's keys: what BaseModel's learning-rate handling and the schedulers (models/lr_scheduler.py) read and write
         self.param_groups = [{"lr": lr, "initial_lr": lr, "betas": betas, "eps": eps, "weight_decay": weight_decay}]
         self.t = 0

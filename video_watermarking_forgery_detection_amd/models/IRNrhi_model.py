@@ -25,6 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import engine, ops
+from .. import glayers as G
 from ..hidden_models import Hidden
 from ..hidden_models.hidden import _FlatAdam
 from ..network.UNet import UNet
@@ -38,6 +39,7 @@ from ..options import HiDDenConfiguration
 from .base_model import BaseModel
 from .lr_scheduler import build_schedulers
 from .modules.Quantization import Quantization
+from .networks import UNetDiscriminator
 
 
 def _get(d, *keys, default=None):
@@ -49,6 +51,62 @@ def _get(d, *keys, default=None):
         except (KeyError, TypeError, IndexError):
             return default
     return default if d is None else d
+
+
+LOCALIZER_ARCHS = ("unet", "unetd")
+
+
+def localizer_arch(train_opt):
+    """train.localizer_arch: 'unet' (the default) or 'unetd'; anything else is a ValueError"""
+    arch = _get(train_opt, 'localizer_arch', default='unet')
+    if arch not in LOCALIZER_ARCHS:
+        raise ValueError(f"train.localizer_arch must be one of {LOCALIZER_ARCHS}, got {arch!r}")
+    return arch
+
+
+def localizer_class(train_opt):
+    """the class IRNrhiModel builds its localiser from"""
+    return UNetDiscriminator if localizer_arch(train_opt) == "unetd" else UNet
+
+
+def build_unetd_localizer(device, dtype, dim=16, fused_head=True):
+    """the localiser the reference's trainers construct (IRNcrop_model.py:125-126, IRNp_model.py:162, IRN_model.py:147): UNetDiscriminator
+    with the SRM / Bayar first block, two dilated residual blocks, one sigmoid mask channel"""
+    return UNetDiscriminator(use_sigmoid=True, in_channels=3, residual_blocks=2, out_channels=1, use_spectral_norm=True, dim=int(dim),
+                             fused_head=bool(fused_head), dtype=dtype).to(device)
+
+
+def unetd_localiser_step(net, flat, optimizer, x, mask, weight=1.0, dice_weight=0.0, amp=None, grad_sync=None, clip=None):
+    """One training step of a UNetDiscriminator localiser on the batch x [B,3,H,W] with the tamper mask [B,1,H,W] -- what _localise runs once
+    the attacked batch exists (IRNcrop_model.py:376-378,391-393,407-416): forward through autograd, weight * BCEWithLogits on the SIGMOID
+    output (+ dice_weight * BinaryDiceLoss), both seeded with the scaler's device-side scale; backward through the network into `flat`
+    (glayers.FlatParameters of net: the convolution kernels add into it) and into x; all-reduce of the flat gradient (one bucket); joint
+    clipping (clip: callable(list of flat gradients)); one step of `optimizer` (_FlatAdam over [flat]).
+    -> (loss, dice or None, pred [B,1,H,W] detached, the gradient wrt x -- still multiplied by the scaler's scale, like the seeds)"""
+    flat.zero_grad()
+    x = x.detach().requires_grad_(True)
+    pred, _ = net(x)
+    p = pred.detach()
+    scale_dev = amp.scale if amp is not None else None
+    # the reference applies BCEWithLogits to the sigmoid output (:378,391-393): the seed is the gradient wrt that output, the network's own
+    # backward (the mask head's kernel, or the sigmoid's) chains the sigmoid
+    loss, g_pred = ops.bce_logits_target(p, mask, weight, chain_sigmoid=False, gscale_dev=scale_dev)
+    dice = None
+    if dice_weight > 0:
+        dice, _ = ops.dice_binary(p, mask, 1.0, 2.0, 'mean', want_grad=True, chain_sigmoid=False, gscale=dice_weight, gscale_dev=scale_dev,
+                                  grad_out=g_pred)
+    pred.backward(g_pred.view_as(pred))
+    gscale = 1.0
+    if grad_sync is not None:
+        grad_sync.finish_all([grad_sync.start(flat.flat_grads)])
+        gscale = grad_sync.scale
+        if clip is not None:
+            grad_sync.average_(flat.flat_grads)
+            gscale = 1.0
+    if clip is not None:
+        clip([flat.flat_grads])
+    optimizer.step(grad_scale=gscale)
+    return loss, dice, p, x.grad
 
 
 class DeferredLogs:
@@ -128,6 +186,7 @@ class _AttackCycle:
 class IRNrhiModel(BaseModel):
     def __init__(self, opt):
         super(IRNrhiModel, self).__init__(opt)
+        self.localizer_arch = localizer_arch(opt['train'])      # (an unknown architecture is refused before anything is built)
         if self.device.type != "cuda":
             raise RuntimeError("IRNrhiModel runs on the MI355X HIP path only (opt['gpu_ids'] must not be None)")
         train_opt = opt['train'] or {}
@@ -221,11 +280,22 @@ class IRNrhiModel(BaseModel):
         self.optimizers = [self.hidden.optimizer_enc_dec, self.hidden.optimizer_discrim]
         self.use_localizer = bool(_get(train_opt, 'localizer', default=False))
         self.localizer = None
+        # train.localizer_arch (default unet): unet = network.UNet on the fused engine; unetd = the reference trainers' own localiser,
+        # models.networks.UNetDiscriminator (IRNcrop_model.py:125-126) of width train.localizer_dim (default 16), trained through autograd on
+        # the HIP layer toolkit; train.localizer_fused_head (default true) runs its full-resolution tail as the one mask-head launch
+        self.localizer_flat = None
         if self.use_localizer:
-            self.localizer = UNet(3, 1, 32).to(self.device)
-            engine.set_compute_dtype(self.localizer, dtype)
-            self.localizer.flatten_parameters_()
-            self.optimizer_localizer = _FlatAdam([self.localizer], lr=lr, betas=betas, weight_decay=wd)
+            if self.localizer_arch == "unetd":
+                self.localizer = build_unetd_localizer(self.device, dtype, _get(train_opt, 'localizer_dim', default=16),
+                                                       _get(train_opt, 'localizer_fused_head', default=True))
+                # every trainable parameter in one flat buffer (the frozen SRMConv2D.weight stays out): one Adam launch, one clip, one bucket
+                self.localizer_flat = G.FlatParameters(self.localizer)
+                self.optimizer_localizer = _FlatAdam([self.localizer_flat], lr=lr, betas=betas, weight_decay=wd)
+            else:
+                self.localizer = UNet(3, 1, 32).to(self.device)
+                engine.set_compute_dtype(self.localizer, dtype)
+                self.localizer.flatten_parameters_()
+                self.optimizer_localizer = _FlatAdam([self.localizer], lr=lr, betas=betas, weight_decay=wd)
             if self.amp is not None:
                 self.optimizer_localizer.attach_amp(self.amp)
             self.optimizers.append(self.optimizer_localizer)
@@ -330,6 +400,13 @@ class IRNrhiModel(BaseModel):
             attacked_q = ops.clamp_quant(attacked)                  # clamp_with_grad + Quantization (:372-373)
         if self.keep_outputs:
             self.last_outputs.update(tampered=tampered, attacked=attacked_q)
+        if self.localizer_arch == "unetd":
+            loss, dice, pred, g_att = unetd_localiser_step(net, self.localizer_flat, self.optimizer_localizer, attacked_q, mask,
+                                                           weight=self.localizer_weight, dice_weight=self.dice_weight, amp=self.amp,
+                                                           grad_sync=self.grad_sync, clip=self._clip if self.gradient_clipping else None)
+            if self.keep_outputs:
+                self.last_outputs["pred"] = pred
+            return self._localise_tail(cA, g_att, g_enc, mask, kind, loss, dice)
         net.refresh_packs()   # all conv weights of the localiser packed in one launch, valid until its optimiser step
         try:
             pred, cU = net.fwd(attacked_q)
@@ -358,6 +435,10 @@ class IRNrhiModel(BaseModel):
                 gscale = 1.0
         self._clip([net.flat_grads])
         self.optimizer_localizer.step(grad_scale=gscale)
+        return self._localise_tail(cA, g_att, g_enc, mask, kind, loss, dice)
+
+    def _localise_tail(self, cA, g_att, g_enc, mask, kind, loss, dice):
+        """the localiser's input gradient back through the attack and the splice into g_enc; the step's logs"""
         g_tamp = self.hybrid.bwd(cA, g_att) if self.hybrid is not None else self.attack.bwd(cA, g_att)
         ops.masked_axpy_(g_enc, g_tamp.contiguous(), mask)
         loc_kind = self.hybrid.name if self.hybrid is not None else self.attack.name
@@ -377,7 +458,10 @@ class IRNrhiModel(BaseModel):
         was = self.localizer.training
         self.localizer.eval()
         try:
-            pred, _ = self.localizer.fwd(x, training=False)
+            if self.localizer_arch == "unetd":
+                pred, _ = self.localizer(x)      # (eval mode: no power iteration, weight_u / weight_v untouched)
+            else:
+                pred, _ = self.localizer.fwd(x, training=False)
         finally:
             self.localizer.train(was)
         return ops.mask_threshold(pred, threshold)

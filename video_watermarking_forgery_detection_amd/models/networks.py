@@ -132,13 +132,23 @@ class UNetDiscriminator(BaseNetwork):
 
     `SRMConv2D.weight` is `srm_weight` [9,in_channels,5,5] (the reference reads it from a MantraNetv4.pt outside its tree) or, when None,
     default_srm_weight(); a load_state_dict replaces it.  It is a frozen parameter and, unlike in the reference (whose init_weights
-    re-draws it, :1022-1023 after :909), init_weights leaves it alone.  `dtype` is the activations' (float32, bfloat16, float16)."""
+    re-draws it, :1022-1023 after :909), init_weights leaves it alone.  `dtype` is the activations' (float32, bfloat16, float16).
+
+    fused_head (additional_conv=False only, out_channels <= 4): decoder_0, the sigmoid and the NCHW f32 conversion run as ONE launch that reads
+    e0 and d1 in place (glayers._Head2Fn) instead of concatenation, padded 1x1 convolution, activation pass and layout pass.  Same parameters
+    and state_dict keys; False keeps the separate launches."""
 
     def __init__(self, in_channels=3, out_channels=3, residual_blocks=8, init_weights=True, use_spectral_norm=True, use_SRM=True,
-                 with_attn=False, additional_conv=False, dim=32, use_sigmoid=False, dtype=torch.float32, srm_weight=None):
+                 with_attn=False, additional_conv=False, dim=32, use_sigmoid=False, dtype=torch.float32, srm_weight=None, fused_head=False):
         super().__init__()
         if with_attn:
             raise NotImplementedError("UNetDiscriminator(with_attn=True), the QF-conditioned variant, is not implemented")
+        if fused_head and additional_conv:
+            raise ValueError("UNetDiscriminator(fused_head=True) fuses the 1x1 decoder_0 of additional_conv=False; with additional_conv=True "
+                             "decoder_0 starts with a 3x3 convolution")
+        if fused_head and not 1 <= out_channels <= 4:
+            raise ValueError(f"UNetDiscriminator(fused_head=True) needs 1 <= out_channels <= 4 (the mask head's kernel), got {out_channels}")
+        self.fused_head = bool(fused_head)
         self.use_SRM, self.use_sigmoid, self.with_attn, self.additional_conv = use_SRM, use_sigmoid, with_attn, additional_conv
         self.in_channels, self.out_channels, self.dim, self.dtype = in_channels, out_channels, dim, dtype
         sn = use_spectral_norm
@@ -202,6 +212,10 @@ class UNetDiscriminator(BaseNetwork):
         m = self.middle(e2)
         d2 = self.decoder_2(G.chan_cat(e2, dim * 4, m, dim * 4))
         d1 = self.decoder_1(G.chan_cat(e1, dim * 2, d2, dim * 2))
+        if self.fused_head:    # decoder_0 + sigmoid + to_nchw in one launch that reads e0 and d1 in place (csrc/mask_head.hip)
+            head = self.decoder_0[0]
+            y = G._Head2Fn.apply(e0, dim, d1, dim, head.weight, head.bias, 1 if self.use_sigmoid else 0)
+            return y, (G.to_nchw(d2, dim * 2), G.to_nchw(d1, dim))
         y = self.decoder_0(G.chan_cat(e0, dim, d1, dim))
         if self.use_sigmoid:
             y = self._sigmoid(y)

@@ -804,6 +804,62 @@ def conv1x1_head_bwd(y, scale, shift, w, gout, dw, dbias, accumulate, want_bn_pa
     return g
 
 
+def _head2_args(name, a, na, b, nb, w, bias):
+    _need_cuda(a, b, w, bias)
+    if (a.dim() != 4 or b.dim() != 4 or a.shape[:3] != b.shape[:3] or a.dtype != b.dtype or not a.is_contiguous() or not b.is_contiguous()
+            or not 0 < na <= a.shape[3] or not 0 < nb <= b.shape[3]):
+        raise ValueError(f"{name}: a and b must be contiguous NHWC tensors of one dtype over the same pixels with 0 < na, nb <= their channel "
+                         f"strides, got {tuple(a.shape)} {a.dtype} / {tuple(b.shape)} {b.dtype}, na = {na}, nb = {nb}")
+    Cout = w.shape[0]
+    if w.dtype != torch.float32 or not w.is_contiguous() or w.numel() != Cout * (na + nb) or not 1 <= Cout <= 4:
+        raise ValueError(f"{name}: w must be contiguous f32 [Cout <= 4, {na + nb}(,1,1)], got {tuple(w.shape)} {w.dtype}")
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != Cout):
+        raise ValueError(f"{name}: bias must be contiguous f32 [{Cout}]")
+    return Cout
+
+
+def head2_fwd(a, na, b, nb, w, bias, act=0):
+    """act(conv1x1(cat(a[..., :na], b[..., :nb]), w, bias)) as NCHW f32 [B,Cout,H,W], read from the two NHWC sources in place (wm_head2_fwd);
+    w [Cout, na+nb(,1,1)] f32, Cout <= 4; act 0 none, 1 sigmoid"""
+    Cout = _head2_args("head2_fwd", a, na, b, nb, w, bias)
+    B, H, W, lda = a.shape
+    out = torch.empty(B, Cout, H, W, device=a.device, dtype=torch.float32)
+    rc = _lib.lib().wm_head2_fwd(_p(a), lda, na, _p(b), b.shape[3], nb, _p(w), _p(bias), _p(out), B, H * W, Cout, int(act), dtype_id(a), _stream())
+    _lib.check(rc, "wm_head2_fwd")
+    return out
+
+
+def head2_bwd(a, na, b, nb, w, gout, out=None, dw_acc=None, db_acc=None):
+    """-> (ga, gb, dw [Cout, na+nb], dbias [Cout]) of head2_fwd for gout f32 [B,Cout,H,W].  out: the saved forward result of act = 1 -- gout is
+    then the gradient wrt the sigmoid output; None: gout is the gradient wrt the logits.  dw_acc AND db_acc: contiguous f32 tensors the two
+    parameter gradients are ADDED to (the old values join the double sum before its one rounding)"""
+    Cout = _head2_args("head2_bwd", a, na, b, nb, w, None)
+    B, H, W, lda = a.shape
+    _need_cuda(gout, out)
+    if gout.dtype != torch.float32 or tuple(gout.shape) != (B, Cout, H, W) or (out is not None and (out.dtype != torch.float32 or out.shape != gout.shape)):
+        raise ValueError(f"head2_bwd: gout (and out) must be f32 [{B},{Cout},{H},{W}], got {tuple(gout.shape)} {gout.dtype}")
+    if (dw_acc is None) != (db_acc is None):
+        raise ValueError("head2_bwd: dw_acc and db_acc come together")
+    acc = dw_acc is not None
+    if acc and (not dw_acc.is_contiguous() or dw_acc.numel() != Cout * (na + nb) or dw_acc.dtype != torch.float32
+                or not db_acc.is_contiguous() or db_acc.numel() != Cout or db_acc.dtype != torch.float32):
+        raise ValueError("head2_bwd: accumulation targets do not match the gradients")
+    gout = gout.contiguous()
+    out = out.contiguous() if out is not None else None
+    L = _lib.lib()
+    nparts = L.wm_head2_nparts(B * H * W)
+    part = torch.empty(nparts, Cout * (na + nb + 1), device=a.device, dtype=torch.float64)
+    ga, gb = torch.empty_like(a), torch.empty_like(b)
+    rc = L.wm_head2_bwd(_p(a), lda, na, _p(b), b.shape[3], nb, _p(w), _p(gout), _p(out), 0 if out is None else 1, _p(ga), lda, _p(gb), b.shape[3],
+                        _p(part), B, H * W, Cout, dtype_id(a), _stream())
+    _lib.check(rc, "wm_head2_bwd")
+    dw = dw_acc if acc else torch.empty(Cout, na + nb, device=a.device, dtype=torch.float32)
+    db = db_acc if acc else torch.empty(Cout, device=a.device, dtype=torch.float32)
+    rc = L.wm_head2_finalize(_p(part), nparts, Cout, na + nb, _p(dw), _p(db), 1 if acc else 0, _stream())
+    _lib.check(rc, "wm_head2_finalize")
+    return ga, gb, dw, db
+
+
 # ----------------------------------------------------------------------------- losses / optimiser
 def mse_fwd_bwd(a, b, gscale, want_grad=True, gscale_dev=None):
     """returns (sum of squared differences partials [nparts], grad = gscale*(a-b))"""
