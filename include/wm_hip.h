@@ -672,6 +672,31 @@ int wm_coupling_fwd(const void* x, const void* s, const void* t, void* y, size_t
 int wm_coupling_bwd(const void* g, const void* v, const void* s, void* gx, void* gs, void* gt, size_t n, float clamp, float eps, int rev,
                     int dtype, void* stream);
 
+/* ------------------------------------------------------------------ instance normalisation (csrc/instnorm.hip)
+ * replaces nn.InstanceNorm2d(C, eps, affine, track_running_stats=False) and the nn.ReLU behind it: models/modules/Subnet_constructor.py:149-169
+ * (ResBlock, the coupling subnet 'Resnet'), models/conditional_jpeg_generator.py conv() letter I, models/networks.py's use_spectral_norm=False
+ * branches.  x, y, dy, dx: NHWC [B,hw,CP] of `dtype` (WM_F32 / WM_BF16 / WM_F16), 16-byte aligned, C real channels of a stride CP that is a
+ * multiple of 16 and at most 256 16-byte vectors (WM_E_SHAPE above); mean, rstd, mg, mgx: f32 [B][CP]; gamma, beta, dgamma, dbeta: f32 [C],
+ * NULL together for affine=False.  act 0 none, 1 ReLU.  partial: scratch of wm_instnorm_scratch_doubles(B, hw, CP) doubles.
+ * wm_instnorm_stats    : mean and rstd = 1 / sqrt(max(var, 0) + eps) of every (sample, channel) plane, biased variance; 0 in channels >= C.
+ * wm_instnorm_apply    : y = act((x - mean) * rstd * gamma + beta); channels >= C are written as zeros.
+ * wm_instnorm_bwd_sums : with g = dy * act'(y) (ReLU: y > 0 on the value as stored) and xhat = (x - mean) * rstd recomputed from x:
+ *                        mg = mean of g, mgx = mean of g * xhat per plane; dgamma = sum over samples and pixels of g * xhat, dbeta = of g.
+ * wm_instnorm_bwd_apply: dx = gamma * rstd * (g - mg - xhat * mgx); zeros in channels >= C.
+ * Every sum is accumulated in double in a fixed order (no atomics): two calls give the same bits.  A plane of more than 256 pixels is
+ * summed by wm_instnorm_splits(hw) workgroups (<= 64) whose partial sums a small second launch adds in order; so are dgamma / dbeta. */
+int wm_instnorm_splits(size_t hw);
+size_t wm_instnorm_scratch_doubles(int B, size_t hw, int CP);
+int wm_instnorm_stats(const void* x, double* partial, float* mean, float* rstd, int B, size_t hw, int C, int CP, double eps, int dtype,
+                      void* stream);
+int wm_instnorm_apply(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* y, int B, size_t hw,
+                      int C, int CP, int act, int dtype, void* stream);
+int wm_instnorm_bwd_sums(const void* x, const void* dy, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                         double* partial, float* mg, float* mgx, float* dgamma, float* dbeta, int B, size_t hw, int C, int CP, int act,
+                         int dtype, void* stream);
+int wm_instnorm_bwd_apply(const void* x, const void* dy, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                          const float* mg, const float* mgx, void* dx, int B, size_t hw, int C, int CP, int act, int dtype, void* stream);
+
 /* ------------------------------------------------------------------ losses of the literal IRNrhi step
  * replaces, in models/IRNrhi_model.py:425-560: nn.SmoothL1Loss (:148,476,481), nn.BCELoss (:147,492-493,505), nn.CrossEntropyLoss
  * (:156,454,485), torch.clamp(x,0,1) with its gradient mask (:430,472), PSNR of the postprocess()ed images (:527, metrics.py:30-46).

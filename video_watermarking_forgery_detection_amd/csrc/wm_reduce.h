@@ -18,6 +18,20 @@ __device__ __forceinline__ double block_sum_f64(double v, double* s) {
     return (s[0] + s[1]) + (s[2] + s[3]);
 }
 
+// per-channel sums of an NHWC stream: thread t of 256 holds, for the VE channels of channel vector t % nv, the partial sums of pixel slot
+// t / nv (slots = 256 / nv of them; threads past slots * nv take no part).  Afterwards threads t < nv hold in v[] the sums over the slots,
+// added in slot order.  sh: 256 * VE doubles of LDS.  Contains two __syncthreads(): sh may be reused at once
+template <int VE> __device__ __forceinline__ void slot_sum_f64(double (&v)[VE], double* sh, int nv, int slots) {
+#pragma unroll
+    for (int e = 0; e < VE; ++e) sh[threadIdx.x * VE + e] = v[e];
+    __syncthreads();
+    if ((int)threadIdx.x < nv)
+        for (int k = 1; k < slots; ++k)
+#pragma unroll
+            for (int e = 0; e < VE; ++e) v[e] += sh[(k * nv + threadIdx.x) * VE + e];
+    __syncthreads();
+}
+
 // [0, n) split for 16-byte access: a scalar head up to the first 16-byte boundary of `a`, nv float4s, a scalar tail.  The other pointers
 // (nullptr = absent) share the split only when they reach a boundary at the same element; otherwise (nv = 0) everything is scalar
 struct Split { size_t head, nv, tail0; };

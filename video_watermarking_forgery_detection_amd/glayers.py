@@ -601,6 +601,60 @@ class Act(nn.Module):
         return self.kind
 
 
+class _InstanceNormFn(Function):
+    """act(nn.InstanceNorm2d(x)) as one node: the forward keeps x and the f32 statistics [B,Cp] (not xhat, not the output); the backward
+    recomputes xhat and the ReLU mask from them (ops.instnorm_bwd)"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, C, eps, act):
+        gamma = weight.detach().contiguous() if weight is not None else None
+        beta = bias.detach().contiguous() if bias is not None else None
+        y, mean, rstd = ops.instnorm_fwd(x, C, eps, gamma, beta, act)
+        ctx.save_for_backward(x, mean, rstd, gamma, beta)
+        ctx.meta = (C, act)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, mean, rstd, gamma, beta = ctx.saved_tensors
+        C, act = ctx.meta
+        dx, dgamma, dbeta = ops.instnorm_bwd(x, g, C, mean, rstd, gamma, beta, act, want_params=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        return (dx if ctx.needs_input_grad[0] else None), (dgamma if ctx.needs_input_grad[1] else None), \
+            (dbeta if ctx.needs_input_grad[2] else None), None, None, None
+
+
+class InstanceNorm2d(nn.Module):
+    """nn.InstanceNorm2d(num_features, eps, momentum, affine, track_running_stats=False) on NHWC activations, optionally with the ReLU
+    the reference puts behind it (act="relu": one launch fewer each way, and no second activation kept for the backward).  Every
+    (sample, channel) plane is normalised with its own biased statistics, in training and in eval alike -- torch's behaviour without
+    running statistics, which this layer does not have (track_running_stats=True raises; the reference never sets it; `momentum` is
+    accepted and unused).  state_dict: `weight`, `bias` [num_features] when affine (ones / zeros at first), nothing otherwise."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=False, track_running_stats=False, act=None):
+        super().__init__()
+        if track_running_stats:
+            raise NotImplementedError("InstanceNorm2d: track_running_stats=True (running statistics) is not implemented")
+        if act not in ops.INSTNORM_ACTS:
+            raise ValueError(f"InstanceNorm2d: act {act!r} (None or 'relu')")
+        self.num_features, self.eps, self.momentum = int(num_features), float(eps), momentum
+        self.affine, self.track_running_stats, self.act = bool(affine), False, act
+        self.weight = nn.Parameter(torch.ones(self.num_features)) if self.affine else None
+        self.bias = nn.Parameter(torch.zeros(self.num_features)) if self.affine else None
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("the HIP layer toolkit runs on the GPU only; there is no CPU fallback")
+        if x.dim() != 4 or x.shape[3] != cpad(self.num_features):
+            raise ValueError(f"InstanceNorm2d expects an NHWC activation of {self.num_features} channels (stride {cpad(self.num_features)}), got {tuple(x.shape)}")
+        B, H, W, _ = x.shape
+        if H * W == 1:      # (torch's _verify_spatial_size; it checks whenever the input's own statistics are used: always, here)
+            raise ValueError(f"Expected more than 1 spatial element when training, got input size {torch.Size([B, self.num_features, H, W])}")
+        return _InstanceNormFn.apply(x, self.weight, self.bias, self.num_features, self.eps, self.act)
+
+    def extra_repr(self):
+        return f"{self.num_features}, eps={self.eps}, affine={self.affine}" + (f", act={self.act}" if self.act else "")
+
+
 class GlobalAvgPool(nn.Module):
     """torch.nn.AdaptiveAvgPool2d((1,1)); the result is f32 [B,1,1,Cp] and stays f32 through the Linear layers after it"""
 

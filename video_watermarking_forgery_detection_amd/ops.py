@@ -1802,6 +1802,89 @@ def coupling_bwd(g, v, s, clamp, eps, rev):
     return gx, gs, gt
 
 
+# ----------------------------------------------------------------------------- instance normalisation (csrc/instnorm.hip)
+INSTNORM_ACTS = {None: 0, "relu": 1}
+
+
+def _instnorm_args(name, x, C, gamma, beta, act):
+    x = _nhwc(x)
+    _need_cuda(gamma, beta)
+    if act not in INSTNORM_ACTS:
+        raise ValueError(f"{name}: act {act!r} (None or 'relu')")
+    if not 0 < C <= x.shape[3]:
+        raise ValueError(f"{name}: {C} channels in a stride of {x.shape[3]}")
+    if (gamma is None) != (beta is None):
+        raise ValueError(f"{name}: gamma and beta come together")
+    for t in (gamma, beta):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != C or not t.is_contiguous()):
+            raise ValueError(f"{name}: gamma / beta must be contiguous float32 [{C}]")
+    return x
+
+
+def instnorm_stats(x, C, eps=1e-5):
+    """(mean, rstd) f32 [B, Cp] of every (sample, channel) plane of x [B,H,W,Cp]: biased variance, rstd = 1 / sqrt(max(var, 0) + eps),
+    zeros in the padding channels; sums in double, fixed order"""
+    x = _instnorm_args("instnorm_stats", x, C, None, None, None)
+    B, H, W, CP = x.shape
+    L = _lib.lib()
+    part = torch.empty(L.wm_instnorm_scratch_doubles(B, H * W, CP), device=x.device, dtype=torch.float64)
+    mean = torch.empty(B, CP, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(B, CP, device=x.device, dtype=torch.float32)
+    rc = L.wm_instnorm_stats(_p(x), _p(part), _p(mean), _p(rstd), B, H * W, C, CP, float(eps), dt_id(x.dtype), _stream())
+    _lib.check(rc, "wm_instnorm_stats")
+    return mean, rstd
+
+
+def instnorm_apply(x, C, mean, rstd, gamma=None, beta=None, act=None):
+    """act((x - mean) * rstd * gamma + beta); padding channels written as zeros"""
+    x = _instnorm_args("instnorm_apply", x, C, gamma, beta, act)
+    B, H, W, CP = x.shape
+    y = torch.empty_like(x)
+    rc = _lib.lib().wm_instnorm_apply(_p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(y), B, H * W, C, CP, INSTNORM_ACTS[act], dt_id(x.dtype),
+                                      _stream())
+    _lib.check(rc, "wm_instnorm_apply")
+    return y
+
+
+def instnorm_fwd(x, C, eps=1e-5, gamma=None, beta=None, act=None):
+    """nn.InstanceNorm2d(C, eps, affine = gamma is not None)(x) (+ ReLU) -> (y, mean, rstd): two launches, three when a plane spans
+    several workgroups (ops.instnorm_splits)"""
+    mean, rstd = instnorm_stats(x, C, eps)
+    return instnorm_apply(x, C, mean, rstd, gamma, beta, act), mean, rstd
+
+
+def instnorm_bwd(x, dy, C, mean, rstd, gamma=None, beta=None, act=None, want_params=True):
+    """(dx, dgamma, dbeta) of instnorm_fwd for the output gradient dy; xhat and the ReLU mask are recomputed from x.  dgamma / dbeta f32 [C],
+    None without gamma or with want_params False"""
+    x = _instnorm_args("instnorm_bwd", x, C, gamma, beta, act)
+    _need_cuda(dy)
+    dy = dy.contiguous()
+    if dy.shape != x.shape or dy.dtype != x.dtype:
+        raise ValueError("instnorm_bwd: the output gradient does not match the input")
+    B, H, W, CP = x.shape
+    L = _lib.lib()
+    part = torch.empty(L.wm_instnorm_scratch_doubles(B, H * W, CP), device=x.device, dtype=torch.float64)
+    mg = torch.empty(B, CP, device=x.device, dtype=torch.float32)
+    mgx = torch.empty(B, CP, device=x.device, dtype=torch.float32)
+    dgamma = dbeta = None
+    if gamma is not None and want_params:
+        dgamma = torch.empty(C, device=x.device, dtype=torch.float32)
+        dbeta = torch.empty(C, device=x.device, dtype=torch.float32)
+    act_id, dt = INSTNORM_ACTS[act], dt_id(x.dtype)
+    rc = L.wm_instnorm_bwd_sums(_p(x), _p(dy), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(part), _p(mg), _p(mgx), _p(dgamma), _p(dbeta), B, H * W, C,
+                                CP, act_id, dt, _stream())
+    _lib.check(rc, "wm_instnorm_bwd_sums")
+    dx = torch.empty_like(x)
+    rc = L.wm_instnorm_bwd_apply(_p(x), _p(dy), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(mg), _p(mgx), _p(dx), B, H * W, C, CP, act_id, dt, _stream())
+    _lib.check(rc, "wm_instnorm_bwd_apply")
+    return dx, dgamma, dbeta
+
+
+def instnorm_splits(hw):
+    """workgroups that share one (sample) plane of hw pixels in the instance-norm kernels"""
+    return _lib.lib().wm_instnorm_splits(hw)
+
+
 # ----------------------------------------------------------------------------- losses of the literal IRNrhi step (SURVEY 8f row 1)
 def _nparts(n):
     return max(1, min(1024, (n + 4095) // 4096))
