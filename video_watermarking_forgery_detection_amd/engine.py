@@ -13,8 +13,10 @@ Data layout in HBM
   * image inputs: 3 channels zero-padded to 16 (one 32-byte bf16 pixel);
   * parameters / gradients / Adam moments: f32, one flat buffer per network.
 """
+import collections
 import contextlib
 import threading
+import types
 
 import torch
 
@@ -27,7 +29,7 @@ class Act:
 
     def __init__(self, t, C, scale=None, shift=None, rev=None, src=None):
         self.t, self.C, self.scale, self.shift = t, C, scale, shift
-        self.bwd = None   # backward: (g, partials, coef or None, g._version) left by the consumer's dgrad when it reduced this layer's BatchNorm sums
+        self.bwd = None   # backward: the BnSums the consumer's dgrad left when it reduced this layer's BatchNorm sums (leave_bn_sums / take_bn_sums)
         self.src = src    # (bn module, stats [4,CP]) of the ConvBNRelu that produced t (lets the consumer's backward finish this layer's statistics).
                           # NOT the layer's ctx: ctx.out -> Act -> src -> ctx would be a reference cycle, and a cycle keeps a step's 134 MB
                           # tensors alive until Python's cyclic collector runs -- the caching allocator then falls back to hipMalloc mid-step
@@ -160,150 +162,183 @@ def fin_rider(x, part, grads, accumulate):
                 dbeta=grads[pbn.bias], accumulate=accumulate)
 
 
+# A layer's BatchNorm-backward sums, reduced ahead of its backward by the kernel that produced `g`, the gradient wrt its output (the consumer's
+# input-gradient kernel, a 1x1 head's backward): valid for exactly that tensor at that version.  partials [n,2,CP] = sum(gz), sum(gz*y);
+# coef [3,CP]: finished already by a rider on the consumer's weight-gradient reduction (dgamma / dbeta written there), or None
+BnSums = collections.namedtuple("BnSums", "g partials coef version")
+
+
+def leave_bn_sums(act, g, partials, coef=None):
+    act.bwd = BnSums(g, partials, coef, g._version)
+
+
+def take_bn_sums(act, g):
+    """the sums left on `act` for the gradient g now handed to its layer, or None; nothing stays behind.  A different or edited g would use
+    stale sums or count dgamma / dbeta twice: refused, even where the coefficients come from elsewhere (coef_pre, pool_stats)"""
+    sums, act.bwd = act.bwd, None
+    if sums is not None and (sums.g is not g or g._version != sums.version):
+        raise RuntimeError("cbr_backward: the gradient handed to this layer is not the tensor its consumer's input-gradient "
+                           "kernel produced (or it was modified in place since); its pre-reduced BatchNorm sums are stale")
+    return sums
+
+
+# Two facts travel on a gradient tensor itself, since g crosses module boundaries bare: the sweep of the kernel that wrote it (its reader starts
+# where it stopped; forward when there is no tensor) and "already multiplied by its layer's ReLU mask" (written by ops._premasked)
+def sweep_after(g):
+    return g is not None and _opposite(getattr(g, "_wm_rev", None))
+
+
+def mark_sweep(gx, d):
+    gx._wm_rev = d
+    return gx
+
+
+def is_premasked(g):
+    return getattr(g, "_wm_masked", False)
+
+
+def select_bwd_route(f):
+    """name of the route cbr_backward takes for a layer with the facts f (bwd_facts: plain values, no tensors).  First match wins"""
+    plain = not f.permuted and f.stats_contig
+    if f.weight_grads and not f.need_input_grad and f.has_g and not f.fed_by_cbr and plain and f.wgrad_bnfused_ok:
+        return "first_layer_weights_only"   # conv1 of the encoder, the UNet, the discriminator in its own update, the decoder behind a zero gradient
+    if not f.weight_grads:                  # the discriminator under the generator's loss: nobody reads its weight gradients
+        if not f.need_input_grad:
+            return "bn_only"                # (no layer of a training step: dgamma / dbeta alone)
+        if f.has_gvec and plain and f.CoutY == 64 and f.feed_stats and f.gvfused_ok:
+            return "dx_only_pooled"         # its pooled last layer
+        if f.g_dense and plain and f.CoutY == 64 and f.rows in (64, 32) and f.applyfused_ok:
+            return "dx_only"                # its body layers (which feed sums) and its conv1 (32 rows)
+        return "dx_only_unfused"            # the same in f32 / shapes without a fused input-gradient kernel
+    if f.has_gvec and f.need_input_grad and f.fed_by_cbr and plain and f.rows == 64 and f.CinX == 64 and f.gvfused_ok:
+        if f.feed_stats and f.CoutY == 64 and f.bwd_fused_ok and f.gvec_cols == 64 and f.B <= f.gvec_max_batch:
+            return "pooled_onepass"         # the discriminator's last layer (64 -> 64) in its own update
+        return "pooled_feed" if f.feed_stats else "pooled"   # the decoder's last layer (64 -> 30), a batch above the one-pass limit / a sliced input
+    if f.g_dense and f.need_input_grad and not f.fed_by_cbr and plain and f.CoutY == 64 and f.bwd_fused16_ok:
+        return "first_layer_onepass"        # conv1 of the decoder and the discriminator when the image gets a gradient (whole 8x16 tiles)
+    if f.g_dense and f.need_input_grad and plain and f.rows in (64, 32) and f.CoutY == 64 and f.applyfused_ok:
+        if f.feed_stats and f.bwd_fused_ok and not f.keep_dy:
+            return "body_onepass"           # the 64 -> 64 body layers of every network, the UNet's 64-channel level
+        return "body_two_kernels"           # those beyond the one-pass kernel's 32-bit offsets or behind a pool; conv1 on partial tiles; keep_dy
+    return "generic"                        # f32 (parity), the unsplit after-concat layer (permuted), the UNet's other widths
+
+
+def bwd_facts(conv, ctx, g, gvec, need_input_grad, dgrad_channels, perm_dev, weight_grads, keep_dy=False):
+    """what select_bwd_route decides on, each computed once: plain values, no tensors.  keep_dy: the caller reads dy again afterwards"""
+    x, y = ctx.x, ctx.y
+    CinX, CoutY, dtype = x.t.shape[-1], y.shape[-1], y.dtype
+    rows = dgrad_channels or round_up(CinX, 32)                     # width of the input gradient
+    fed_by_cbr = x.scale is not None                                # the input is itself a ConvBNRelu output
+    permuted = ctx.perm is not None or perm_dev is not None         # the input is the encoder's permuted concat
+    g_dense = g is not None and g.shape == y.shape and g.is_contiguous()
+    # this layer's input-gradient kernel can reduce the FEEDING layer's BatchNorm-backward sums on the way
+    feed_stats = (need_input_grad and fed_by_cbr and not permuted and rows == 64 and CinX == 64 and x.t.is_contiguous()
+                  and ops.conv3x3_dgrad_bwdstats_supported(CoutY, rows, dtype))
+    # the library's answers, each asked only where select_bwd_route gets to it
+    bwd_fused_ok = feed_stats and CoutY == 64 and ops.conv3x3_bwd_fused_supported(dtype, y.shape)
+    bwd_fused16_ok = (g_dense and weight_grads and need_input_grad and not fed_by_cbr and CinX == 16 and dgrad_channels is None
+                      and conv.weight.shape[1] <= 16 and ops.conv3x3_bwd_fused16_supported(y.shape, dtype))    # an image filter, 16 channels back
+    return types.SimpleNamespace(
+        has_g=g is not None, has_gvec=gvec is not None, need_input_grad=need_input_grad, weight_grads=weight_grads, keep_dy=keep_dy,
+        fed_by_cbr=fed_by_cbr, permuted=permuted, rows=rows, CinX=CinX, CoutY=CoutY, dtype=dtype, B=y.shape[0], g_dense=g_dense,
+        gvec_cols=gvec.shape[-1] if gvec is not None else 0, feed_stats=feed_stats, stats_contig=ctx.stats.is_contiguous(),
+        wgrad_bnfused_ok=(weight_grads and not need_input_grad and g is not None and not fed_by_cbr and g.shape[-1] == CoutY
+                          and ops.conv3x3_wgrad_bnfused_supported(CinX, CoutY, dtype)),
+        gvfused_ok=gvec is not None and need_input_grad and ops.conv3x3_gvfused_supported(64, CoutY, dtype),
+        applyfused_ok=g_dense and need_input_grad and not bwd_fused16_ok and ops.conv3x3_dgrad_applyfused_supported(64, rows, dtype),
+        bwd_fused_ok=bwd_fused_ok, bwd_fused16_ok=bwd_fused16_ok,
+        gvec_max_batch=ops.conv3x3_bwd_fused_gvec_max_batch() if gvec is not None and bwd_fused_ok else 0)
+
+
 def cbr_backward(conv, bn, ctx, grads, g=None, gvec=None, need_input_grad=True, accumulate=False,
-                 dgrad_channels=None, perm_dev=None, pool_stats=None, weight_grads=True, coef_pre=None):
+                 dgrad_channels=None, perm_dev=None, pool_stats=None, weight_grads=True, coef_pre=None, slice_perms=None):
     """Backward of ConvBNRelu.  g: NHWC gradient wrt the ReLU output ([B,H,W,>=CoutP]) or gvec [B,CoutP]
     (global-average-pool gradient, already / (H*W)).  grads: dict param -> f32 grad view.
     Returns the NHWC gradient wrt the (activated) input, `dgrad_channels` wide (default: the input's
     physical channels rounded up to 32), or None.
     weight_grads=False: the input gradient alone -- conv.weight's gradient is neither computed nor touched (the BatchNorm affine
     gradients, a by-product of the backward coefficients, still are): the discriminator under the generator's loss, whose parameter
-    gradients nobody reads (hidden.py:67 zeroes them first thing in the next step)."""
+    gradients nobody reads (hidden.py:67 zeroes them first thing in the next step).
+    slice_perms: the encoder's split after-concat layer, an unpermuted 64 -> 64 layer whose filter is a channel slice of a wider one:
+    (that selection for the filter pack, the same for the weight gradient).  dy then stays in memory and (input gradient, dy) is returned."""
     if not ctx.training:
         raise RuntimeError("backward through eval-mode BatchNorm is not supported by the HIP path")
-    y, x = ctx.y, ctx.x
-    Cout = conv.weight.shape[0]
-    dtype = y.dtype
-    # The gradient of a conv bias in front of a training-mode BatchNorm is identically zero (sum(dy) == 0: the batch mean
-    # removes the bias); the reference's autograd produces rounding noise of ~1e-9 there.  The bias gradient view is
-    # zero-initialised and never written, which is the exact value and saves a reduction + two launches per layer.
-    dbias = None
-    # The dgrad that produced g (the next layer's, below) may have reduced this layer's sums in its epilogue already
-    pre, ctx.out.bwd = ctx.out.bwd, None
-    d = _opposite(getattr(g, "_wm_rev", None)) if g is not None else False   # this layer's input-gradient sweep
-
-    def tag(gx, direction=d):
-        gx._wm_rev = direction
-        return gx
-    gam, dgam, dbet = bn.weight.data, grads[bn.weight], grads[bn.bias]
+    f = bwd_facts(conv, ctx, g, gvec, need_input_grad, dgrad_channels, perm_dev, weight_grads, keep_dy=slice_perms is not None)
+    route = select_bwd_route(f)
+    x, y, stats = ctx.x, ctx.y, ctx.stats
+    xin = (x.t, x.scale, x.shift)
+    feed = xin if f.feed_stats else ()
+    bn_args = (y, stats, conv.weight.shape[0], bn.weight.data, grads[bn.weight], grads[bn.bias], accumulate)
+    dw = grads[conv.weight] if weight_grads else None
+    wperm, wgrad_perm = (ctx.perm, perm_dev) if slice_perms is None else slice_perms    # channel order of the filter pack / the weight gradient
+    sums = take_bn_sums(ctx.out, g)
+    d = sweep_after(g)                                  # this layer's input-gradient sweep
+    # the premasked tag (the staging then skips the mask arithmetic) is trusted only for the tensor a kernel returned, unmodified: the one with sums
+    premasked = sums is not None and is_premasked(g)
 
     def coef_of():
-        if gvec is not None and coef_pre is not None:     # finished already by the fused pooled head (ops.pooled_head: dgamma / dbeta written there)
+        """coefficients [3,CP] of the BatchNorm-backward apply pass; dgamma / dbeta are written on the way, or were by whoever finished them"""
+        if gvec is not None and coef_pre is not None:       # the fused pooled head (ops.pooled_head)
             return coef_pre
-        if gvec is not None and pool_stats is not None:   # (N+, S+) from the forward pool: no pass over y
-            return ops.bn_bwd_coef_pooled(gvec, pool_stats, y, ctx.stats, Cout, gam, dgam, dbet, accumulate)
-        if pre is not None:
-            # the consumer's input-gradient kernel already reduced this layer's sums over the tensor it returned: they are only
-            # valid for exactly that tensor, unmodified (a different or edited g would silently use stale sums, or -- when the
-            # rider already wrote dgamma / dbeta -- count them twice)
-            if g is None or pre[0] is not g or g._version != pre[3]:
-                raise RuntimeError("cbr_backward: the gradient handed to this layer is not the tensor its consumer's input-gradient "
-                                   "kernel produced (or it was modified in place since); its pre-reduced BatchNorm sums are stale")
-            if pre[2] is not None:   # finished already, as a rider on the next layer's weight-gradient reduction (dgamma / dbeta written there)
-                return pre[2]
-            return ops.bn_bwd_coef_raw(pre[1], y, ctx.stats, Cout, gam, dgam, dbet, accumulate)
-        return ops.bn_bwd_coef(g, gvec, y, ctx.stats, Cout, gam, dgam, dbet, accumulate)
+        if gvec is not None and pool_stats is not None:     # (N+, S+) from the forward pool: no pass over y
+            return ops.bn_bwd_coef_pooled(gvec, pool_stats, *bn_args)
+        if sums is None:
+            return ops.bn_bwd_coef(g, gvec, *bn_args)
+        if sums.coef is not None:                           # finished by a rider on the consumer's weight-gradient reduction
+            return sums.coef
+        return ops.bn_bwd_coef_raw(sums.partials, *bn_args)
 
-    # An image-fed first layer whose input needs no gradient: dy has ONE consumer, the weight gradient -- its kernel forms dy
-    # from (g, y) while staging the tile, so the apply pass (a write and a read of dy) disappears.
-    if (weight_grads and not need_input_grad and g is not None and x.scale is None and perm_dev is None and ctx.stats.is_contiguous()
-            and g.shape[-1] == y.shape[-1] and ops.conv3x3_wgrad_bnfused_supported(x.t.shape[-1], y.shape[-1], dtype)):
-        ops.conv3x3_wgrad_bnfused(x.t, g, y, ctx.stats, coef_of(), grads[conv.weight], accumulate)
-        return None
-    rows = dgrad_channels or round_up(x.t.shape[-1], 32)
-    # the input is itself a ConvBNRelu output: this layer's dgrad can reduce THAT layer's BatchNorm-backward sums on the way
-    feed_stats = (need_input_grad and x.scale is not None and perm_dev is None and ctx.perm is None and rows == 64
-                  and x.t.shape[-1] == 64 and x.t.is_contiguous() and ops.conv3x3_dgrad_bwdstats_supported(y.shape[-1], rows, dtype))
-    def rider(part):
-        """the feeding layer's BatchNorm-backward finalisation, to ride on this layer's weight-gradient slab reduction"""
-        if x.src is None or not ops.fin_rider_enabled():
-            return None
-        pbn, pstats = x.src
-        return dict(partials=part, y_shape=tuple(x.t.shape), stats=pstats, C=x.C, gamma=pbn.weight.data, dgamma=grads[pbn.weight],
-                    dbeta=grads[pbn.bias], accumulate=accumulate)
+    def wpt(cols=f.rows):
+        return _packed(conv, f.CoutY, cols, f.dtype, wperm, True)
+    def rider(part):    # the feeding layer's BatchNorm-backward finalisation, to ride on this layer's weight-gradient reduction
+        return None if part is None else fin_rider(x, part, grads, accumulate)
 
-    if not weight_grads:
-        if not need_input_grad:
-            coef_of()      # dgamma / dbeta only
-            return None
-        rows16 = ctx.perm is None and perm_dev is None and ctx.stats.is_contiguous() and y.shape[-1] == 64 and rows in (64, 32)
-        if gvec is not None and rows16 and rows == 64 and feed_stats and ops.conv3x3_gvfused_supported(64, 64, dtype):
-            gx, part = ops.conv3x3_dgrad_bwdstats(y, _packed(conv, 64, 64, dtype, None, True), x.t, x.scale, x.shift, gvec, ctx.stats, coef_of())
-            x.bwd = (gx, part, None, gx._version)
-            return tag(gx)
-        if g is not None and rows16 and g.shape == y.shape and g.is_contiguous() and ops.conv3x3_dgrad_applyfused_supported(64, rows, dtype):
-            wpt = _packed(conv, 64, rows, dtype, None, True)
-            if feed_stats and rows == 64:
-                _, gx, part = ops.conv3x3_dgrad_applyfused(g, y, ctx.stats, coef_of(), wpt, x.t, x.scale, x.shift, reverse=d, want_dy=False)
-                x.bwd = (gx, part, None, gx._version)
-            else:
-                _, gx, _ = ops.conv3x3_dgrad_applyfused(g, y, ctx.stats, coef_of(), wpt, reverse=d, want_dy=False)
-            return tag(gx)
-        # shapes / dtypes without a fused input-gradient kernel: the apply pass, then the plain input gradient
-        dy = ops.bn_bwd(g, gvec, y, ctx.stats, Cout, gam, dgam, dbet, accumulate, dbias, coef=coef_of())
-        gx, _ = ops.conv3x3_fwd(dy, _packed(conv, y.shape[-1], rows, dtype, ctx.perm, True), None, None, None, want_stats=False)
-        return tag(gx, False)
-    # A globally pooled layer (the gradient wrt its ReLU output is one row per sample): both consumers of dy -- the weight
-    # gradient and the input gradient -- form it from (gvec, y) while staging their tiles; no apply pass, no dy tensor.
-    if (gvec is not None and need_input_grad and x.scale is not None and perm_dev is None and ctx.perm is None and rows == 64
-            and x.t.shape[-1] == 64 and ctx.stats.is_contiguous() and ops.conv3x3_gvfused_supported(64, y.shape[-1], dtype)):
-        coef = coef_of()
-        wpt = _packed(conv, y.shape[-1], rows, dtype, None, True)
-        if (feed_stats and y.shape[-1] == 64 and ops.conv3x3_bwd_fused_supported(dtype, y.shape) and gvec.shape[-1] == 64
-                and y.shape[0] <= ops.conv3x3_bwd_fused_gvec_max_batch()):
-            # one kernel for both gradients (csrc/bwd_ws.hip, gvec form): y and the feeding layer's raw output are read once
-            gx, part, pcoef = ops.conv3x3_bwd_fused(None, y, ctx.stats, coef, wpt, x.t, x.scale, x.shift, grads[conv.weight], accumulate,
-                                                    fin=rider, gvec=gvec)
-            x.bwd = (gx, part, pcoef, gx._version)
-            return tag(gx)
-        if feed_stats:   # input gradient first: the sums it emits are finished by a rider on the weight gradient's reduction
-            gx, part = ops.conv3x3_dgrad_bwdstats(y, wpt, x.t, x.scale, x.shift, gvec, ctx.stats, coef)
-            pcoef = ops.conv3x3_wgrad_gvfused(x.t, x.scale, x.shift, gvec, y, ctx.stats, coef, grads[conv.weight], accumulate, fin=rider(part))
-            x.bwd = (gx, part, pcoef, gx._version)
-            return tag(gx)
-        ops.conv3x3_wgrad_gvfused(x.t, x.scale, x.shift, gvec, y, ctx.stats, coef, grads[conv.weight], accumulate)
-        return tag(ops.conv3x3_dgrad_gvfused(y, wpt, gvec, ctx.stats, coef))
-    # An image-fed first layer whose input needs a gradient too (the decoder's and the discriminator's conv1): one kernel forms dy from
-    # (g, y) once and feeds both the input gradient (16 channels, 3 real) and the weight gradient (csrc/bwd_ws16.hip); no dy tensor
-    if (g is not None and need_input_grad and x.scale is None and perm_dev is None and ctx.perm is None and dgrad_channels is None
-            and x.t.shape[-1] == 16 and y.shape[-1] == 64 and g.shape == y.shape and g.is_contiguous() and ctx.stats.is_contiguous()
-            and conv.weight.shape[1] <= 16 and ops.conv3x3_bwd_fused16_supported(y.shape, dtype)):
-        gx = ops.conv3x3_bwd_fused16(g, y, ctx.stats, coef_of(), _packed(conv, 64, 16, dtype, None, True), x.t, grads[conv.weight], accumulate,
-                                     reverse=d, premasked=pre is not None and getattr(g, "_wm_masked", False))
-        return tag(gx)
-    # An ordinary 64 -> 64 layer: the input-gradient kernel reads g and y, forms dy while staging and leaves it in memory
-    # for the weight gradient -- the stand-alone apply pass is gone.
-    if (g is not None and need_input_grad and perm_dev is None and ctx.perm is None and rows in (64, 32)
-            and y.shape[-1] == 64 and g.shape == y.shape and g.is_contiguous() and ctx.stats.is_contiguous()
-            and ops.conv3x3_dgrad_applyfused_supported(64, rows, dtype)):
-        coef = coef_of()
-        wpt = _packed(conv, 64, rows, dtype, None, True)
-        if feed_stats and rows == 64 and ops.conv3x3_bwd_fused_supported(dtype, y.shape):
-            # one kernel: dy is formed in the LDS and feeds BOTH gradients; the feeding layer's raw output is read once (csrc/bwd_ws.hip)
-            # (g itself may come from such a kernel, which writes its gradient already multiplied by this layer's ReLU mask: the staging
-            # then skips the mask arithmetic -- trusted only for exactly that tensor, unmodified: the check in coef_of())
-            gx, part, pcoef = ops.conv3x3_bwd_fused(g, y, ctx.stats, coef, wpt, x.t, x.scale, x.shift, grads[conv.weight], accumulate,
-                                                    reverse=d, fin=rider, premasked=pre is not None and getattr(g, "_wm_masked", False))
-            x.bwd = (gx, part, pcoef, gx._version)
-        elif feed_stats:
-            dy, gx, part = ops.conv3x3_dgrad_applyfused(g, y, ctx.stats, coef, wpt, x.t, x.scale, x.shift, reverse=d)
-            pcoef = ops.conv3x3_wgrad(x.t, x.t.shape[-1], x.scale, x.shift, dy, grads[conv.weight], accumulate, reverse=not d, fin=rider(part))
-            x.bwd = (gx, part, pcoef, gx._version)
-        else:
-            dy, gx, _ = ops.conv3x3_dgrad_applyfused(g, y, ctx.stats, coef, wpt, reverse=d)
-            ops.conv3x3_wgrad(x.t, x.t.shape[-1], x.scale, x.shift, dy, grads[conv.weight], accumulate, reverse=not d)
-        return tag(gx)
-    dy = ops.bn_bwd(g, gvec, y, ctx.stats, Cout, gam, dgam, dbet, accumulate, dbias, coef=coef_of())
-    ops.conv3x3_wgrad(x.t, x.t.shape[-1], x.scale, x.shift, dy, grads[conv.weight], accumulate, perm_dev=perm_dev, reverse=True)   # the apply pass swept forwards
-    if not need_input_grad:
-        return None
-    wpt = _packed(conv, y.shape[-1], rows, dtype, ctx.perm, True)
-    if feed_stats:
-        gx, part = ops.conv3x3_dgrad_bwdstats(dy, wpt, x.t, x.scale, x.shift)
-        x.bwd = (gx, part, None, gx._version)
-        return tag(gx, False)
-    gx, _ = ops.conv3x3_fwd(dy, wpt, None, None, None, want_stats=False)
-    return tag(gx, False)
+    def leave(gx, part=None, pcoef=None, direction=d):      # gx is the result: mark its sweep, leave the feeding layer's sums for who gets it
+        if part is not None:
+            leave_bn_sums(x, gx, part, pcoef)
+        return mark_sweep(gx, direction)
+
+    gx = dy = None
+    if route == "first_layer_weights_only":     # dy has ONE consumer, the weight gradient: its kernel forms dy from (g, y) while staging
+        ops.conv3x3_wgrad_bnfused(x.t, g, y, stats, coef_of(), dw, accumulate)
+    elif route == "bn_only":
+        coef_of()
+    elif route == "dx_only_pooled":
+        gx = leave(*ops.conv3x3_dgrad_bwdstats(y, wpt(), *xin, gvec, stats, coef_of()))
+    elif route == "dx_only":
+        packed = wpt()
+        _, gx, part = ops.conv3x3_dgrad_applyfused(g, y, stats, coef_of(), packed, *feed, reverse=d, want_dy=False)
+        gx = leave(gx, part)
+    elif route in ("pooled_onepass", "body_onepass"):
+        # one kernel (csrc/bwd_ws.hip): dy is formed in the LDS from (g or gvec, y) and feeds BOTH gradients; its input's raw tensor is read once
+        gx = leave(*ops.conv3x3_bwd_fused(g, y, stats, coef_of(), wpt(), *xin, dw, accumulate, reverse=d, fin=rider, premasked=premasked, gvec=gvec))
+    elif route == "pooled_feed":
+        # no apply pass: both kernels form dy from (gvec, y).  Input gradient first: a rider on the weight-gradient reduction finishes its sums
+        coef, packed = coef_of(), wpt()
+        gx, part = ops.conv3x3_dgrad_bwdstats(y, packed, *xin, gvec, stats, coef)
+        gx = leave(gx, part, ops.conv3x3_wgrad_gvfused(*xin, gvec, y, stats, coef, dw, accumulate, fin=rider(part)))
+    elif route == "pooled":
+        coef, packed = coef_of(), wpt()
+        ops.conv3x3_wgrad_gvfused(*xin, gvec, y, stats, coef, dw, accumulate)
+        gx = leave(ops.conv3x3_dgrad_gvfused(y, packed, gvec, stats, coef))
+    elif route == "first_layer_onepass":        # one kernel (csrc/bwd_ws16.hip) forms dy once for both gradients (the input's: 16 channels, 3 real)
+        gx = leave(ops.conv3x3_bwd_fused16(g, y, stats, coef_of(), wpt(16), x.t, dw, accumulate, reverse=d, premasked=premasked))
+    elif route == "body_two_kernels":
+        # the input-gradient kernel reads g and y, forms dy while staging and leaves it in memory for the weight gradient: no apply pass
+        coef, packed = coef_of(), wpt()
+        dy, gx, part = ops.conv3x3_dgrad_applyfused(g, y, stats, coef, packed, *feed, reverse=d)
+        pcoef = ops.conv3x3_wgrad(x.t, f.CinX, x.scale, x.shift, dy, dw, accumulate, perm_dev=wgrad_perm, reverse=not d, fin=rider(part))
+        gx = leave(gx, part, pcoef)
+    else:   # "dx_only_unfused", "generic": the stand-alone apply pass, then the plain kernels.  The gradient of a conv bias in front of a
+        # training-mode BatchNorm is identically zero (the batch mean removes the bias): its view is zero-initialised and never written
+        dy = ops.bn_bwd(g, gvec, *bn_args, None, coef=coef_of())
+        if weight_grads:
+            ops.conv3x3_wgrad(x.t, f.CinX, x.scale, x.shift, dy, dw, accumulate, perm_dev=wgrad_perm, reverse=True)   # the apply pass swept forwards
+        if need_input_grad and f.feed_stats and weight_grads:
+            gx = leave(*ops.conv3x3_dgrad_bwdstats(dy, wpt(), *xin), direction=False)
+        elif need_input_grad:
+            gx = leave(ops.conv3x3_fwd(dy, wpt(), None, None, None, want_stats=False)[0], direction=False)
+    return gx if slice_perms is None else (gx, dy)
 
 
 def grad_dict(module, flat_grad=None):

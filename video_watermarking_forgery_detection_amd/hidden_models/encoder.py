@@ -112,7 +112,7 @@ class Encoder(nn.Module, engine.FlatModule):
         g, bnp = ops.conv1x1_head_bwd(a5.t, a5.scale, a5.shift, fl.weight.data.view(3, c), g_enc,
                                       grads[fl.weight].view(3, c), grads[fl.bias], accumulate, want_bn_partials=True)
         if bnp is not None:
-            a5.bwd = (g, bnp, None, g._version)
+            engine.leave_bn_sums(a5, g, bnp)
         blk = self.after_concat_layer
         if ctx.split:
             g = self._after_concat_bwd_split(ctx, g, grads, accumulate)
@@ -134,50 +134,15 @@ class Encoder(nn.Module, engine.FlatModule):
         on its slab reduction) writing the feature channels of dW; the image channels of dW come from the image-fed weight-gradient
         kernel, the message channels from per-sample border-class sums of dy."""
         conv, bn = self.after_concat_layer.layers[0], self.after_concat_layer.layers[1]
-        cx = ctx.cat_ctx
-        y, x, dt = cx.y, cx.x, cx.y.dtype
-        dev = y.device
+        dt, dev = ctx.cat_ctx.y.dtype, ctx.cat_ctx.y.device
         if self._fperm_dev is None or self._fperm_dev.device != dev:
             self._fperm_dev = torch.tensor(self._fperm, dtype=torch.int32, device=dev)
             self._iperm_dev = torch.tensor(self._iperm, dtype=torch.int32, device=dev)
-        dw = grads[conv.weight]
-        pre, cx.out.bwd = cx.out.bwd, None
-        if pre is not None and pre[0] is g and g._version == pre[3]:    # sums already reduced by the head's backward
-            coef = ops.bn_bwd_coef_raw(pre[1], y, cx.stats, 64, bn.weight.data, grads[bn.weight], grads[bn.bias], accumulate)
-        else:
-            coef = ops.bn_bwd_coef(g, None, y, cx.stats, 64, bn.weight.data, grads[bn.weight], grads[bn.bias], accumulate)
-        wpt = engine._packed(conv, 64, 64, dt, self._fperm, True)
-        d = engine._opposite(getattr(g, "_wm_rev", None))
-        fused = ops.conv3x3_dgrad_applyfused_supported(64, 64, dt)
-        feed = fused and ops.conv3x3_dgrad_bwdstats_supported(64, 64, dt) and x.src is not None
-        if feed:
-            dy, gx, part = ops.conv3x3_dgrad_applyfused(g, y, cx.stats, coef, wpt, x.t, x.scale, x.shift, reverse=d)
-            pcoef = ops.conv3x3_wgrad(x.t, 64, x.scale, x.shift, dy, dw, accumulate, perm_dev=self._fperm_dev, reverse=not d,
-                                      fin=engine.fin_rider(x, part, grads, accumulate))
-            x.bwd = (gx, part, pcoef, gx._version)
-        else:
-            if fused:
-                dy, gx, _ = ops.conv3x3_dgrad_applyfused(g, y, cx.stats, coef, wpt, reverse=d)
-                ops.conv3x3_wgrad(x.t, 64, x.scale, x.shift, dy, dw, accumulate, perm_dev=self._fperm_dev, reverse=not d)
-            else:   # (debug build with the fusion switched off: the stand-alone apply pass, as engine.cbr_backward's generic branch)
-                dy = ops.bn_bwd(g, None, y, cx.stats, 64, bn.weight.data, grads[bn.weight], grads[bn.bias], accumulate, None, coef=coef)
-                ops.conv3x3_wgrad(x.t, 64, x.scale, x.shift, dy, dw, accumulate, perm_dev=self._fperm_dev, reverse=True)
-                if x.src is not None and ops.conv3x3_dgrad_bwdstats_supported(64, 64, dt):
-                    gx, part = ops.conv3x3_dgrad_bwdstats(dy, wpt, x.t, x.scale, x.shift)
-                    x.bwd = (gx, part, None, gx._version)
-                else:
-                    gx, _ = ops.conv3x3_fwd(dy, wpt, None, None, None, want_stats=False)
-                d = False
-        gx._wm_rev = d
+        gx, dy = engine.cbr_backward(conv, bn, ctx.cat_ctx, grads, g, accumulate=accumulate, slice_perms=(self._fperm, self._fperm_dev))
         img16 = engine.image_to_act(ctx.image, dt)
-        ops.conv3x3_wgrad(img16.t, 16, None, None, dy, dw, accumulate, perm_dev=self._iperm_dev)
-        ops.concat_side_msg_wgrad(dy, ctx.message, dw, accumulate, 0, self.message_length)
+        ops.conv3x3_wgrad(img16.t, 16, None, None, dy, grads[conv.weight], accumulate, perm_dev=self._iperm_dev)
+        ops.concat_side_msg_wgrad(dy, ctx.message, grads[conv.weight], accumulate, 0, self.message_length)
         return gx
-
-    def _bump_bn_counters(self):
-        for m in self.modules():
-            if isinstance(m, nn.BatchNorm2d) and m.num_batches_tracked is not None:
-                m.num_batches_tracked += 1
 
     # -- reference-style call (autograd) -------------------------------------------------------
     def forward(self, image, message):

@@ -457,6 +457,13 @@ def conv3x3_dgrad_gvfused(y, wpt, gvec, stats, coef):
     return dx
 
 
+def _premasked(dx):
+    """tag an input gradient whose kernel wrote gz = g * [z > 0] of the feeding layer (what the premasked staging of conv3x3_bwd_fused /
+    conv3x3_bwd_fused16 expects); read by engine.is_premasked"""
+    dx._wm_masked = True
+    return dx
+
+
 def conv3x3_dgrad_bwdstats_supported(CoutY, CinP, dtype):
     return bool(_lib.lib().wm_conv3x3_dgrad_bwdstats_supported(CoutY, CinP, dt_id(dtype)))
 
@@ -474,8 +481,7 @@ def conv3x3_dgrad_bwdstats(src, wpt, ry, r_scale, r_shift, gvec=None, stats=None
     rc = _lib.lib().wm_conv3x3_dgrad_bwdstats(_p(src), lds, CoutY, _p(wpt), _p(gvec), _p(stats), _p(coef), _p(ry), _p(r_scale), _p(r_shift), _p(dx),
                                               _p(part), B, H, W, CinP, dtype_id(src), _sweep(reverse), _stream())
     _lib.check(rc, "wm_conv3x3_dgrad_bwdstats")
-    dx._wm_masked = True   # the kernel writes gz = g * [z > 0] of the feeding layer (what conv3x3_bwd_fused's premasked staging expects)
-    return dx, part
+    return _premasked(dx), part
 
 
 def conv3x3_dgrad_applyfused_supported(CoutY, CinP, dtype):
@@ -498,9 +504,7 @@ def conv3x3_dgrad_applyfused(g, y, stats, coef, wpt, ry=None, r_scale=None, r_sh
         _p(g), _p(y), _p(stats), _p(coef), _p(wpt), _p(dy), _p(dx), _p(ry), _p(r_scale), _p(r_shift), _p(part), B, H, W, CinP, dtype_id(y),
         _sweep(reverse), _stream()))
     _lib.check(rc, "wm_conv3x3_dgrad_applyfused")
-    if ry is not None:
-        dx._wm_masked = True   # as conv3x3_dgrad_bwdstats
-    return dy, dx, part
+    return dy, _premasked(dx) if ry is not None else dx, part
 
 
 def conv3x3_bwd_fused_supported(dtype, shape=None):
@@ -540,8 +544,7 @@ def conv3x3_bwd_fused(g, y, stats, coef, wpt, xr, in_scale, in_shift, dw, accumu
     rc = L.wm_conv3x3_bwd_fused_reduce(_p(ws), _p(dw), 1 if accumulate else 0, B, H, W, Cin, Cout, ctypes.byref(fst) if fst is not None else None,
                                        _stream())
     _lib.check(rc, "wm_conv3x3_bwd_fused_reduce")
-    dx._wm_masked = True
-    return dx, part, fcoef
+    return _premasked(dx), part, fcoef
 
 
 def conv3x3_bwd_fused16_supported(shape, dtype):
