@@ -17,58 +17,12 @@
 // LDS layouts: 128-byte pixel rows.  The dy halo is read BOTH by the input gradient's ds_read_b128 (16 consecutive pixels, one 16-byte
 // slot each) and by the weight gradient's transposing ds_read_b64_tr_b16 (pixels {c..c+3, c+8..c+11}, 32 bytes each); the 16-byte slot
 // index is XORed with fsw(px) = bit2(px) | bit1(px) << 1 | bit3(px) << 2 -- a bit permutation of (px >> 1) & 7, so 16 consecutive
-// pixels hit 16 distinct slots, and its upper two bits are wgrad_ws.hip's swz16, so the transposing reads fill a bank row exactly once.
+// pixels hit 16 distinct slots, and its upper two bits are swz16 (wm_mfma.h, where fsw is defined and the relation asserted), so the
+// transposing reads fill a bank row exactly once.  What this kernel shares with bwd_ws8.hip is defined in bwd_onepass.h.
 #include <type_traits>
-#include "wm_common.h"
-
-#ifdef WM_H16_F16
-typedef f16_t hx_t;
-#define WM_HSYM(name) name##_f16
-#else
-typedef bf16_t hx_t;
-#define WM_HSYM(name) name##_bf16
-#endif
-typedef h16<hx_t> HX;
-typedef HX::x8 hx8;
-typedef HX::x2 hx2;
+#include "bwd_onepass.h"
 
 namespace {
-
-constexpr int TH = 8, TW = 16, HH = 10, HW = 18, NPX = HH * HW, C = 64;
-constexpr int SW_BYTES = 9 * C * C * 2, SDY_BYTES = NPX * 128, SA_BYTES = TH * TW * 128, BUF_BYTES = SDY_BYTES + SA_BYTES;
-constexpr int XV = (NPX * 8 + 255) / 256;        // dy halo vectors per thread (6; the last one partially live)
-constexpr int AV = TH * TW * 8 / 256;            // a-tile vectors per thread (4)
-constexpr int GV_MAXB = 24;                      // GVEC: samples whose k3g rows fit the LDS left over (24 x 256 B)
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-struct BwdArgs {
-    const hx_t* g; const hx_t* y;                          // layer L: gradient wrt its ReLU output, its raw conv output [B,H,W,64]
-    const float* gvec; int gv_ld;                          // GVEC: the gradient is one row per sample [B][gv_ld] (a globally pooled layer); g unused
-    const float* stats4; int st_ld; const float* coef;     // [scale | shift | mean | invstd][st_ld], wm_bn_bwd_finalize's coef [3][st_ld]
-    const hx_t* wpt;                                       // [9][64][64] filter packed for the input gradient (rows = input channels)
-    const hx_t* xr; const float* in_scale; const float* in_shift;   // layer L-1: raw conv output, its BatchNorm scale / shift
-    hx_t* dx;                                              // [B,H,W,64]
-    float* stat;                                           // [gridDim.x][2][64]
-    float* ws;                                             // [gridDim.x][9][64][64]
-    int B, H, W, tilesX, tilesY, ntiles, reverse;
-    unsigned mX, mY, m2X;                                  // ceil(2^32 / d) of tilesX, tilesY, 2 tilesX (0 for d = 1): tile index / d = mulhi
-};
-
-__device__ __forceinline__ int fsw(int px) { return ((px >> 2) & 1) | (((px >> 1) & 1) << 1) | (((px >> 3) & 1) << 2); }
-__device__ __forceinline__ int swz16(int col) { return (((col >> 1) & 1) << 5) | (((col >> 3) & 1) << 6); }
-__device__ __forceinline__ int swzw(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ hx8 tr_frag(const char* p0, const char* p1) {
-    typedef short s4 __attribute__((ext_vector_type(4)));
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p0));
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p1));
-    typedef short s8 __attribute__((ext_vector_type(8)));
-    s8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(hx8, v);
-}
 
 // PREMASKED: g arrives already multiplied by its layer's ReLU mask (this kernel's own dx is written that way, see the epilogue), so the
 // staging's compare + select + the z fma disappear; masking twice is the identity, so results do not depend on the flag
@@ -82,13 +36,13 @@ __device__ __forceinline__ hx8 tr_frag(const char* p0, const char* p1) {
 // choice among four per-thread bit masks (top / bottom / left / right edge), and the a tile needs no masking at all.
 template <bool PREMASKED, bool GVEC = false, bool ALIGNED = false>
 __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[SW_BYTES + 2 * BUF_BYTES + 4 * 2 * C * 4 + 2 * C * 4 + (C * 8 + 32) * 4 + (GVEC ? GV_MAXB * C * 4 : 0)];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES<GVEC>];   // (the carve-up: bwd_onepass.h)
     hx_t* sW = reinterpret_cast<hx_t*>(smem);
-    unsigned char* sBuf = smem + SW_BYTES;
-    float* sRed = reinterpret_cast<float*>(smem + SW_BYTES + 2 * BUF_BYTES);
-    float* sTab = sRed + 4 * 2 * C;   // in_scale | in_shift of the feeding layer (the epilogue's mask)
-    float* sG = sTab + 2 * C + C * 8 + 32;   // GVEC: [B][64] k3 + ca * gvec[b][c]
-    float* sK = sTab + 2 * C;         // per channel: scale, shift, ca, k2, k3 (wm_bn_fold) of layer L; in_scale, in_shift of layer L-1; 0
+    unsigned char* sBuf = smem + LDS_BUF;
+    float* sRed = reinterpret_cast<float*>(smem + LDS_RED);
+    float* sTab = reinterpret_cast<float*>(smem + LDS_TAB);   // in_scale | in_shift of the feeding layer (the epilogue's mask)
+    float* sK = reinterpret_cast<float*>(smem + LDS_K);       // the per-channel constant table (onepass_commit_consts)
+    float* sG = reinterpret_cast<float*>(smem + LDS_G);       // GVEC: [B][64] k3 + ca * gvec[b][c]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < C) {
         sTab[tid] = a.in_scale[tid]; sTab[C + tid] = a.in_shift[tid];
@@ -117,13 +71,13 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
                 const int i = tid + 256 * (9 * half + k);
                 const int row = i >> 3, tap = row / C, n = row % C;
                 const int lrow = tap * C + ((n >> 2) & 3) * 16 + 4 * (n >> 4) + (n & 3);
-                *reinterpret_cast<hx8*>(sW + lrow * C + swzw(lrow, i & 7) * 8) = wv[k];
+                *reinterpret_cast<hx8*>(sW + lrow * C + swz128(lrow, i & 7) * 8) = wv[k];
             }
         }
     }
     // ---- run of tiles (XCD-aware: workgroups b and b+8 share an L2, give each XCD consecutive runs)
     const int G = gridDim.x;
-    const int run = (G & 7) == 0 ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int run = wm_xcd_run(G, blockIdx.x);
     const int t_begin = (int)(((long)run * a.ntiles) / G), t_end = (int)(((long)(run + 1) * a.ntiles) / G);
     struct TileGeo { int b, ty0, tx0; };
     // tile order: pairs of tile rows walked column by column (upper tile, lower tile, next column ...), so the two halo rows a tile
@@ -300,7 +254,7 @@ __global__ __launch_bounds__(256, 1) void bwd_ws_kernel(BwdArgs a) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) aoff[kw][ks] = ((wave * 2 * HW + p + kw) * 128) + (((ks * 4 + q) ^ fsw(p + kw)) << 4);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) boff[ks] = (p * C + swzw(p, ks * 4 + q) * 8) * 2;
+    for (int ks = 0; ks < 2; ++ks) boff[ks] = (p * C + swz128(p, ks * 4 + q) * 8) * 2;
     float s1[16], s2[16];
 #pragma unroll
     for (int c = 0; c < 16; ++c) { s1[c] = 0.f; s2[c] = 0.f; }
@@ -670,13 +624,7 @@ void WM_HSYM(wm_launch_bwd_ws)(const void* g, const void* y, const float* stats4
                                const float* in_scale, const float* in_shift, void* dx, float* stat, float* ws, int B, int H, int W, int nwg,
                                int reverse, hipStream_t s, int premasked, const float* gvec, int gv_ld) {
     BwdArgs a;
-    a.g = (const hx_t*)g; a.y = (const hx_t*)y; a.stats4 = stats4; a.st_ld = st_ld; a.coef = coef; a.wpt = (const hx_t*)wpt;
-    a.gvec = gvec; a.gv_ld = gv_ld;
-    a.xr = (const hx_t*)xr; a.in_scale = in_scale; a.in_shift = in_shift; a.dx = (hx_t*)dx; a.stat = stat; a.ws = ws;
-    a.B = B; a.H = H; a.W = W; a.tilesX = wm_cdiv(W, TW); a.tilesY = wm_cdiv(H, TH); a.ntiles = B * a.tilesX * a.tilesY;
-    auto magic = [](int d) { return d == 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); };
-    a.mX = magic(a.tilesX); a.mY = magic(a.tilesY); a.m2X = magic(2 * a.tilesX);
-    a.reverse = reverse ? 1 : 0;
+    onepass_fill_args(a, g, y, stats4, st_ld, coef, wpt, xr, in_scale, in_shift, dx, stat, ws, B, H, W, reverse, gvec, gv_ld);
     const bool aligned = H % TH == 0 && W % TW == 0;
     if (aligned) {
         if (gvec) hipLaunchKernelGGL((bwd_ws_kernel<false, true, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);

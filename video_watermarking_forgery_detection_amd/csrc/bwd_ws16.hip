@@ -7,7 +7,7 @@
 // from ONE staged dy halo tile.  The two-kernel form (conv3x3_ws.hip <64,32,..,BNBWD = 2> + wgrad_ws.hip <16,..,0>) reads (g, y) to form
 // dy, writes dy (134 MB at B = 16, 256x256) and reads it back for the weight gradient: 470 + 167 MB; this kernel moves 268 + 33 + 33 MB.
 //
-// It is csrc/bwd_ws.hip's scheme (same LDS layout of the dy halo: 128-byte pixel rows, 16-byte slots XORed with fsw(px), read both by the
+// It is csrc/bwd_ws.hip's scheme (same LDS layout of the dy halo: 128-byte pixel rows, 16-byte slots XORed with wm_mfma.h's fsw(px), read both by the
 // input gradient's ds_read_b128 and by the weight gradient's transposing ds_read_b64_tr_b16) with two differences that follow from the
 // shapes.  (1) Both GEMMs are tiny -- 36 + 36 MFMAs per wave and tile against 144 + 144 -- so the kernel is bound by the staging and by
 // memory, not by the matrix pipe: instead of hand-interleaving the staging with the MFMAs, a workgroup needs so little LDS (75 KB) and so
@@ -15,18 +15,8 @@
 // ([channel][pixel], 8 two-byte writes per thread and tile) so that the weight gradient's B operand is a plain 16-byte read.
 // Whole-tile shapes only (H % 8 == 0, W % 16 == 0: buffer addressing with per-thread constant offsets, as bwd_ws.hip's ALIGNED form);
 // other shapes keep the two-kernel form.
-#include "wm_common.h"
+#include "wm_mfma.h"
 
-#ifdef WM_H16_F16
-typedef f16_t hx_t;
-#define WM_HSYM(name) name##_f16
-#else
-typedef bf16_t hx_t;
-#define WM_HSYM(name) name##_bf16
-#endif
-typedef h16<hx_t> HX;
-typedef HX::x8 hx8;
-typedef HX::x2 hx2;
 
 namespace {
 
@@ -38,9 +28,6 @@ constexpr int SX_BYTES = CX * XROW;
 constexpr int BUF_BYTES = SDY_BYTES + SX_BYTES;
 constexpr int XV = (NPX * 8 + 255) / 256;         // dy halo vectors per thread (6; the last one partially live)
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 struct Bwd16Args {
     const hx_t* g; const hx_t* y;                 // layer 1: gradient wrt its ReLU output, its raw conv output [B,H,W,64]
     const float* stats4; int st_ld; const float* coef;
@@ -50,18 +37,6 @@ struct Bwd16Args {
     float* ws;                                    // [gridDim.x][9][16][64]
     int B, H, W, tilesX, tilesY, ntiles, reverse;
 };
-
-__device__ __forceinline__ int fsw(int px) { return ((px >> 2) & 1) | (((px >> 1) & 1) << 1) | (((px >> 3) & 1) << 2); }
-__device__ __forceinline__ int swzw(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ hx8 tr_frag(const char* p0, const char* p1) {
-    typedef short s4 __attribute__((ext_vector_type(4)));
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p0));
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p1));
-    typedef short s8 __attribute__((ext_vector_type(8)));
-    s8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(hx8, v);
-}
 
 // PREMASKED: g arrives already multiplied by the layer's ReLU mask (what every gradient-producing kernel of this library writes)
 template <bool PREMASKED>
@@ -78,7 +53,7 @@ __global__ __launch_bounds__(256, 2) void bwd_ws16_kernel(Bwd16Args a) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) sK[tid * 8 + (tid >> 3) * 4 + i] = v[i];   // (8-channel blocks shifted by 16 B: bwd_ws.hip's bank spread)
     }
-    // ---- filter -> LDS: row = tap * 16 + image channel, 64 dy channels = 8 sixteen-byte slots, slot XORed with swzw(row)
+    // ---- filter -> LDS: row = tap * 16 + image channel, 64 dy channels = 8 sixteen-byte slots, slot swizzled by swz128(row, .) (wm_mfma.h)
     // (all loads in flight, then the stores: a `load, wait, store` loop runs its trips one L2 round trip after the other)
     {
         constexpr int NV = 9 * CX * 8, WV = (NV + 255) / 256;
@@ -91,11 +66,13 @@ __global__ __launch_bounds__(256, 2) void bwd_ws16_kernel(Bwd16Args a) {
 #pragma unroll
         for (int k = 0; k < WV; ++k) {
             const int i = tid + 256 * k, row = i >> 3;
-            if (i < NV) *reinterpret_cast<hx8*>(sW + row * C + swzw(row, i & 7) * 8) = wv[k];
+            if (i < NV) *reinterpret_cast<hx8*>(sW + row * C + swz128(row, i & 7) * 8) = wv[k];
         }
     }
     const int G = gridDim.x;
-    const int run = (G & 7) == 0 ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;   // XCD-aware: consecutive runs per XCD
+    // XCD-aware: consecutive runs per XCD.  (wm_common.h's wm_xcd_run, written out: through the function this kernel's compare-and-branch
+    // on G & 7 comes out inverted and three instructions move -- no difference in cost, but the kernels here change only with identical code)
+    const int run = (G & 7) == 0 ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
     const int t_begin = (int)(((long)run * a.ntiles) / G), t_end = (int)(((long)(run + 1) * a.ntiles) / G);
     struct TileGeo { int b, ty0, tx0; };
     auto geo = [&](int tile) {   // pairs of tile rows walked column by column (bwd_ws.hip's order; tilesY odd: row-major)
@@ -201,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void bwd_ws16_kernel(Bwd16Args a) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) aoff[kw][ks] = ((wave * 2 * HW + p + kw) * 128) + (((ks * 4 + q) ^ fsw(p + kw)) << 4);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) boff[ks] = (p * C + swzw(p, ks * 4 + q) * 8) * 2;
+    for (int ks = 0; ks < 2; ++ks) boff[ks] = (p * C + swz128(p, ks * 4 + q) * 8) * 2;
     const unsigned eofs = (unsigned)(((wave * 2 * a.W + p) * CX + 4 * q) * 2);   // this lane's 4 channels of output pixel (row 2 wave, column p)
 
     // ================================================================== weight-gradient role: wave w owns dy channels [16w, 16w + 16) x 16 image channels x 9 taps

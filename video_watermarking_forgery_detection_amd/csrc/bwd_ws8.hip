@@ -16,67 +16,19 @@
 // not live in the other's loop) and meet at the one barrier per tile.  Whole-tile shapes only (buffer addressing as bwd_ws.hip's ALIGNED
 // form); everything else stays on bwd_ws.hip.
 #include <type_traits>
-#include "wm_common.h"
-
-#ifdef WM_H16_F16
-typedef f16_t hx_t;
-#define WM_HSYM(name) name##_f16
-#else
-typedef bf16_t hx_t;
-#define WM_HSYM(name) name##_bf16
-#endif
-typedef h16<hx_t> HX;
-typedef HX::x8 hx8;
-typedef HX::x2 hx2;
+#include "bwd_onepass.h"   // the tile constants, Bwd8Args, the LDS carve-up, the launchers' argument fill
 
 namespace {
 
-constexpr int TH = 8, TW = 16, HH = 10, HW = 18, NPX = HH * HW, C = 64;
-constexpr int SW_BYTES = 9 * C * C * 2, SDY_BYTES = NPX * 128, SA_BYTES = TH * TW * 128, BUF_BYTES = SDY_BYTES + SA_BYTES;
-constexpr int XV = (NPX * 8 + 255) / 256;        // dy halo vectors per D thread (6; the last one partially live)
-constexpr int AV = TH * TW * 8 / 256;            // a-tile vectors per W thread (4)
-constexpr int GV_MAXB = 24;
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-struct Bwd8Args {
-    const hx_t* g; const hx_t* y;
-    const float* gvec; int gv_ld;
-    const float* stats4; int st_ld; const float* coef;
-    const hx_t* wpt;
-    const hx_t* xr; const float* in_scale; const float* in_shift;
-    hx_t* dx;
-    float* stat;                                           // [gridDim.x][2][64]
-    float* ws;                                             // [gridDim.x][9][64][64]
-    int B, H, W, tilesX, tilesY, ntiles, reverse;
-    int tq, trem;                                          // ntiles / gridDim.x, ntiles % gridDim.x
-    unsigned mX, mY, m2X;
-};
-
-__device__ __forceinline__ int fsw(int px) { return ((px >> 2) & 1) | (((px >> 1) & 1) << 1) | (((px >> 3) & 1) << 2); }
-__device__ __forceinline__ int swz16(int col) { return (((col >> 1) & 1) << 5) | (((col >> 3) & 1) << 6); }
-__device__ __forceinline__ int swzw(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ hx8 tr_frag(const char* p0, const char* p1) {
-    typedef short s4 __attribute__((ext_vector_type(4)));
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p0));
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p1));
-    typedef short s8 __attribute__((ext_vector_type(8)));
-    s8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(hx8, v);
-}
-
 template <bool PREMASKED, bool GVEC>
 __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[SW_BYTES + 2 * BUF_BYTES + 4 * 2 * C * 4 + 2 * C * 4 + (C * 8 + 32) * 4 + (GVEC ? GV_MAXB * C * 4 : 0)];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES<GVEC>];   // (the carve-up: bwd_onepass.h)
     hx_t* sW = reinterpret_cast<hx_t*>(smem);
-    unsigned char* sBuf = smem + SW_BYTES;
-    float* sRed = reinterpret_cast<float*>(smem + SW_BYTES + 2 * BUF_BYTES);
-    float* sTab = sRed + 4 * 2 * C;          // in_scale | in_shift of the feeding layer
-    float* sK = sTab + 2 * C;                // per channel: scale, shift, ca, k2, k3 of layer L; in_scale, in_shift of layer L-1; 0
-    float* sG = sK + C * 8 + 32;             // GVEC: [B][64] k3 + ca * gvec[b][c]
+    unsigned char* sBuf = smem + LDS_BUF;
+    float* sRed = reinterpret_cast<float*>(smem + LDS_RED);
+    float* sTab = reinterpret_cast<float*>(smem + LDS_TAB);   // in_scale | in_shift of the feeding layer
+    float* sK = reinterpret_cast<float*>(smem + LDS_K);       // per channel: scale, shift, ca, k2, k3 of layer L; in_scale, in_shift of layer L-1; 0
+    float* sG = reinterpret_cast<float*>(smem + LDS_G);       // GVEC: [B][64] k3 + ca * gvec[b][c]
     const int tid = threadIdx.x, lane = tid & 63;
     const bool wrole = tid >= 256;           // waves 4..7: the weight gradient
     const int rt = tid & 255, wave = rt >> 6;   // index inside the role
@@ -109,11 +61,11 @@ __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
             const int i = tid + 512 * k;
             const int row = i >> 3, tap = row / C, n = row % C;
             const int lrow = tap * C + ((n >> 2) & 3) * 16 + 4 * (n >> 4) + (n & 3);
-            *reinterpret_cast<hx8*>(sW + lrow * C + swzw(lrow, i & 7) * 8) = wv[k];
+            *reinterpret_cast<hx8*>(sW + lrow * C + swz128(lrow, i & 7) * 8) = wv[k];
         }
     };
     const int G = gridDim.x;
-    const int run = (G & 7) == 0 ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int run = wm_xcd_run(G, blockIdx.x);
     // run r takes tiles [r q + min(r, rem), ...): q = ntiles / G, rem = ntiles % G from the host (no 64-bit division in the prologue)
     const int t_begin = run * a.tq + min(run, a.trem), t_end = t_begin + a.tq + (run < a.trem ? 1 : 0);
     struct TileGeo { int b, ty0, tx0; };
@@ -383,7 +335,7 @@ __global__ __launch_bounds__(512, 1) void bwd_ws8_kernel(Bwd8Args a) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) aoff[kw][ks] = ((wave * 2 * HW + p + kw) * 128) + (((ks * 4 + q) ^ fsw(p + kw)) << 4);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) boff[ks] = (p * C + swzw(p, ks * 4 + q) * 8) * 2;
+    for (int ks = 0; ks < 2; ++ks) boff[ks] = (p * C + swz128(p, ks * 4 + q) * 8) * 2;
     const unsigned eofs = (unsigned)(((wave * 2 * a.W + p) * C + 16 * q) * 2);
     float s1[16], s2[16];
 #pragma unroll
@@ -549,14 +501,8 @@ int WM_HSYM(wm_launch_bwd_ws8)(const void* g, const void* y, const float* stats4
                                 const float* in_scale, const float* in_shift, void* dx, float* stat, float* ws, int B, int H, int W, int nwg,
                                 int reverse, hipStream_t s, int premasked, const float* gvec, int gv_ld) {
     Bwd8Args a;
-    a.g = (const hx_t*)g; a.y = (const hx_t*)y; a.stats4 = stats4; a.st_ld = st_ld; a.coef = coef; a.wpt = (const hx_t*)wpt;
-    a.gvec = gvec; a.gv_ld = gv_ld;
-    a.xr = (const hx_t*)xr; a.in_scale = in_scale; a.in_shift = in_shift; a.dx = (hx_t*)dx; a.stat = stat; a.ws = ws;
-    a.B = B; a.H = H; a.W = W; a.tilesX = W / TW; a.tilesY = H / TH; a.ntiles = B * a.tilesX * a.tilesY;
-    auto magic = [](int d) { return d == 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); };
-    a.mX = magic(a.tilesX); a.mY = magic(a.tilesY); a.m2X = magic(2 * a.tilesX);
+    onepass_fill_args(a, g, y, stats4, st_ld, coef, wpt, xr, in_scale, in_shift, dx, stat, ws, B, H, W, reverse, gvec, gv_ld);
     a.tq = a.ntiles / nwg; a.trem = a.ntiles % nwg;
-    a.reverse = reverse ? 1 : 0;
     // (the unmasked-gradient form is not instantiated: it needs ~15 registers more than a two-waves-per-SIMD kernel has and stays on
     // bwd_ws.hip -- wgrad.hip dispatches.  Both instantiated forms: 250 registers, no scratch.)  An unmasked tensor gradient handed to
     // this launcher would be staged WITHOUT its ReLU mask: refused here, whatever the caller's dispatch condition says

@@ -11,23 +11,12 @@
 // Backward: the feature part is an ordinary 64 -> 64 layer; dW of the image channels comes from the image-fed weight-gradient kernel;
 // dW of message channel l at tap t is sum_b m[b,l] * S[b,t,:] with S[b,t,:] = the sum of dy over the pixels for which tap t is inside
 // the image -- per-sample sums of dy over the 9 border classes (dy_total / border kernels below).
-#include "wm_common.h"
+#include "wm_mfma.h"
 
-// compiled twice (build.py): the 16-bit activation dtype of P / dy is bf16, or f16 with -DWM_H16_F16
-#ifdef WM_H16_F16
-typedef f16_t hx_t;
-#define WM_HSYM(name) name##_f16
-#else
-typedef bf16_t hx_t;
-#define WM_HSYM(name) name##_bf16
-#endif
-typedef h16<hx_t> HX;
-typedef HX::x8 hx8;
 
 namespace {
 
 constexpr int TS = 16, HS = 18;   // 16x16-pixel tiles, 18x18 halo
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // tap (kh, kw) reads pixel (h + kh - 1, w + kw - 1); row class rc: 0 = first row, 2 = last row, 1 = neither
 __device__ __forceinline__ bool tap_valid(int k, int c) { return !(k == 0 && c == 0) && !(k == 2 && c == 2); }

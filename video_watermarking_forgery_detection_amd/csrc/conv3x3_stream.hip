@@ -9,20 +9,8 @@
 // next item's first chunks load while the current one drains.  Filter slab traffic is served by L2 (every workgroup of an
 // output tile reads the same slabs).
 #include <stdlib.h>
-#include "wm_common.h"
+#include "wm_mfma.h"
 
-// This file is compiled twice (build.py): plain for bf16 (production), and with -DWM_H16_F16 for the f16 twin of every kernel in
-// it (the reference's autocast dtype, BASELINE config C5).  Everything that depends on the 16-bit layout goes through h16<> (wm_common.h).
-#ifdef WM_H16_F16
-typedef f16_t hx_t;
-#define WM_HSYM(name) name##_f16
-#else
-typedef bf16_t hx_t;
-#define WM_HSYM(name) name##_bf16
-#endif
-typedef h16<hx_t> HX;
-typedef HX::x8 hx8;
-typedef HX::x2 hx2;
 
 namespace {
 
@@ -33,9 +21,6 @@ constexpr int XB = NPIX * CK * 2;            // 20,736 B
 constexpr int WB = 9 * NT * CK * 2;          // 36,864 B
 constexpr int XV = (NPIX * 4 + 255) / 256;   // halo vectors per producer thread (6)
 constexpr int WV = 9 * NT * 4 / 256;         // filter vectors per producer thread (9)
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
 
 struct StArgs {
     const hx_t* x; int ldx;
@@ -61,7 +46,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StArgs a) {
     const int nch = (a.Cin + CK - 1) / CK;               // chunks per item
     // XCD-aware run assignment (see conv3x3_ws.hip); items are ordered (output tile, pixel tile): a run shares its filter slabs
     const int G = gridDim.x;
-    const int run = (G & 7) == 0 ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int run = wm_xcd_run(G, blockIdx.x);
     const int i_begin = run * a.items_per_wg;
     const int i_end = min(a.nitems, i_begin + a.items_per_wg);
     const int nstream = (i_end - i_begin) * nch;         // chunks this workgroup streams

@@ -17,20 +17,8 @@
 // column index is XOR-swizzled with (row >> 1) & 7, which makes 16 consecutive rows hit 16 distinct bank slots
 // for ds_read_b128 and for the producers' ds_write_b128.
 #include <stdlib.h>
-#include "wm_common.h"
+#include "wm_mfma.h"
 
-// This file is compiled twice (build.py): plain for bf16 (production), and with -DWM_H16_F16 for the f16 twin of every kernel in
-// it (the reference's autocast dtype, BASELINE config C5).  Everything that depends on the 16-bit layout goes through h16<> (wm_common.h).
-#ifdef WM_H16_F16
-typedef f16_t hx_t;
-#define WM_HSYM(name) name##_f16
-#else
-typedef bf16_t hx_t;
-#define WM_HSYM(name) name##_bf16
-#endif
-typedef h16<hx_t> HX;
-typedef HX::x8 hx8;
-typedef HX::x2 hx2;
 
 namespace {
 
@@ -54,23 +42,16 @@ struct WsArgs {
     unsigned mX, mY;   // ceil(2^32 / tilesX), ceil(2^32 / tilesY) (0 for 1): the tile index is divided by mulhi, not by ~40 scalar instructions
 };
 
-inline void ws_magic(WsArgs& a) {
-    auto m = [](int d) { return d == 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); };
-    a.mX = m(a.tilesX); a.mY = m(a.tilesY);
-}
+inline void ws_magic(WsArgs& a) { a.mX = wm_magic_u32(a.tilesX); a.mY = wm_magic_u32(a.tilesY); }
 
-// 16-byte column swizzles.  Filter rows: key = (row >> 1) & 7.  Halo pixels: key = (halo column >> 1) & 7 -- it does
+// 16-byte column swizzles (swz128 of wm_mfma.h).  Filter rows: key = (row >> 1) & 7.  Halo pixels: key = (halo column >> 1) & 7 -- it does
 // not depend on the halo ROW, so for a consumer lane the swizzled address of tap (kh, kw) is a per-(kw, k-step)
 // register plus a compile-time (kh, M-fragment) offset; 16 consecutive pixels of a row (from any kw) and the
 // pixels of the row below all land on distinct 16-byte bank slots.
 // CIN = 16 / 32 (image-fed first layers, the dgrad of the 30-channel decoder layer) are stored unswizzled: their
 // 9 / 18-step MFMA loops are a small part of a store-bound kernel.
-template <int CIN> __device__ __forceinline__ int swz(int row, int slot) { return CIN == 64 ? slot ^ ((row >> 1) & 7) : slot; }
-template <int CIN> __device__ __forceinline__ int swz_px(int px, int slot) { return CIN == 64 ? slot ^ ((px >> 1) & 7) : slot; }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
+template <int CIN> __device__ __forceinline__ int swz(int row, int slot) { return CIN == 64 ? swz128(row, slot) : slot; }
+template <int CIN> __device__ __forceinline__ int swz_px(int px, int slot) { return CIN == 64 ? swz128(px, slot) : slot; }
 
 // M16: consumers use v_mfma_f32_16x16x32_bf16 (needs CIN % 32 == 0) instead of 32x32x16: same FLOPs per cycle, but the
 // chip holds a higher clock on it under load (MI355X_MICROARCH.md, DVFS give-back item 7); A/B: tools/ab_step.py
@@ -160,7 +141,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(WsArgs a) {
     // consecutive runs [x*G/8, (x+1)*G/8): vertically adjacent tile rows then meet in ONE L2 at about the same time
     // and the halo rows they share are fetched from HBM once
     const int G = gridDim.x;
-    const int run = (G & 7) == 0 ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int run = wm_xcd_run(G, blockIdx.x);
     const int t_begin = run * a.tiles_per_wg;
     const int t_end = min(a.ntiles, t_begin + a.tiles_per_wg);
     struct TileGeo { int b, ty0, tx0; };

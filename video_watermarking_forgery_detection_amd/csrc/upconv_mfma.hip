@@ -6,31 +6,14 @@
 //   upconv_wgrad_kernel    dW      : dW[ci][(ij,co)] = sum_p A[p][ci] * G4[p][(ij,co)] (split over pixel ranges) + column sums
 // All use v_mfma_f32_16x16x32_bf16 with the WEIGHTS as the A operand (accumulator rows = output channels), so a lane owns
 // 16 adjacent channels of one pixel and stores 2 x 16 bytes (see conv3x3_ws.hip).  The f32 / odd-shape path stays in unet.hip.
-#include "wm_common.h"
+#include "wm_mfma.h"
 
-// This file is compiled twice (build.py): plain for bf16 (production), and with -DWM_H16_F16 for the f16 twin of every kernel in
-// it (the reference's autocast dtype, BASELINE config C5).  Everything that depends on the 16-bit layout goes through h16<> (wm_common.h).
-#ifdef WM_H16_F16
-typedef f16_t hx_t;
-#define WM_HSYM(name) name##_f16
-#else
-typedef bf16_t hx_t;
-#define WM_HSYM(name) name##_bf16
-#endif
-typedef h16<hx_t> HX;
-typedef HX::x8 hx8;
-typedef HX::x2 hx2;
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int PT = 128;   // pixels per workgroup tile
 constexpr int NT = 64;    // output columns per workgroup tile
 constexpr int KC = 64;    // K chunk
-
-__device__ __forceinline__ int swz128(int row, int slot) { return slot ^ ((row >> 1) & 7); }   // 16-byte slots of a 128-byte row
 
 struct UpArgs {
     const hx_t* in; int ldin;              // MODE 0: x [Min][ldin];  MODE 1: gy [B,2H,2W,ldin]
@@ -198,23 +181,13 @@ __global__ __launch_bounds__(256, 2) void upconv_mfma_kernel(UpArgs a) {
 // partial[split][ci][(ij,co)] = sum over the split's pixels of A[p][ci] * G4[p][(ij,co)];  bias_partial[split][(ij,co)] = sum G4.
 // Workgroup = 64 ci x 64 columns; wave w owns ci fragment w (16 ci) x 4 column fragments; both operands reach the MFMA
 // through transposing reads (K = pixels).  64-pixel chunks, double-buffered in LDS, rows of 128 B with the byte-offset
-// swizzle of wgrad_ws.hip (bits 5-6 keyed on pixel bits 1 and 3): conflict-free ds_read_b64_tr_b16.
+// swizzle swz16 of wm_mfma.h (bits 5-6 keyed on pixel bits 1 and 3): conflict-free ds_read_b64_tr_b16.
 struct UpWgArgs {
     const hx_t* x; int ldx; const float* scale; const float* shift;
     const hx_t* gy; int ldgy; int c0;
     float* partial; float* bias_partial;
     int B, H, W, Cin, Cout, nsplit;
 };
-
-__device__ __forceinline__ int swzt(int pix) { return (((pix >> 1) & 1) << 5) | (((pix >> 3) & 1) << 6); }
-__device__ __forceinline__ hx8 tr_frag2(const char* p0, const char* p1) {
-    typedef short s4 __attribute__((ext_vector_type(4)));
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p0));
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p1));
-    typedef short s8 __attribute__((ext_vector_type(8)));
-    s8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(hx8, v);
-}
 
 __global__ __launch_bounds__(256, 2) void upconv_wgrad_kernel(UpWgArgs a) {
     constexpr int PC = 64;   // pixels per chunk
@@ -269,7 +242,7 @@ __global__ __launch_bounds__(256, 2) void upconv_wgrad_kernel(UpWgArgs a) {
             const unsigned keep = rok[k] ? 0xffffffffu : 0u;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { w[e] &= keep; g[e] &= keep; }
-            const int off = pix * 128 + ((vec * 16) ^ swzt(pix));
+            const int off = pix * 128 + ((vec * 16) ^ swz16(pix));
             *reinterpret_cast<u32x4*>(sA[buf] + off) = w;
             *reinterpret_cast<u32x4*>(sG[buf] + off) = g;
         }
@@ -281,9 +254,9 @@ __global__ __launch_bounds__(256, 2) void upconv_wgrad_kernel(UpWgArgs a) {
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
         const int pix = 8 * kq + qq + 4 * s2;
-        aoffs[s2] = pix * 128 + (((wave * 16 + 4 * pp) * 2) ^ swzt(pix));
+        aoffs[s2] = pix * 128 + (((wave * 16 + 4 * pp) * 2) ^ swz16(pix));
 #pragma unroll
-        for (int nf = 0; nf < 4; ++nf) goffs[s2][nf] = pix * 128 + (((nf * 16 + 4 * pp) * 2) ^ swzt(pix));
+        for (int nf = 0; nf < 4; ++nf) goffs[s2][nf] = pix * 128 + (((nf * 16 + 4 * pp) * 2) ^ swz16(pix));
     }
     f32x4 acc[4], accb = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -303,10 +276,10 @@ __global__ __launch_bounds__(256, 2) void upconv_wgrad_kernel(UpWgArgs a) {
         const char* cG = reinterpret_cast<const char*>(sG[buf]);
 #pragma unroll
         for (int ks = 0; ks < PC / 32; ++ks) {
-            const hx8 af = tr_frag2(cA + ks * 32 * 128 + aoffs[0], cA + ks * 32 * 128 + aoffs[1]);
+            const hx8 af = tr_frag(cA + ks * 32 * 128 + aoffs[0], cA + ks * 32 * 128 + aoffs[1]);
             hx8 gf[4];
 #pragma unroll
-            for (int nf = 0; nf < 4; ++nf) gf[nf] = tr_frag2(cG + ks * 32 * 128 + goffs[0][nf], cG + ks * 32 * 128 + goffs[1][nf]);
+            for (int nf = 0; nf < 4; ++nf) gf[nf] = tr_frag(cG + ks * 32 * 128 + goffs[0][nf], cG + ks * 32 * 128 + goffs[1][nf]);
 #pragma unroll
             for (int nf = 0; nf < 4; ++nf) acc[nf] = HX::mfma16(af, gf[nf], acc[nf]);
             // column sums of G4 (the bias gradient): ones x G for this wave's own column fragment

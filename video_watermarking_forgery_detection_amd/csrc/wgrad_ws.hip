@@ -7,20 +7,8 @@
 // One workgroup barrier per tile.  LDS (CI = 64): 2 x (x halo 41,472 B + dy 32,768 B) = 148,480 B.
 // (A 32x32x16 form with 64-byte-half swizzle preceded this one: 1.6 % slower on the step; a paced / prioritised
 // producer variant of it 1.4 % slower still -- tools/ab_step.py.)
-#include "wm_common.h"
+#include "wm_mfma.h"
 
-// This file is compiled twice (build.py): plain for bf16 (production), and with -DWM_H16_F16 for the f16 twin of every kernel in
-// it (the reference's autocast dtype, BASELINE config C5).  Everything that depends on the 16-bit layout goes through h16<> (wm_common.h).
-#ifdef WM_H16_F16
-typedef f16_t hx_t;
-#define WM_HSYM(name) name##_f16
-#else
-typedef bf16_t hx_t;
-#define WM_HSYM(name) name##_bf16
-#endif
-typedef h16<hx_t> HX;
-typedef HX::x8 hx8;
-typedef HX::x2 hx2;
 
 namespace {
 
@@ -49,24 +37,14 @@ struct WsWgArgs {
     int reverse;
 };
 
-__device__ __forceinline__ hx8 tr_frag(const char* p0, const char* p1) {
-    typedef short s4 __attribute__((ext_vector_type(4)));
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p0));
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p1));
-    typedef short s8 __attribute__((ext_vector_type(8)));
-    s8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(hx8, v);
-}
-
 // ----------------------------------------------------------------------------------------------------------------
 // 16x16x32 form (v_mfma_f32_16x16x32_bf16): the chip holds a higher clock on this shape (see conv3x3_ws.hip), and a
 // 16-row M lets the image-fed first layers (CinX = 16) run with CI = 16 instead of padding their input to 64 channels.
 //   D[ci 16 x co 16] += A[ci x 32 pixels] * B[32 pixels x co]; a K-step is two tile rows; lane (r = lane&15, kq = lane>>4)
 //   owns pixels 8kq .. 8kq+7 of the step = tile row (kq>>1), columns 8(kq&1) .. +7, fetched by two transposing reads.
-// LDS: pixel rows of CI*2 bytes.  CI = 64 and the dy tile: byte offset XOR (((col>>1)&1) << 5 | ((col>>3)&1) << 6) -- the
+// LDS: pixel rows of CI*2 bytes.  CI = 64 and the dy tile: byte offset XOR swz16(col) (wm_mfma.h) -- the
 // 8 pixels x 32 B one half-wave touches ({c..c+3} and {c+8..c+11}, any tap shift) fill a 256-byte bank row exactly once.
 // CI = 16 (32-byte pixels): halo column c is stored at slot c ^ (((c>>3)&1) << 2), which does the same.
-__device__ __forceinline__ int swz16(int col) { return (((col >> 1) & 1) << 5) | (((col >> 3) & 1) << 6); }
 __device__ __forceinline__ int slot16(int col) { return col ^ (((col >> 3) & 1) << 2); }
 
 // DYF: dy is not read but formed on the fly from (g, y) -- the apply pass of the BatchNorm backward, fused for layers whose dy
@@ -99,7 +77,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_ws16_kernel(WsWgArgs a) {
         __syncthreads();
     }
     const int G = gridDim.x;
-    const int run = (G & 7) == 0 ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int run = wm_xcd_run(G, blockIdx.x);
     const int t_begin = (int)(((long)run * a.ntiles) / G);
     const int t_end = (int)(((long)(run + 1) * a.ntiles) / G);
     struct TileGeo { int b, ty0, tx0; };
@@ -111,8 +89,6 @@ __global__ __launch_bounds__(512, 2) void wgrad_ws16_kernel(WsWgArgs a) {
         g.b = t; g.ty0 = tyi * TH; g.tx0 = txi * TW;
         return g;
     };
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        typedef short i16x2 __attribute__((ext_vector_type(2)));
 
     if (producer) {
         // ================================================================== PRODUCER waves

@@ -43,6 +43,11 @@ void wm_set_error(const char* fmt, ...);
 
 static inline int wm_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// ---- XCD-aware run assignment of the persistent kernels: workgroup `block` of a grid of G walks run wm_xcd_run(G, block) of the work
+// list.  Workgroups b and b + 8 share an XCD (and its L2), so each XCD gets G / 8 CONSECUTIVE runs: neighbouring tiles' shared halo
+// rows and filter slabs are re-read from that L2.  G not a multiple of 8: the identity.
+__device__ __forceinline__ int wm_xcd_run(int G, unsigned block) { return (G & 7) == 0 ? (block & 7) * (G >> 3) + (block >> 3) : block; }
+
 // ---- clamp_with_grad + Quantization of the localisation branch (IRNcrop_model.py:320-322,344-345,372-373; models/modules/Quantization.py:7-14):
 // torch.clamp(x,0,1) then (x*255).round()/255 -- rintf = round half to even like torch.round, true f32 division.  The one definition behind
 // wm_clamp_quant_fwd, wm_splice_fwd (localise.hip) and wm_mix_fwd's quant = 1 (hybrid.hip), so the three agree bit for bit.
