@@ -584,7 +584,9 @@ int wm_scale_dev(float* x, size_t n, const float* scale_dev, void* stream);
  * wm_add_scaled : out = a + alpha * b.
  * wm_qfatt_fwd  : out = x + gamma[b,c] * res + beta[b,c] (gamma / beta f32 [B][ldv]); wm_qfatt_bwd: gres = gamma * g,
  *                 ggamma[b,c] = sum_p g * res, gbeta[b,c] = sum_p g (the gradient wrt x is g itself); scratch:
- *                 wm_qfatt_bwd_scratch_floats(B, hw, ldv) floats.
+ *                 wm_qfatt_bwd_scratch_floats(B, hw, ldv) floats.  Both need ldv >= C; wm_qfatt_bwd also needs C % 16 == 0 (it walks
+ *                 16-byte vectors of 64-channel blocks, like wm_unary_bwd_colsum) and returns WM_E_BADARG otherwise; columns [C, ldv)
+ *                 of ggamma / gbeta are left as they were.
  * wm_gpool_fwd  : out f32 [B][C] = mean over the hw pixels of x [B,hw,C]; wm_gpool_bwd: gx = g / hw.
  * wm_pad_nchw_to_nhwc(_bwd): x [B,C,H,W] f32 -> out [B,H+top+bottom,W+left+right,CP], mode 0 symmetric, 1 replicate (pads may
  *                 be 0: a plain layout change); the backward sums every padded position back onto its source pixel.

@@ -542,7 +542,9 @@ extern "C" int wm_qfatt_fwd(const void* x, const void* res, const float* gamma, 
 extern "C" size_t wm_qfatt_bwd_scratch_floats(int B, size_t hw, int ldv) { return (size_t)qfatt_nsplit(hw) * B * 2 * ldv; }
 extern "C" int wm_qfatt_bwd(const void* g, const void* res, const float* gamma, void* gres, float* ggamma, float* gbeta, float* scratch, int B, size_t hw,
                             int C, int ldv, int dtype, void* stream) {
-    WM_REQUIRE(g && res && gamma && gres && ggamma && gbeta && scratch && B > 0 && hw > 0 && C > 0 && ldv >= C, WM_E_BADARG, "wm_qfatt_bwd: bad arguments");
+    // the kernel owns whole 16-byte vectors of 64-channel blocks whose last holds at least 16 channels (its LDS rows are sized for that): C % 16 == 0
+    WM_REQUIRE(g && res && gamma && gres && ggamma && gbeta && scratch && B > 0 && hw > 0 && C > 0 && C % 16 == 0 && ldv >= C, WM_E_BADARG,
+               "wm_qfatt_bwd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int ns = qfatt_nsplit(hw);
     WM_DISPATCH_DTYPE(dtype, "wm_qfatt_bwd",
