@@ -36,7 +36,7 @@ from layers_exact import EPS32, FACTOR, SENTINEL, Cmp, grid, half_ulp, normal, p
 from layers_exact import DTYPES, TORCH, VE, all_ok, f64, first_bad  # noqa: F401
 
 # OpenCL C specification, "Relative Error as ULPs", single precision, full profile
-U = {"exp": 3.0, "expm1": 3.0, "erf": 16.0, "tanh": 5.0}
+U = {"exp": 3.0, "expm1": 3.0, "erf": 16.0, "tanh": 5.0, "log": 3.0, "log1p": 2.0}      # log, log1p: tests/steploss_exact.py
 F32_MAX = float(np.finfo(np.float32).max)
 TINY32 = 2.0 ** -149
 MIN_NORMAL = {"f32": 2.0 ** -126, "bf16": 2.0 ** -126, "f16": 2.0 ** -14}

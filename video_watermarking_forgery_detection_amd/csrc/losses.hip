@@ -87,7 +87,10 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
 }
 
 __global__ __launch_bounds__(256) void clamp01_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) y[i] = fminf(fmaxf(x[i], 0.f), 1.f);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float v = x[i];
+        y[i] = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);   // torch.clamp keeps a nan a nan (fminf(fmaxf(v, 0), 1) would turn it into 0)
+    }
 }
 __global__ __launch_bounds__(256) void clamp01_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ gx, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {

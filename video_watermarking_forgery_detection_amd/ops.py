@@ -1114,6 +1114,11 @@ def psnr_gate(partials, n, threshold=33.0, w_below=1.0, w_above=0.8):
 
 def mse_fwd_bwd_gated(a, b, gscale, gate, gscale_dev=None):
     """mse_fwd_bwd with the gradient scale multiplied by the device scalar gate[0]"""
+    _need_cuda(a, b, gate, gscale_dev)
+    if a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError(f"mse_fwd_bwd_gated: float32 tensors of one shape expected, got {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}")
+    if gate.dtype != torch.float32 or gate.numel() < 1 or (gscale_dev is not None and (gscale_dev.dtype != torch.float32 or gscale_dev.numel() < 1)):
+        raise ValueError("mse_fwd_bwd_gated: gate and gscale_dev are float32 device scalars")
     a = a.contiguous(); b = b.contiguous()
     n = a.numel()
     nparts = max(1, min(1024, (n + 4095) // 4096))
@@ -1143,8 +1148,12 @@ def bce_logits_target(p, target, gscale=1.0, want_grad=True, chain_sigmoid=False
 
 def masked_axpy_(a, g, mask):
     """a += g * (1 - mask), mask [B,1,H,W] broadcast over channels"""
+    _need_cuda(a, g, mask)
+    if a.dim() != 4 or g.shape != a.shape or tuple(mask.shape) != (a.shape[0], 1, a.shape[2], a.shape[3]):
+        raise ValueError(f"masked_axpy_: a, g [B,C,H,W] and mask [B,1,H,W] expected, got {tuple(a.shape)}, {tuple(g.shape)}, {tuple(mask.shape)}")
+    if not (a.dtype == g.dtype == mask.dtype == torch.float32) or not (a.is_contiguous() and g.is_contiguous() and mask.is_contiguous()):
+        raise ValueError("masked_axpy_: contiguous float32 tensors expected (a is updated in place)")
     B, C, H, W = a.shape
-    assert a.is_contiguous() and g.is_contiguous() and g.shape == a.shape and mask.is_contiguous() and tuple(mask.shape) == (B, 1, H, W)
     rc = _lib.lib().wm_masked_axpy(_p(a), _p(g), _p(mask), B, C, H * W, _stream())
     _lib.check(rc, "wm_masked_axpy")
     _wrote(a)
@@ -1947,6 +1956,9 @@ def clamp01_fwd(x):
 
 def clamp01_bwd(x, g):
     _need_cuda(x, g)
+    if x.shape != g.shape:
+        raise ValueError(f"clamp01_bwd: x {tuple(x.shape)} and g {tuple(g.shape)} disagree")
+    x = x.contiguous().float()          # (the kernel walks both flat: a view's storage is not its elements)
     g = g.contiguous().float()
     gx = torch.empty_like(g)
     rc = _lib.lib().wm_clamp01_bwd(_p(x), _p(g), _p(gx), g.numel(), _stream())
