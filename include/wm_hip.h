@@ -538,6 +538,14 @@ int wm_amp_update(float* state, int noptimizers, void* stream);
  * wm_splice_fwd: q = clamp_quant(enc); fwd_q (may be NULL) = q; tampered (may be NULL) = q*(1-mask) + prev*mask with mask
  *   [B,1,HW] broadcast over the C planes; psnr_partials [wm_splice_nparts(B*C*HW)] doubles (with real; both may be NULL) =
  *   partial sums of (int(255*real) - int(255*q))^2.
+ * wm_copymove_fwd (models/IRNp_model.py:561-598, :1007-1037, the copy-move forgery): q = clamp_quant(enc) [B,C,H,W];
+ *   mask_shifted[b,0,i,j] = clamp01(mask[b,0,i-sx_b,j-sy_b]) and t[b,c,i,j] = q[b,c,i-sx_b,j-sy_b], both 0 where the source pixel lies
+ *   outside the frame; tampered = q*(1-mask_shifted) + t*mask_shifted; fwd_q (may be NULL) = q.  shifts: device int32 [B][2] = (sx_b rows,
+ *   sy_b columns), clamped to [-H,H] x [-W,W] by the kernel (a larger magnitude has the same effect).  partials (may be NULL without real)
+ *   = [2][wm_splice_nparts(B*C*H*W)] doubles: row 0 as wm_splice_fwd's psnr_partials (zeros when real is NULL), row 1 partial sums of
+ *   mask_shifted (valid = their sum / (B*H*W)).  Not in place; B*C*H < 2^31 (WM_E_SHAPE).
+ * wm_copymove_valid: out[0] = (sum of row 1 of wm_copymove_fwd's partials [2][nparts]) / count, added in double in a fixed order
+ *   (IRNp_model.py:592 valid = torch.mean(masks), count = B*H*W); wm_psnr_gate reads row 0 as it reads wm_splice_fwd's partials.
  * wm_psnr_gate: out2[0] = PSNR (0 when the images are equal, like metrics.py:41-42), out2[1] = PSNR < threshold ? w_below : w_above.
  * wm_mse_fwd_bwd_gated: wm_mse_fwd_bwd with the gradient scale multiplied by the device scalar gate_dev[0].
  * wm_bce_logits_target: *loss_out = mean BCE-with-logits(p, target), grad_out (may be NULL) = gscale * d loss / d p;
@@ -551,6 +559,9 @@ int wm_clamp_quant_fwd(const float* x, float* y, size_t n, void* stream);
 int wm_splice_nparts(size_t n);
 int wm_splice_fwd(const float* enc, const float* real, const float* prev, const float* mask, float* fwd_q, float* tampered,
                   double* psnr_partials, int B, int C, size_t HW, void* stream);
+int wm_copymove_fwd(const float* enc, const float* real, const float* mask, const int* shifts, float* fwd_q, float* tampered,
+                    float* mask_shifted, double* partials, int B, int C, int H, int W, void* stream);
+int wm_copymove_valid(const double* partials, int nparts, double count, float* out, void* stream);
 int wm_psnr_gate(const double* psnr_partials, int nparts, double n, float threshold, float w_below, float w_above, float* out2,
                  void* stream);
 int wm_mse_fwd_bwd_gated(const float* a, const float* b, float* grad_a, float gscale, const float* gate_dev, const float* gscale_dev,

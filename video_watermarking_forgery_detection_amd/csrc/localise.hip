@@ -7,6 +7,7 @@
 //   clip_grad_norm_ over a group of flat buffers   IRNcrop_model.py:410-412
 // All HBM-bound streaming passes; the reductions are two-stage and deterministic (per-workgroup partials in a fixed order).
 #include "wm_common.h"
+#include "wm_reduce.h"
 
 namespace {
 
@@ -51,6 +52,100 @@ __global__ __launch_bounds__(256) void splice_kernel(const float* __restrict__ e
         __syncthreads();
     }
     if (threadIdx.x == 0 && partials) partials[blockIdx.x] = s[0];
+}
+
+// copy-move (IRNp_model.py:561-598 inline, :1007-1037 copy_move()): the region under the mask is filled with the SAME frame moved by
+// (sx, sy) rows / columns, and the mask moves with it.  The reference pads by 2|s|, writes at offset |s|+s and reads back at |s|, which is
+//   ms[b,0,i,j] = clamp01(mask[b,0,i-sx,j-sy]),  t[b,c,i,j] = q[b,c,i-sx,j-sy]   (0 where the source lies outside the frame)
+//   out = q*(1-ms) + t*ms,  q = Q(clamp(enc)) recomputed on the gathered value (fwd_q is never read back)
+// One item = V consecutive pixels of one row (V = 4: 16-byte loads and stores on enc, real, fwd_q, out, ms; W % 4 == 0 keeps an item
+// inside its row; the gathers stay 4-byte: their alignment depends on sy).  ms is stored, and summed, by the channel-0 items only.
+// partials [2][gridDim.x]: row 0 as splice_kernel's (zeros without real), row 1 the sums of ms (valid = mean(ms)); fixed order, f64.
+// shifts [B][2] int32, clamped to [-H,H] x [-W,W] here: any larger magnitude moves everything out of the frame just the same.
+// q*(1-m) + t*m with each of the four operations rounded, never contracted into an fma: what a float32 run of the reference computes, and
+// what splice_kernel's compiled form computes (a packed pair of products and a sum), so a zero shift gives the splice of q with itself bit for bit
+__device__ __forceinline__ float blend_unfused(float q, float t, float m) {
+#pragma clang fp contract(off)
+    const float a = q * (1.f - m), b = t * m;
+    return a + b;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void copymove_kernel(const float* __restrict__ enc, const float* __restrict__ real,
+                                                       const float* __restrict__ mask, const int* __restrict__ shifts,
+                                                       float* __restrict__ fwd_q, float* __restrict__ out, float* __restrict__ ms_out,
+                                                       double* __restrict__ partials, int C, int H, int W, size_t items) {
+    constexpr int V = VEC ? 4 : 1;
+    const unsigned per = (unsigned)(W / V);                   // items of a row
+    const size_t HW = (size_t)H * W;
+    double accp = 0.0, accv = 0.0;
+    for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (size_t)gridDim.x * blockDim.x) {
+        const size_t rowl = it / per;                         // (b*C + c)*H + i < 2^31 (checked by the caller)
+        const int j0 = (int)(it - rowl * per) * V;
+        const unsigned rowg = (unsigned)rowl, plane = rowg / (unsigned)H, b = plane / (unsigned)C;
+        const int i = (int)(rowg - plane * (unsigned)H), c = (int)(plane - b * (unsigned)C);
+        const int sx = min(max(shifts[2 * b], -H), H), sy = min(max(shifts[2 * b + 1], -W), W);
+        const int si = i - sx;                                // the source row: within [-H, 2H)
+        const bool rowok = si >= 0 && si < H;
+        const size_t at = rowl * (size_t)W + j0;
+        const float* esrc = enc + (size_t)plane * HW + (size_t)(rowok ? si : 0) * W;
+        const float* msrc = mask + (size_t)b * HW + (size_t)(rowok ? si : 0) * W;
+        float e[V], q[V], o[V], m[V];
+        if constexpr (VEC) {
+            const float4 x = ld16(enc + at);
+            e[0] = x.x; e[1] = x.y; e[2] = x.z; e[3] = x.w;
+        } else {
+            e[0] = enc[at];
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int sj = j0 + k - sy;                       // within [-W, 2W)
+            float t = 0.f;
+            m[k] = 0.f;
+            if (rowok && sj >= 0 && sj < W) {
+                m[k] = fminf(fmaxf(msrc[sj], 0.f), 1.f);
+                t = clamp_quant(esrc[sj]);
+            }
+            q[k] = clamp_quant(e[k]);
+            o[k] = blend_unfused(q[k], t, m[k]);
+        }
+        if constexpr (VEC) {
+            *reinterpret_cast<float4*>(out + at) = make_float4(o[0], o[1], o[2], o[3]);
+            if (fwd_q) *reinterpret_cast<float4*>(fwd_q + at) = make_float4(q[0], q[1], q[2], q[3]);
+        } else {
+            out[at] = o[0];
+            if (fwd_q) fwd_q[at] = q[0];
+        }
+        if (c == 0) {
+            float* mdst = ms_out + (size_t)b * HW + (size_t)i * W + j0;
+            if constexpr (VEC) *reinterpret_cast<float4*>(mdst) = make_float4(m[0], m[1], m[2], m[3]);
+            else *mdst = m[0];
+#pragma unroll
+            for (int k = 0; k < V; ++k) accv += (double)m[k];
+        }
+        if (real) {
+            float r[V];
+            if constexpr (VEC) {
+                const float4 x = ld16(real + at);
+                r[0] = x.x; r[1] = x.y; r[2] = x.z; r[3] = x.w;
+            } else {
+                r[0] = real[at];
+            }
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const int a = (int)(r[k] * 255.0f), f = (int)(q[k] * 255.0f);   // postprocess(): (img * 255.0).int() truncates
+                const float d = (float)a - (float)f;
+                accp += (double)(d * d);
+            }
+        }
+    }
+    __shared__ double s[2][4];
+    accp = block_sum_f64(accp, s[0]);
+    accv = block_sum_f64(accv, s[1]);
+    if (threadIdx.x == 0 && partials) {
+        partials[blockIdx.x] = accp;
+        partials[gridDim.x + blockIdx.x] = accv;
+    }
 }
 
 // metrics.py:30-46 with max_val 255: psnr = 20*log(255)/log(10) - 10*log(mse)/log(10); mse == 0 -> 0.
@@ -192,6 +287,33 @@ extern "C" int wm_splice_fwd(const float* enc, const float* real, const float* p
     hipLaunchKernelGGL(splice_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, (hipStream_t)stream, enc, real, prev, mask, fwd_q, tampered,
                        psnr_partials, C, HW, n);
     WM_LAUNCH_CHECK("wm_splice_fwd");
+    return WM_OK;
+}
+
+extern "C" int wm_copymove_fwd(const float* enc, const float* real, const float* mask, const int* shifts, float* fwd_q, float* tampered,
+                               float* mask_shifted, double* partials, int B, int C, int H, int W, void* stream) {
+    WM_REQUIRE(enc && mask && shifts && tampered && mask_shifted && B > 0 && C > 0 && H > 0 && W > 0, WM_E_BADARG,
+               "wm_copymove_fwd: bad arguments");
+    WM_REQUIRE(real == nullptr || partials != nullptr, WM_E_BADARG, "wm_copymove_fwd: real needs partials");
+    WM_REQUIRE(tampered != enc && mask_shifted != mask, WM_E_BADARG, "wm_copymove_fwd: not in place (the gather reads enc and mask at other pixels)");
+    const size_t rows = (size_t)B * C * H, n = rows * W;
+    WM_REQUIRE(rows <= 0x7fffffffu, WM_E_SHAPE, "wm_copymove_fwd: B*C*H must be below 2^31");
+    const uintptr_t bases = (uintptr_t)enc | (uintptr_t)real | (uintptr_t)fwd_q | (uintptr_t)tampered | (uintptr_t)mask_shifted;
+    const dim3 grid(grid_for(n, 1024));      // == wm_splice_nparts(n): one partial per workgroup and row
+    if (W % 4 == 0 && (bases & 15) == 0)
+        hipLaunchKernelGGL(copymove_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, enc, real, mask, shifts, fwd_q, tampered, mask_shifted,
+                           partials, C, H, W, rows * (size_t)(W / 4));
+    else
+        hipLaunchKernelGGL(copymove_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, enc, real, mask, shifts, fwd_q, tampered, mask_shifted,
+                           partials, C, H, W, n);
+    WM_LAUNCH_CHECK("wm_copymove_fwd");
+    return WM_OK;
+}
+
+extern "C" int wm_copymove_valid(const double* partials, int nparts, double count, float* out, void* stream) {
+    WM_REQUIRE(partials && out && nparts > 0 && count > 0, WM_E_BADARG, "wm_copymove_valid: bad arguments");
+    wm_sum_finalize(partials + nparts, (size_t)nparts, 1.0 / count, out, (hipStream_t)stream);   // row 1: the sums of mask_shifted
+    WM_LAUNCH_CHECK("wm_copymove_valid");
     return WM_OK;
 }
 

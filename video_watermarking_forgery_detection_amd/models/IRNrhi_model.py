@@ -11,7 +11,8 @@ The step behind it is the HiDDeN-order watermark embed -> attack -> extract GAN 
 hidden_models/hidden.py:54-118 on the HIP kernels (hidden_models.Hidden), optionally followed by the
 tamper-localisation branch: STE clamp -> Quantization -> splice with the previous batch by the mask ->
 attack -> Quantization -> UNet -> BCEWithLogits on the (sigmoid) mask, whose gradient reaches both the
-UNet and, through the attack, the encoder.
+UNet and, through the attack, the encoder.  train.tamper_cycle alternates that splice with the reference's
+other forgery, copy-move within the frame (models/IRNp_model.py:497-499,561-598).
 
 Bookkeeping kept from the reference: `global_step`, input clamp to [0,1] (:430), no work until two
 previous batches exist (:446), checkpoint every `save_interval` steps at `step % save_interval == 10`
@@ -62,6 +63,41 @@ def localizer_arch(train_opt):
     if arch not in LOCALIZER_ARCHS:
         raise ValueError(f"train.localizer_arch must be one of {LOCALIZER_ARCHS}, got {arch!r}")
     return arch
+
+
+TAMPER_KINDS = ("splicing", "copymove")
+REFERENCE_TAMPER_CYCLE = ("splicing", "copymove", "splicing")   # IRNp_model.py:499: copy-move where global_step % 3 == 1
+
+
+def tamper_cycle(train_opt):
+    """train.tamper_cycle: the forgeries the localiser is trained on, a list drawn from 'splicing' (the previous batch through the mask,
+    IRNcrop_model.py:348) and 'copymove' (the same frame, moved, IRNp_model.py:561-598), indexed by global_step % len.  Absent:
+    ['splicing'].  The reference's schedule is REFERENCE_TAMPER_CYCLE.  An unknown name or an empty list is a ValueError"""
+    cycle = _get(train_opt, 'tamper_cycle', default=None)
+    if cycle is None:
+        return ["splicing"]
+    cycle = [cycle] if isinstance(cycle, str) else list(cycle)
+    if not cycle or any(k not in TAMPER_KINDS for k in cycle):
+        raise ValueError(f"train.tamper_cycle must be a non-empty list drawn from {TAMPER_KINDS}, got {cycle!r}")
+    return cycle
+
+
+def draw_copymove_shifts(n_frames, H, W, frac=1.0, per_clip_T=None, rand=np.random.rand):
+    """per-frame (sx rows, sy columns) of a copy-move step: int(H * frac * (rand() - 0.5)), then int(W * frac * (rand() - 0.5)) -- the
+    reference's order of draws and its truncation towards zero (IRNp_model.py:567-568 with frac 1.0; :1010-1011, copy_move(), is frac 0.25).
+    One draw serves the whole batch, as in the reference; per_clip_T = T: one draw per clip of T consecutive frames, so that what was moved
+    stays put through a clip."""
+    if per_clip_T is None:
+        per_clip_T = n_frames
+    per_clip_T = int(per_clip_T)
+    if n_frames <= 0 or per_clip_T <= 0 or n_frames % per_clip_T:
+        raise ValueError(f"draw_copymove_shifts: {n_frames} frames are not whole clips of {per_clip_T}")
+    shifts = []
+    for _ in range(n_frames // per_clip_T):
+        sx = int(H * frac * (rand() - 0.5))
+        sy = int(W * frac * (rand() - 0.5))
+        shifts += [(sx, sy)] * per_clip_T
+    return shifts
 
 
 def localizer_class(train_opt):
@@ -187,6 +223,16 @@ class IRNrhiModel(BaseModel):
     def __init__(self, opt):
         super(IRNrhiModel, self).__init__(opt)
         self.localizer_arch = localizer_arch(opt['train'])      # (an unknown architecture is refused before anything is built)
+        # train.tamper_cycle (absent = ['splicing'], today's step): which forgery each step's localiser sees; with the key present the logs
+        # also carry ('Tamper', name) and ('Valid', mean of the ground-truth mask).  train.copymove_shift_frac (default 1.0, the inline
+        # form's range; 0.25 is copy_move()'s) and train.copymove_per_clip (default false: one draw per batch, as in the reference)
+        self.tamper_cycle = tamper_cycle(opt['train'])
+        self.log_tamper = _get(opt['train'], 'tamper_cycle', default=None) is not None
+        self.copymove_shift_frac = float(_get(opt['train'], 'copymove_shift_frac', default=1.0))
+        self.copymove_per_clip = bool(_get(opt['train'], 'copymove_per_clip', default=False))
+        self.copymove_rand = np.random.rand     # the shifts' source of draws (tests script it)
+        self._clip_T = None                     # frames per clip of the fed batch (feed_data), None for a batch of images
+        self._tamper = None                     # (kind, shifts, valid) of the step's forgery (_gate)
         if self.device.type != "cuda":
             raise RuntimeError("IRNrhiModel runs on the MI355X HIP path only (opt['gpu_ids'] must not be None)")
         train_opt = opt['train'] or {}
@@ -347,8 +393,10 @@ class IRNrhiModel(BaseModel):
         else:
             imgs = batch
         imgs, mask = self._to_device(imgs), (self._to_device(mask) if mask is not None else None)
+        self._clip_T = None
         if imgs.dim() == 5:
             B, C, T, H, W = imgs.shape
+            self._clip_T = T
             imgs = imgs.permute(0, 2, 1, 3, 4).reshape(B * T, C, H, W)
             if mask is not None:
                 mask = mask.permute(0, 2, 1, 3, 4).reshape(B * T, 1, H, W)
@@ -375,11 +423,24 @@ class IRNrhiModel(BaseModel):
     # ------------------------------------------------------------------ localisation branch
     def _gate(self, encoded, images):
         """IRNcrop_model.py:344-348,379-388: one pass over the encoded batch forms Q(clamp(encoded)), the spliced (tampered)
-        batch for _localise and the PSNR partial sums; the 1.0 / 0.8 forward weight stays on the device."""
+        batch for _localise and the PSNR partial sums; the 1.0 / 0.8 forward weight stays on the device.  Where train.tamper_cycle names
+        copymove for this step, the one pass is ops.copymove_fwd instead and self._loc carries the moved mask."""
         mask = self.mask
         if mask is None:
             mask = torch.zeros(encoded.shape[0], 1, encoded.shape[2], encoded.shape[3], device=encoded.device)
-        _, tampered, part = ops.splice_fwd(encoded, real=images, prev=self.previous_images, mask=mask)
+        kind = self.tamper_cycle[self.global_step % len(self.tamper_cycle)]
+        if kind == "copymove":
+            # IRNp_model.py:561-598: the masked region is filled with the same frame moved by the drawn shift, and the mask moves with it;
+            # from here on the moved mask is the ground truth (the loss target and the gradient's 1 - mask)
+            B, _, H, W = encoded.shape
+            shifts = draw_copymove_shifts(B, H, W, self.copymove_shift_frac, self._clip_T if self.copymove_per_clip else None,
+                                          self.copymove_rand)
+            _, tampered, mask, part = ops.copymove_fwd(encoded, mask, shifts, real=images)
+            self._tamper = (kind, shifts, ops.copymove_valid(part, B * H * W))
+            part = part[0]
+        else:
+            _, tampered, part = ops.splice_fwd(encoded, real=images, prev=self.previous_images, mask=mask)
+            self._tamper = (kind, None, mask.mean() if self.log_tamper else None)
         self._loc = (tampered, mask)
         return ops.psnr_gate(part, encoded.numel(), 33.0, 1.0, 0.8)
 
@@ -399,7 +460,7 @@ class IRNrhiModel(BaseModel):
             attacked, cA = self.attack.fwd(tampered, exclude=(Crop,), cover=images)   # the reference's localiser sees no geometric attack (:362-366)
             attacked_q = ops.clamp_quant(attacked)                  # clamp_with_grad + Quantization (:372-373)
         if self.keep_outputs:
-            self.last_outputs.update(tampered=tampered, attacked=attacked_q)
+            self.last_outputs.update(tampered=tampered, attacked=attacked_q, mask_gt=mask, shifts=self._tamper[1])
         if self.localizer_arch == "unetd":
             loss, dice, pred, g_att = unetd_localiser_step(net, self.localizer_flat, self.optimizer_localizer, attacked_q, mask,
                                                            weight=self.localizer_weight, dice_weight=self.dice_weight, amp=self.amp,
@@ -442,7 +503,31 @@ class IRNrhiModel(BaseModel):
         g_tamp = self.hybrid.bwd(cA, g_att) if self.hybrid is not None else self.attack.bwd(cA, g_att)
         ops.masked_axpy_(g_enc, g_tamp.contiguous(), mask)
         loc_kind = self.hybrid.name if self.hybrid is not None else self.attack.name
-        return [('lB', loss), ('CE', loss)] + ([('Dice', dice)] if dice is not None else []) + [('Kind', kind), ('LocKind', loc_kind)]
+        logs = [('lB', loss), ('CE', loss)] + ([('Dice', dice)] if dice is not None else []) + [('Kind', kind), ('LocKind', loc_kind)]
+        if self.log_tamper:
+            logs += [('Tamper', self._tamper[0]), ('Valid', self._tamper[2])]
+        return logs
+
+    @torch.no_grad()
+    def tamper(self, images, mask, kind, shifts=None, source=None):
+        """The step's forgery on a batch of one's own, for evaluation scripts: images [B,C,H,W] (clamped and quantised as the step does),
+        mask [B,1,H,W] -> (tampered, mask_gt).  kind 'copymove': shifts = B (sx, sy) pairs or an int32 [B,2] device tensor (default: drawn
+        as the step draws them, one draw for the batch); mask_gt is the moved mask.  kind 'splicing': source = the batch spliced in
+        (default: the previous batch); mask_gt is the mask."""
+        if kind not in TAMPER_KINDS:
+            raise ValueError(f"tamper: kind must be one of {TAMPER_KINDS}, got {kind!r}")
+        images = images.to(self.device, torch.float32).contiguous()
+        mask = mask.to(self.device, torch.float32).contiguous()
+        if kind == "copymove":
+            if shifts is None:
+                shifts = draw_copymove_shifts(images.shape[0], images.shape[2], images.shape[3], self.copymove_shift_frac, None, self.copymove_rand)
+            _, tampered, mask_gt, _ = ops.copymove_fwd(images, mask, shifts)
+            return tampered, mask_gt
+        source = self.previous_images if source is None else source
+        if source is None:
+            raise RuntimeError("tamper: splicing needs a source batch (none given and no previous batch fed yet)")
+        _, tampered, _ = ops.splice_fwd(images, prev=source.to(self.device, torch.float32), mask=mask)
+        return tampered, mask
 
     def _clip(self, flats):
         if self.gradient_clipping:

@@ -1104,6 +1104,72 @@ def splice_fwd(enc, real=None, prev=None, mask=None, want_fwd=False):
     return fwd, tam, part
 
 
+COPYMOVE_MAX_SHIFT = 2 ** 20   # host-side shifts: a larger magnitude is a mistake (the kernel clamps to the frame's size anyway)
+
+
+def _copymove_shifts(shifts, B):
+    """the checked per-frame (sx rows, sy columns) as an int32 [B, 2] tensor: a tensor is returned as given; a host sequence of B pairs
+    becomes a FRESH host tensor, which copymove_fwd copies into a fresh device tensor on every call -- a reused staging buffer could be
+    rewritten by the next call while an enqueued launch still has to read it"""
+    if torch.is_tensor(shifts):
+        if shifts.dtype != torch.int32 or tuple(shifts.shape) != (B, 2):
+            raise ValueError(f"copymove_fwd: shifts must be int32 [{B}, 2], got {shifts.dtype} {tuple(shifts.shape)}")
+        return shifts
+    pairs = [tuple(p) for p in shifts]
+    if len(pairs) != B or any(len(p) != 2 for p in pairs):
+        raise ValueError(f"copymove_fwd: shifts must be {B} (sx, sy) pairs, got {pairs!r}")
+    flat = []
+    for sx, sy in pairs:
+        for s in (sx, sy):
+            if isinstance(s, bool) or int(s) != s:
+                raise ValueError(f"copymove_fwd: shifts are integers, got {s!r}")
+            if abs(int(s)) > COPYMOVE_MAX_SHIFT:
+                raise ValueError(f"copymove_fwd: shift {s} exceeds 2**20 in magnitude")
+            flat.append(int(s))
+    return torch.tensor(flat, dtype=torch.int32).view(B, 2)
+
+
+def copymove_fwd(enc, mask, shifts, real=None, want_fwd=False):
+    """The copy-move forgery (IRNp_model.py:561-598, :1007-1037) in one launch: q = clamp_quant(enc);
+    mask_shifted[b,0,i,j] = clamp01(mask[b,0,i-sx_b,j-sy_b]), t[b,c,i,j] = q[b,c,i-sx_b,j-sy_b] (0 where the source lies outside the frame);
+    tampered = q*(1-mask_shifted) + t*mask_shifted.  shifts: int32 [B,2] device tensor or a host sequence of B (sx, sy) pairs.
+    Returns (fwd_q or None, tampered, mask_shifted, partials): partials f64 [2, wm_splice_nparts(enc.numel())], row 0 the PSNR sums of
+    splice_fwd (zeros without `real`; psnr_gate takes partials[0]), row 1 the sums of mask_shifted (copymove_valid)."""
+    if enc.dim() != 4 or enc.dtype != torch.float32:
+        raise ValueError(f"copymove_fwd: enc must be float32 [B,C,H,W], got {enc.dtype} {tuple(enc.shape)}")
+    B, C, H, W = enc.shape
+    if tuple(mask.shape) != (B, 1, H, W) or mask.dtype != torch.float32:
+        raise ValueError(f"copymove_fwd: mask must be float32 [{B},1,{H},{W}], got {mask.dtype} {tuple(mask.shape)}")
+    if real is not None and (real.shape != enc.shape or real.dtype != torch.float32):
+        raise ValueError(f"copymove_fwd: real must be float32 {tuple(enc.shape)}, got {real.dtype} {tuple(real.shape)}")
+    sh = _copymove_shifts(shifts, B)
+    for t in (enc, mask, real, shifts if torch.is_tensor(shifts) else None):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("copymove_fwd runs on the HIP path only: move the tensors to cuda (shifts: or pass a host sequence of pairs)")
+    sh = sh.contiguous() if sh.is_cuda else sh.to(enc.device)
+    enc = enc.contiguous(); mask = mask.contiguous()
+    real = real.contiguous() if real is not None else None
+    L = _lib.lib()
+    fwd = torch.empty_like(enc) if want_fwd else None
+    tam = torch.empty_like(enc)
+    ms = torch.empty_like(mask)
+    part = torch.empty(2, L.wm_splice_nparts(enc.numel()), device=enc.device, dtype=torch.float64)
+    rc = L.wm_copymove_fwd(_p(enc), _p(real), _p(mask), _p(sh), _p(fwd), _p(tam), _p(ms), _p(part), B, C, H, W, _stream())
+    _lib.check(rc, "wm_copymove_fwd")
+    return fwd, tam, ms, part
+
+
+def copymove_valid(partials, count):
+    """[1] f32 device tensor: mean of the shifted mask over count = B*H*W pixels (IRNp_model.py:592) from copymove_fwd's partials; no host sync"""
+    _need_cuda(partials)
+    if partials.dim() != 2 or partials.shape[0] != 2 or partials.dtype != torch.float64 or not partials.is_contiguous() or count <= 0:
+        raise ValueError("copymove_valid: contiguous float64 partials [2, nparts] of copymove_fwd and a positive count expected")
+    out = torch.empty(1, device=partials.device, dtype=torch.float32)
+    rc = _lib.lib().wm_copymove_valid(_p(partials), partials.shape[1], float(count), _p(out), _stream())
+    _lib.check(rc, "wm_copymove_valid")
+    return out
+
+
 def psnr_gate(partials, n, threshold=33.0, w_below=1.0, w_above=0.8):
     """[2] f32 device tensor: (PSNR, forward-loss weight) -- IRNcrop_model.py:379-388, no host sync"""
     out = torch.empty(2, device=partials.device, dtype=torch.float32)
