@@ -685,6 +685,37 @@ int wm_coupling_fwd(const void* x, const void* s, const void* t, void* y, size_t
 int wm_coupling_bwd(const void* g, const void* v, const void* s, void* gx, void* gs, void* gt, size_t n, float clamp, float eps, int rev,
                     int dtype, void* stream);
 
+/* ------------------------------------------------------------------ InvBlockExp couplings (csrc/invblock.hip)
+ * replaces, for models/modules/Inv_arch.py InvBlockExp (:55-88), everything but the subnets F, G, H: x.narrow, the add, sigmoid / exp /
+ * mul / div, torch.cat and torch.sum(self.s).  n1 = split_len1, n2 = split_len2, cp(n) = n rounded up to 16.  NHWC tensors of `dtype`, f32
+ * arithmetic; x is the block's input [npix][xstride], read in place: x1 = channels [0, n1), x2 = channels [n1, n1 + n2) (WM_E_BADARG when
+ * they do not fit the stride, or a stride is no multiple of 16).  Padding channels of every output are written as zero, those of an input
+ * are never used.  16-byte accesses when every base pointer is 16-byte aligned, element accesses otherwise: the same bits either way.
+ * wm_invblock_shift : v = x1 + sign * f (sign +1 / -1), f [npix][cp(n1)].  other == NULL: out [npix][cp(n1)] = v (the forward's y1);
+ *                     other [npix][cp(n2)]: out [npix][cp(n1+n2)] = cat(v, other[:, :n2]) (the reverse's block output).
+ * wm_invblock_affine: s = clamp * (2 sigmoid(h) - 1); rev 0: v = x2 * exp(s) + g; rev 1: v = (x2 - g) / exp(s); h, g [npix][cp(n2)].
+ *                     other [npix][cp(n1)]: out [npix][cp(n1+n2)] = cat(other[:, :n1], v) (the forward's block output); other == NULL:
+ *                     out [npix][cp(n2)] = v (the reverse's y2).  npix = B * hw.  jac != NULL: jac[b] = the sum of s over sample b's hw pixels
+ *                     and n2 channels, added in double in a fixed order (per-workgroup partials in `scratch`, wm_invblock_scratch_doubles
+ *                     doubles, then one small launch) and stored as f32: two calls give the same bits.  exp(s) is wm_coupling_fwd's e(s), eps = 0.
+ * wm_invblock_shift_bwd : gout = dL/dout, whole != 0: [npix][cp(n1+n2)] as the forward wrote it with `other`, else [npix][cp(n1)].
+ *                     gx [npix][gxstride] = dL/dx (gout in channels < n1, zero elsewhere), gf [npix][cp(n1)] = sign * gout,
+ *                     gother [npix][cp(n2)] = gout's channels [n1, n1+n2) (whole only, NULL otherwise).
+ * wm_invblock_affine_bwd: gout as above (whole: the v channels are read in place at n1; else [npix][cp(n2)]).  v = x for rev 0 (vstride =
+ *                     xstride, voff = n1), the forward's stored OUTPUT for rev 1 (voff = n1 in the whole form, 0 otherwise) -- wm_coupling_bwd's
+ *                     rule.  gx [npix][gxstride] (zero outside [n1, n1+n2)), gh, gg [npix][cp(n2)], gother [npix][cp(n1)] = gout's
+ *                     channels < n1 (whole only). */
+int wm_invblock_shift(const void* x, int xstride, const void* f, const void* other, void* out, size_t npix, int n1, int n2, float sign,
+                      int dtype, void* stream);
+int wm_invblock_shift_bwd(const void* gout, int whole, void* gx, int gxstride, void* gf, void* gother, size_t npix, int n1, int n2,
+                          float sign, int dtype, void* stream);
+size_t wm_invblock_scratch_doubles(int B, size_t hw, int n1, int n2);
+int wm_invblock_affine(const void* x, int xstride, const void* h, const void* g, const void* other, void* out, float* jac,
+                       double* scratch, int B, size_t hw, int n1, int n2, float clamp, int rev, int dtype, void* stream);
+int wm_invblock_affine_bwd(const void* gout, int whole, const void* v, int vstride, int voff, const void* h, void* gx, int gxstride,
+                           void* gh, void* gg, void* gother, size_t npix, int n1, int n2, float clamp, int rev, int dtype,
+                           void* stream);
+
 /* ------------------------------------------------------------------ instance normalisation (csrc/instnorm.hip)
  * replaces nn.InstanceNorm2d(C, eps, affine, track_running_stats=False) and the nn.ReLU behind it: models/modules/Subnet_constructor.py:149-169
  * (ResBlock, the coupling subnet 'Resnet'), models/conditional_jpeg_generator.py conv() letter I, models/networks.py's use_spectral_norm=False

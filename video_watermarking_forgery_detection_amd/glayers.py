@@ -309,6 +309,17 @@ class _AddFn(Function):
         return g, g
 
 
+class _SubFn(Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        return ops.add_scaled(a, b, -1.0)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        return g, ops.add_scaled(g, g, -2.0)        # g - 2 g = -g, exactly
+
+
 class _QFAttFn(Function):
     """x + gamma * res + beta, gamma / beta f32 [B, Cp] (conditional_jpeg_generator.py:196-200)"""
 
@@ -402,6 +413,10 @@ def to_nchw(x, C, H=None, W=None):
 
 def add(a, b):
     return _AddFn.apply(a, b)
+
+
+def sub(a, b):
+    return _SubFn.apply(a, b)
 
 
 def qf_attention(x, res, gamma, beta):
@@ -760,6 +775,59 @@ def chan_cat(a, na, b, nb):
 
 def coupling(x, s, t, clamp, eps, rev):
     return _CouplingFn.apply(x, s, t, float(clamp), float(eps), bool(rev))
+
+
+# ----------------------------------------------------------------------------- InvBlockExp couplings (models/modules/Inv_arch.py)
+class _InvShiftFn(Function):
+    """x[..., :n1] + sign * f, alone or as cat(that, other[..., :n2]); x is the block's whole input, read in place (ops.invblock_shift_fwd).
+    The backward is one launch: gx at x's width (zero outside the first n1 channels), gf, gother"""
+
+    @staticmethod
+    def forward(ctx, x, f, other, n1, n2, sign):
+        ctx.meta = (n1, n2, sign, other is not None, x.shape[3])
+        return ops.invblock_shift_fwd(x, f, n1, n2, sign, other)
+
+    @staticmethod
+    def backward(ctx, g):
+        n1, n2, sign, whole, xstride = ctx.meta
+        gx, gf, gother = ops.invblock_shift_bwd(g.contiguous(), n1, n2, sign, whole, xstride)
+        return gx, gf, gother, None, None, None
+
+
+class _InvAffineFn(Function):
+    """rev False: x[..., n1:n1+n2] * exp(s) + g, rev True: (.. - g) / exp(s), s = clamp * (2 sigmoid(h) - 1), alone or as
+    cat(other[..., :n1], that) (ops.invblock_affine_fwd) -> (out, jac); jac = sum of s per sample, f32 [B] (None unless want_jac), is not
+    differentiable.  Saved for the backward, as _CouplingFn does: x for rev False, the output for rev True; and h"""
+
+    @staticmethod
+    def forward(ctx, x, h, g, other, n1, n2, clamp, rev, want_jac):
+        out, jac = ops.invblock_affine_fwd(x, h, g, n1, n2, clamp, rev, other, want_jac)
+        whole = other is not None
+        ctx.save_for_backward(out if rev else x, h)
+        ctx.meta = (n1, n2, clamp, rev, whole, x.shape[3])
+        if jac is not None:
+            ctx.mark_non_differentiable(jac)
+        return out, jac
+
+    @staticmethod
+    def backward(ctx, gout, _gjac):
+        v, h = ctx.saved_tensors
+        n1, n2, clamp, rev, whole, xstride = ctx.meta
+        voff = n1 if (not rev or whole) else 0
+        gx, gh, gg, gother = ops.invblock_affine_bwd(gout.contiguous(), v, voff, h, n1, n2, clamp, rev, whole, xstride)
+        return gx, gh, gg, gother, None, None, None, None, None
+
+
+def invblock_shift(x, f, n1, n2, sign=1.0, other=None):
+    """InvBlockExp's additive half on the block's whole input x [B,H,W,cpad(n1+n2)]: x1 + sign * f [.., cpad(n1)], or with `other`
+    [.., cpad(n2)] the whole block output cat(x1 + sign * f, other)"""
+    return _InvShiftFn.apply(x, f, other, int(n1), int(n2), float(sign))
+
+
+def invblock_affine(x, h, g, n1, n2, clamp, rev, other=None, want_jac=False):
+    """InvBlockExp's affine half on the block's whole input x: (out, jac).  out = x2 * exp(s) + g (rev: (x2 - g) / exp(s)) [.., cpad(n2)], or
+    with `other` [.., cpad(n1)] the whole block output cat(other, that); jac (want_jac) = sum of s per sample, f32 [B], detached"""
+    return _InvAffineFn.apply(x, h, g, other, int(n1), int(n2), float(clamp), bool(rev), bool(want_jac))
 
 
 # ----------------------------------------------------------------------------- losses, clamp and the optimiser of the literal IRNrhi step

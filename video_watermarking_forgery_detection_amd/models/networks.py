@@ -1,12 +1,34 @@
 """models/networks.py of the reference on the HIP layer toolkit (glayers.py): `Discriminator` (networks.py:631-749),
 same constructor, same forward contract (NCHW f32 image in, [B,1,H/32,W/32] f32 out), same state_dict keys
 (`init_conv.0.weight_orig`, `.weight_u`, `.weight_v`, ..., `conv5.0.weight`); and the tamper localiser of the reference's trainers,
-`UNetDiscriminator` (networks.py:896-1113) with its `ResnetBlock` (:1387-1421), under the same rules."""
+`UNetDiscriminator` (networks.py:896-1113) with its `ResnetBlock` (:1387-1421), under the same rules; and `define_G` (:13-31), the
+factory of the IRN trainers' generator (models/modules/Inv_arch.InvRescaleNet)."""
 import torch
 import torch.nn as nn
 
 from .. import glayers as G
 from .. import ops
+
+
+def define_G(opt, subnet_type, block_num, dtype=torch.float32):
+    """networks.py:13-31: the generator of every IRN trainer from an option file's `network_G` block (`in_nc`, `out_nc`, `scale` ->
+    down_num = log2(scale), `init`, default 'xavier'): InvRescaleNet(in_nc, out_nc, subnet, block_num, down_num).  subnet_type 'DBNet'
+    (what every option file of the reference names) takes Subnet_constructor.DenseBlock directly -- `subnet('DBNet')` keeps refusing --
+    any other name goes through `subnet(subnet_type, init)`."""
+    import math
+
+    from .modules.Inv_arch import InvRescaleNet
+    from .modules.Subnet_constructor import DenseBlock, subnet
+
+    opt_net = opt["network_G"]
+    init = opt_net["init"] if opt_net.get("init") else "xavier"
+    down_num = int(math.log(opt_net["scale"], 2))
+    if subnet_type == "DBNet":
+        def constructor(channel_in, channel_out):
+            return DenseBlock(channel_in, channel_out, init) if init == "xavier" else DenseBlock(channel_in, channel_out)
+    else:
+        constructor = subnet(subnet_type, init)
+    return InvRescaleNet(opt_net["in_nc"], opt_net["out_nc"], constructor, block_num, down_num, dtype=dtype)
 
 
 def spectral_norm_conv(cin, cout, k, stride, padding, use_spectral_norm):

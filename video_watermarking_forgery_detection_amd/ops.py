@@ -1880,6 +1880,77 @@ def coupling_bwd(g, v, s, clamp, eps, rev):
     return gx, gs, gt
 
 
+# ----------------------------------------------------------------------------- InvBlockExp couplings (csrc/invblock.hip)
+def _invblock_args(name, x, n1, n2, **tensors):
+    """x [B,H,W,>= n1+n2] and every named tensor [B,H,W,stride] of x's pixel grid and dtype, contiguous -> (x, the tensors, npix)"""
+    x = _nhwc(x)
+    if n1 < 1 or n2 < 1 or n1 + n2 > x.shape[3]:
+        raise ValueError(f"{name}: channels [0,{n1 + n2}) do not fit the stride {x.shape[3]}")
+    out = []
+    for k, (t, stride) in tensors.items():
+        if t is not None:
+            t = _nhwc(t)
+            if t.shape[:3] != x.shape[:3] or t.dtype != x.dtype or t.shape[3] != stride:
+                raise ValueError(f"{name}: {k} {tuple(t.shape)} {t.dtype} is not [{', '.join(map(str, x.shape[:3]))}, {stride}] {x.dtype}")
+        out.append(t)
+    return x, out, x.shape[0] * x.shape[1] * x.shape[2]
+
+
+def invblock_shift_fwd(x, f, n1, n2, sign, other=None):
+    """x[..., :n1] + sign * f as its own tensor [.., cpad(n1)], or, with other [.., cpad(n2)], as cat(that, other[..., :n2]) [.., cpad(n1+n2)]"""
+    x, (f, other), npix = _invblock_args("invblock_shift_fwd", x, n1, n2, f=(f, cpad(n1)), other=(other, cpad(n2)))
+    out = torch.empty(*x.shape[:3], cpad(n1 + n2) if other is not None else cpad(n1), device=x.device, dtype=x.dtype)
+    rc = _lib.lib().wm_invblock_shift(_p(x), x.shape[3], _p(f), _p(other), _p(out), npix, n1, n2, float(sign), dt_id(x.dtype), _stream())
+    _lib.check(rc, "wm_invblock_shift")
+    return out
+
+
+def invblock_shift_bwd(g, n1, n2, sign, whole, xstride):
+    """g = dL/dout of invblock_shift_fwd (whole: it had `other`) -> (gx [.., xstride], gf [.., cpad(n1)], gother [.., cpad(n2)] or None)"""
+    g = _nhwc(g)
+    if g.shape[3] != (cpad(n1 + n2) if whole else cpad(n1)) or n1 + n2 > xstride:
+        raise ValueError(f"invblock_shift_bwd: gradient stride {g.shape[3]} / x stride {xstride} do not match splits {n1}, {n2}")
+    new = lambda c: torch.empty(*g.shape[:3], c, device=g.device, dtype=g.dtype)       # noqa: E731
+    gx, gf, gother = new(xstride), new(cpad(n1)), (new(cpad(n2)) if whole else None)
+    rc = _lib.lib().wm_invblock_shift_bwd(_p(g), 1 if whole else 0, _p(gx), xstride, _p(gf), _p(gother), g.shape[0] * g.shape[1] * g.shape[2],
+                                          n1, n2, float(sign), dt_id(g.dtype), _stream())
+    _lib.check(rc, "wm_invblock_shift_bwd")
+    return gx, gf, gother
+
+
+def invblock_affine_fwd(x, h, g, n1, n2, clamp, rev, other=None, want_jac=False):
+    """s = clamp * (2 sigmoid(h) - 1); v = x[..., n1:n1+n2] * exp(s) + g (rev: (.. - g) / exp(s)) as its own tensor [.., cpad(n2)], or, with
+    other [.., cpad(n1)], as cat(other[..., :n1], v) [.., cpad(n1+n2)].  -> (out, jac): jac f32 [B] = sum of s per sample (None unless
+    want_jac), summed in double in a fixed order"""
+    x, (h, g, other), npix = _invblock_args("invblock_affine_fwd", x, n1, n2, h=(h, cpad(n2)), g=(g, cpad(n2)), other=(other, cpad(n1)))
+    B, hw = x.shape[0], x.shape[1] * x.shape[2]
+    out = torch.empty(*x.shape[:3], cpad(n1 + n2) if other is not None else cpad(n2), device=x.device, dtype=x.dtype)
+    jac = scratch = None
+    if want_jac:
+        jac = torch.empty(B, device=x.device, dtype=torch.float32)
+        scratch = torch.empty(max(int(_lib.lib().wm_invblock_scratch_doubles(B, hw, n1, n2)), 1), device=x.device, dtype=torch.float64)
+    rc = _lib.lib().wm_invblock_affine(_p(x), x.shape[3], _p(h), _p(g), _p(other), _p(out), _p(jac), _p(scratch), B, hw, n1, n2, float(clamp),
+                                       1 if rev else 0, dt_id(x.dtype), _stream())
+    _lib.check(rc, "wm_invblock_affine")
+    return out, jac
+
+
+def invblock_affine_bwd(gout, v, voff, h, n1, n2, clamp, rev, whole, xstride):
+    """gout = dL/dout of invblock_affine_fwd (whole: it had `other`); v = x (rev False, voff = n1) or the forward's output (rev True, voff =
+    n1 if whole else 0) -> (gx [.., xstride], gh, gg [.., cpad(n2)], gother [.., cpad(n1)] or None)"""
+    gout, v, h = _nhwc(gout), _nhwc(v), _nhwc(h)
+    if gout.shape[3] != (cpad(n1 + n2) if whole else cpad(n2)) or h.shape[3] != cpad(n2) or n1 + n2 > xstride or voff + n2 > v.shape[3] \
+            or not (gout.shape[:3] == v.shape[:3] == h.shape[:3]) or not (gout.dtype == v.dtype == h.dtype):
+        raise ValueError("invblock_affine_bwd: operands disagree with the splits %d, %d" % (n1, n2))
+    new = lambda c: torch.empty(*gout.shape[:3], c, device=gout.device, dtype=gout.dtype)       # noqa: E731
+    gx, gh, gg, gother = new(xstride), new(cpad(n2)), new(cpad(n2)), (new(cpad(n1)) if whole else None)
+    rc = _lib.lib().wm_invblock_affine_bwd(_p(gout), 1 if whole else 0, _p(v), v.shape[3], voff, _p(h), _p(gx), xstride, _p(gh), _p(gg), _p(gother),
+                                           gout.shape[0] * gout.shape[1] * gout.shape[2], n1, n2, float(clamp), 1 if rev else 0,
+                                           dt_id(gout.dtype), _stream())
+    _lib.check(rc, "wm_invblock_affine_bwd")
+    return gx, gh, gg, gother
+
+
 # ----------------------------------------------------------------------------- instance normalisation (csrc/instnorm.hip)
 INSTNORM_ACTS = {None: 0, "relu": 1}
 
