@@ -741,6 +741,38 @@ int wm_instnorm_bwd_sums(const void* x, const void* dy, const float* mean, const
 int wm_instnorm_bwd_apply(const void* x, const void* dy, const float* mean, const float* rstd, const float* gamma, const float* beta,
                           const float* mg, const float* mgx, void* dx, int B, size_t hw, int C, int CP, int act, int dtype, void* stream);
 
+/* ------------------------------------------------------------------ LayerNorm and Swin window attention (csrc/swin.hip)
+ * replaces, in network/SUNet_detail.py: nn.LayerNorm (norm1 / norm2, :192,198) and, in one launch each way, the roll (:238,255),
+ * window_partition / window_reverse (:27-56), the head split, q*scale @ k^T, the relative-position bias gather, the shifted-window mask add,
+ * the softmax and attn @ v of WindowAttention.forward (:113-135).  Activations of `dtype` (WM_F32 / WM_BF16 / WM_F16) are token grids
+ * [tokens][CP] = [B][H][W][CP], C real channels of a stride CP that is a multiple of 16; padding channels are written as zeros.
+ * wm_layernorm_fwd : y = (x - mean) * rstd * gamma + beta over the C channels of every token, biased variance, rstd = 1 / sqrt(var + eps);
+ *                    mean and var in f32 (two passes over the row); mean, rstd: f32 [tokens], kept for the backward.  gamma, beta: f32 [C].
+ * wm_layernorm_bwd : dx = rstd * (dy gamma - mean_c(dy gamma) - xhat mean_c(dy gamma xhat)); dgamma = sum over tokens of dy * xhat, dbeta = of dy
+ *                    (NULL together: not computed), summed in double over slices of the tokens whose partial rows a finalise launch adds in
+ *                    order: no atomics, two calls give the same bits.  scratch: wm_layernorm_scratch_doubles(tokens, C) doubles.
+ * wm_winattn_fwd   : qkv [B][H][W][CP3], the qkv Linear's output on the un-partitioned grid, channel = (q|k|v) * C + head * hd + d with
+ *                    hd = C / nH <= 96; out [B][H][W][CPO], channel = head * hd + d.  Per window of ws x ws tokens (1 <= ws <= 8, H and W
+ *                    multiples of ws) of the grid rolled by -shift (0 <= shift < ws) and per head:
+ *                    out = softmax(scale * q k^T + table[rel_index] + mask) v.  table: f32 [(2 ws - 1)^2][nH]; rel_index and mask (-100 where
+ *                    the two tokens' regions of the rolled grid differ, shift > 0 only) are the reference's (:86-96, :202-221), computed in
+ *                    the kernel.  lse: f32 [B][nH][H][W], the row log-sum-exp, kept for the backward.
+ * wm_winattn_bwd   : g_qkv [B][H][W][CP3] and g_table [(2 ws - 1)^2][nH] for the output gradient g_out [B][H][W][CPO]; the probabilities are
+ *                    recomputed from qkv and lse.  g_table sums dS over samples, windows and token pairs by relative index: per-workgroup
+ *                    partial tables in scratch (wm_winattn_scratch_floats floats) added in order; no atomics, two calls give the same bits.
+ * bf16 / f16: both products of each direction run on MFMA with f32 accumulation; f32: FMAs.  The softmax is f32 with the row maximum
+ * subtracted. */
+size_t wm_layernorm_scratch_doubles(size_t tokens, int C);
+int wm_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, size_t tokens, int C, int CP,
+                     float eps, int dtype, void* stream);
+int wm_layernorm_bwd(const void* x, const void* dy, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
+                     float* dbeta, double* scratch, size_t tokens, int C, int CP, int dtype, void* stream);
+size_t wm_winattn_scratch_floats(int B, int H, int W, int nH, int ws);
+int wm_winattn_fwd(const void* qkv, const float* table, void* out, float* lse, int B, int H, int W, int C, int nH, int ws, int shift,
+                   float scale, int CP3, int CPO, int dtype, void* stream);
+int wm_winattn_bwd(const void* g_out, const void* qkv, const float* table, const float* lse, void* g_qkv, float* g_table, float* scratch,
+                   int B, int H, int W, int C, int nH, int ws, int shift, float scale, int CP3, int CPO, int dtype, void* stream);
+
 /* ------------------------------------------------------------------ losses of the literal IRNrhi step
  * replaces, in models/IRNrhi_model.py:425-560: nn.SmoothL1Loss (:148,476,481), nn.BCELoss (:147,492-493,505), nn.CrossEntropyLoss
  * (:156,454,485), torch.clamp(x,0,1) with its gradient mask (:430,472), PSNR of the postprocess()ed images (:527, metrics.py:30-46).

@@ -585,7 +585,8 @@ class ReflectionPad2d(nn.Module):
 
 
 class Linear(nn.Module):
-    """nn.Linear on [B,1,1,Cp] activations (a 1x1 convolution); `weight` [out,in], `bias` [out]"""
+    """nn.Linear on [B,1,1,Cp] activations or on every token of a [B,H,W,Cp] grid (a 1x1 convolution either way); `weight` [out,in],
+    `bias` [out]"""
 
     def __init__(self, in_features, out_features, bias=True):
         super().__init__()
@@ -668,6 +669,82 @@ class InstanceNorm2d(nn.Module):
 
     def extra_repr(self):
         return f"{self.num_features}, eps={self.eps}, affine={self.affine}" + (f", act={self.act}" if self.act else "")
+
+
+class _LayerNormFn(Function):
+    """nn.LayerNorm over the channels of every token: the forward keeps x and the f32 statistics per token; the backward recomputes xhat"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, C, eps):
+        gamma, beta = weight.detach().contiguous(), bias.detach().contiguous()
+        y, mean, rstd = ops.layernorm_fwd(x, C, gamma, beta, eps)
+        ctx.save_for_backward(x, mean, rstd, gamma)
+        ctx.C = C
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, mean, rstd, gamma = ctx.saved_tensors
+        dx, dgamma, dbeta = ops.layernorm_bwd(x, g, ctx.C, gamma, mean, rstd, want_params=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        return (dx if ctx.needs_input_grad[0] else None), (dgamma if ctx.needs_input_grad[1] else None), \
+            (dbeta if ctx.needs_input_grad[2] else None), None, None
+
+
+class LayerNorm(nn.Module):
+    """nn.LayerNorm(C, eps) (affine) over the channels of every token of a [B,H,W,Cp] grid; parameters `weight`, `bias` [C]"""
+
+    def __init__(self, normalized_shape, eps=1e-5):
+        super().__init__()
+        if not isinstance(normalized_shape, int):
+            (normalized_shape,) = normalized_shape
+        self.normalized_shape, self.eps = (int(normalized_shape),), float(eps)
+        self.weight = nn.Parameter(torch.ones(normalized_shape))
+        self.bias = nn.Parameter(torch.zeros(normalized_shape))
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("the HIP layer toolkit runs on the GPU only; there is no CPU fallback")
+        C = self.normalized_shape[0]
+        if x.dim() != 4 or x.shape[3] != cpad(C):
+            raise ValueError(f"LayerNorm expects a token grid [B,H,W,{cpad(C)}] of {C} channels, got {tuple(x.shape)}")
+        return _LayerNormFn.apply(x, self.weight, self.bias, C, self.eps)
+
+    def extra_repr(self):
+        return f"{self.normalized_shape}, eps={self.eps}"
+
+
+class _WindowAttentionFn(Function):
+    """the Swin attention core as one node over two launches; keeps qkv, the table and the row log-sum-exp"""
+
+    @staticmethod
+    def forward(ctx, qkv, table, C, num_heads, ws, shift, scale):
+        tbl = table.detach().contiguous()
+        out, lse = ops.winattn_fwd(qkv, tbl, C, num_heads, ws, shift, scale)
+        ctx.save_for_backward(qkv, tbl, lse)
+        ctx.meta = (C, num_heads, ws, shift, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        qkv, tbl, lse = ctx.saved_tensors
+        g_qkv, g_table = ops.winattn_bwd(g, qkv, tbl, lse, *ctx.meta)
+        return (g_qkv if ctx.needs_input_grad[0] else None), (g_table if ctx.needs_input_grad[1] else None), None, None, None, None, None
+
+
+def window_attention(qkv, table, num_heads, ws, shift, scale, H, W, dim=None):
+    """softmax(scale q k^T + table[relative index] + shifted-window mask) v per (ws x ws window of the grid rolled by -shift, head), written
+    back at the tokens' own grid positions.  qkv [B,H,W,cpad(3C)]: the qkv Linear's output on the un-partitioned grid, channels in the
+    reference's reshape(B_, N, 3, nH, hd) order; table f32 [(2ws-1)^2, nH] -> [B,H,W,cpad(C)].  dim = C; it may be left out only when the
+    stride says it (3C a multiple of 16)"""
+    if not qkv.is_cuda:
+        raise RuntimeError("the HIP layer toolkit runs on the GPU only; there is no CPU fallback")
+    if qkv.dim() != 4 or tuple(qkv.shape[1:3]) != (H, W):
+        raise ValueError(f"window_attention expects a [B,{H},{W},Cp] grid, got {tuple(qkv.shape)}")
+    if dim is None:
+        if qkv.shape[3] % 3:
+            raise ValueError(f"window_attention: a qkv stride of {qkv.shape[3]} does not say how many channels it holds; pass dim")
+        dim = qkv.shape[3] // 3
+    return _WindowAttentionFn.apply(qkv, table, int(dim), int(num_heads), int(ws), int(shift), float(scale))
 
 
 class GlobalAvgPool(nn.Module):

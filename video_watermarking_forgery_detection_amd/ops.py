@@ -2034,6 +2034,95 @@ def instnorm_splits(hw):
     return _lib.lib().wm_instnorm_splits(hw)
 
 
+# ----------------------------------------------------------------------------- LayerNorm and Swin window attention (csrc/swin.hip)
+def _layernorm_args(name, x, C, gamma, beta):
+    x = _nhwc(x)
+    _need_cuda(gamma, beta)
+    if not 0 < C <= x.shape[3]:
+        raise ValueError(f"{name}: {C} channels in a stride of {x.shape[3]}")
+    for t in (gamma, beta):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != C or not t.is_contiguous()):
+            raise ValueError(f"{name}: gamma / beta must be contiguous float32 [{C}]")
+    return x
+
+
+def layernorm_fwd(x, C, gamma, beta, eps=1e-5):
+    """nn.LayerNorm(C, eps)(x) over the C channels of every token of x [B,H,W,Cp] -> (y, mean, rstd); mean, rstd f32 [B*H*W]; padding
+    channels of y written as zeros"""
+    x = _layernorm_args("layernorm_fwd", x, C, gamma, beta)
+    B, H, W, CP = x.shape
+    y = torch.empty_like(x)
+    mean = torch.empty(B * H * W, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(B * H * W, device=x.device, dtype=torch.float32)
+    rc = _lib.lib().wm_layernorm_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), B * H * W, C, CP, float(eps), dt_id(x.dtype), _stream())
+    _lib.check(rc, "wm_layernorm_fwd")
+    return y, mean, rstd
+
+
+def layernorm_bwd(x, dy, C, gamma, mean, rstd, want_params=True):
+    """(dx, dgamma, dbeta) of layernorm_fwd for the output gradient dy; xhat is recomputed from x.  dgamma / dbeta f32 [C] (None with
+    want_params False): partial rows in double added in a fixed order, so two calls give the same bits"""
+    x = _layernorm_args("layernorm_bwd", x, C, gamma, None)
+    _need_cuda(dy, mean, rstd)
+    dy = dy.contiguous()
+    if dy.shape != x.shape or dy.dtype != x.dtype:
+        raise ValueError("layernorm_bwd: the output gradient does not match the input")
+    B, H, W, CP = x.shape
+    L = _lib.lib()
+    dx = torch.empty_like(x)
+    dgamma = dbeta = part = None
+    if want_params:
+        part = torch.empty(L.wm_layernorm_scratch_doubles(B * H * W, C), device=x.device, dtype=torch.float64)
+        dgamma = torch.empty(C, device=x.device, dtype=torch.float32)
+        dbeta = torch.empty(C, device=x.device, dtype=torch.float32)
+    rc = L.wm_layernorm_bwd(_p(x), _p(dy), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta), _p(part), B * H * W, C, CP, dt_id(x.dtype),
+                            _stream())
+    _lib.check(rc, "wm_layernorm_bwd")
+    return dx, dgamma, dbeta
+
+
+def _winattn_args(name, qkv, table, C, num_heads, ws):
+    qkv = _nhwc(qkv)
+    _need_cuda(table)
+    if C % num_heads or qkv.shape[3] != cpad(3 * C):
+        raise ValueError(f"{name}: qkv of stride {qkv.shape[3]} for 3 x {C} channels in {num_heads} heads (expected stride {cpad(3 * C)})")
+    if table.dtype != torch.float32 or not table.is_contiguous() or tuple(table.shape) != ((2 * ws - 1) ** 2, num_heads):
+        raise ValueError(f"{name}: the bias table must be contiguous float32 [{(2 * ws - 1) ** 2}, {num_heads}], got {tuple(table.shape)} {table.dtype}")
+    return qkv
+
+
+def winattn_fwd(qkv, table, C, num_heads, ws, shift, scale):
+    """the (shifted-)window attention core on the token grid: qkv [B,H,W,cpad(3C)] (channel = (q|k|v)*C + head*hd + d) -> (out [B,H,W,cpad(C)],
+    lse f32 [B,nH,H,W]).  Roll, window partition, head split, bias gather, mask, softmax and their reverses are one launch"""
+    qkv = _winattn_args("winattn_fwd", qkv, table, C, num_heads, ws)
+    B, H, W, CP3 = qkv.shape
+    out = torch.empty(B, H, W, cpad(C), device=qkv.device, dtype=qkv.dtype)
+    lse = torch.empty(B, num_heads, H, W, device=qkv.device, dtype=torch.float32)
+    rc = _lib.lib().wm_winattn_fwd(_p(qkv), _p(table), _p(out), _p(lse), B, H, W, C, num_heads, ws, shift, float(scale), CP3, cpad(C), dt_id(qkv.dtype),
+                                   _stream())
+    _lib.check(rc, "wm_winattn_fwd")
+    return out, lse
+
+
+def winattn_bwd(g_out, qkv, table, lse, C, num_heads, ws, shift, scale):
+    """(g_qkv [B,H,W,cpad(3C)], g_table f32 [(2ws-1)^2, nH]) of winattn_fwd; the probabilities are recomputed from qkv and lse.  g_table is
+    summed from per-workgroup partial tables in a fixed order: two calls give the same bits"""
+    qkv = _winattn_args("winattn_bwd", qkv, table, C, num_heads, ws)
+    _need_cuda(g_out, lse)
+    g_out = g_out.contiguous()
+    B, H, W, CP3 = qkv.shape
+    if tuple(g_out.shape) != (B, H, W, cpad(C)) or g_out.dtype != qkv.dtype:
+        raise ValueError("winattn_bwd: the output gradient does not match the forward's output")
+    L = _lib.lib()
+    g_qkv = torch.empty_like(qkv)
+    g_table = torch.empty_like(table)
+    scratch = torch.empty(L.wm_winattn_scratch_floats(B, H, W, num_heads, ws), device=qkv.device, dtype=torch.float32)
+    rc = L.wm_winattn_bwd(_p(g_out), _p(qkv), _p(table), _p(lse), _p(g_qkv), _p(g_table), _p(scratch), B, H, W, C, num_heads, ws, shift, float(scale),
+                          CP3, cpad(C), dt_id(qkv.dtype), _stream())
+    _lib.check(rc, "wm_winattn_bwd")
+    return g_qkv, g_table
+
+
 # ----------------------------------------------------------------------------- losses of the literal IRNrhi step (SURVEY 8f row 1)
 def _nparts(n):
     return max(1, min(1024, (n + 4095) // 4096))
