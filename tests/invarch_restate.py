@@ -269,6 +269,9 @@ class ShiftCase:
         self.gother = finish(*_placed(cp2, npix, (0, g[:, n1:], np.zeros((npix, n2)))), dt) if whole else None
         self.label = "invblock_shift %s npix=%d %d/%d sign=%+g %s" % (dt, npix, n1, n2, sign, "whole" if whole else "own")
 
+    def largest_stored(self):
+        return float(np.abs(self.out[0]).max())
+
     def check_fwd(self, out):
         return [Cmp(self.label + " out", out, *self.out)]
 
@@ -339,6 +342,10 @@ class AffineCase:
         self.gother = finish(*_placed(cp1, npix, (0, go[:, :n1], np.zeros((npix, n1)))), dt) if whole else None
         self.label = "invblock_affine %s B=%d hw=%d %d/%d rev=%d %s clamp=%g" % (dt, B, hw, n1, n2, self.rev, "whole" if whole else "own", clamp)
 
+    def largest_stored(self):
+        """the largest |reference| among the outputs stored in the activation type (f16: must stay below 65504)"""
+        return float(max(np.abs(t[0]).max() for t in (self.out, self.gx, self.gh, self.gg)))
+
     def check_fwd(self, out, jac=None):
         c = [Cmp(self.label + " out", out, *self.out)]
         return c + ([Cmp(self.label + " jac", jac, *self.jac)] if jac is not None else [])
@@ -348,10 +355,17 @@ class AffineCase:
         return c + ([Cmp(self.label + " gother", gother, *self.gother)] if self.whole else [])
 
 
-SPLITS = ((3, 9), (3, 45))
-PIXELS = ((2, 35), (1, 257))            # (B, hw): 70 pixels = 2 x 5 x 7, no multiple of a block or a vector; 257
-KERNEL_DTYPES = ("f32", "bf16")
+# n1 / n2.  3 / 9 and 3 / 45 are the reference's; n1 = 4 (f32), 8 (16-bit) and 16 are multiples of the vector, so an operand n1 channels
+# off the walk is loaded as vectors at c0 + shift (ld_win's guard i0 >= 0); 19 / 13 has n1 > 16 (two vectors of padding walk) and n2 < n1
+SPLITS = ((3, 9), (3, 45), (4, 8), (8, 24), (16, 32), (19, 13))
+# (B, hw): 70 pixels = 2 x 5 x 7, no multiple of a block or a vector; 257; B = 5 and 16: jac rows b >= 4 (jac_finalize's b += 4 loop)
+PIXELS = ((2, 35), (1, 257), (5, 3), (16, 9))
+KERNEL_DTYPES = ("f32", "bf16", "f16")
 CLAMPS = (1.0, 0.0)
+MAX_F16 = 65504.0
+P64_KEY = (1, 5462, 3, 45)              # hw * 48 > 64 * 4096: the jac partial count at its cap of 64
+BIG_KEY = (2, 21850, 3, 45)             # 43 700 pixels, f32, misaligned: 43 700 * 48 > 8192 * 256 (a second grid-stride trip of the three
+#                                         capped kernels); 21 850 * 48 / 256 > 2048 (the no-jac forward's grid at its cap)
 
 
 def affine_keys(dt):

@@ -12,6 +12,9 @@
    roundings is accepted within R * k * (sum of |terms|), R = FACTOR * 2**-24; expf / logf take U ulps of their result, propagated through
    the expression that uses them; an operand rounded to bf16 / f16 for the MFMA adds half an ulp of that type; a stored value adds its
    store rounding (finish).  Probabilities below the float32 normal range may be flushed: MIN_NORMAL is added to every probability's bound.
+   f16 is the same model with half_ulp(., "f16"): 2**-11 relative and never below 2**-25, the half-spacing of the subnormals that P and
+   dS reach below 2**-14 as operands; the data keeps every stored value below 65504 (largest_stored(), asserted in tests/test_cpu_swin.py).
+   tests/test_cpu_swin.py holds float32 imitations of the kernels that pass these models and named defects that fail them.
 """
 import numpy as np
 import torch
@@ -363,16 +366,38 @@ class LnCase:
         self.dbeta = (dbet, ulp32(dbet) + GX.TINY32)
         self.label = "layernorm %s T=%d C=%d" % (dt, T, C)
 
+    def largest_stored(self):
+        """the largest |reference| among the outputs stored in the activation type (f16: must stay below 65504)"""
+        return float(max(np.abs(self.y[0]).max(), np.abs(self.dx[0]).max()))
+
     def check(self, y, mean, rstd, dx, dgamma, dbeta):
         return [Cmp(self.label + " " + k, got, *ref) for k, got, ref in (("y", y, self.y), ("mean", mean, self.mean), ("rstd", rstd, self.rstd),
                                                                           ("dx", dx, self.dx), ("dgamma", dgamma, self.dgamma), ("dbeta", dbeta, self.dbeta))]
 
 
-LN_C = (1, 24, 96, 100)
-LN_T = (1, 3, 130)
-KERNEL_DTYPES = ("f32", "bf16")
-# (ws, hd, heads, shift, H, W)
-ATTN_SHAPES = ((4, 12, 2, 2, 8, 8), (7, 24, 2, 3, 14, 7), (8, 96, 1, 4, 8, 16), (8, 12, 8, 0, 8, 8), (1, 4, 1, 0, 2, 2), (2, 5, 3, 1, 4, 4))
+# C: 16 / 64 no padding and exactly one lane pass, 65 one over; 192 / 384 / 768 the reference's widths (EMB_DIM 96 doubled per stage), 257 /
+# 384 / 768 the second and third channel block of the parameter kernel, 768 twelve elements per lane.  T: 4 / 5 a full workgroup and one
+# over, 64 / 65 the slice boundary, 130 three slices.  LN_BIG (f32 only): ceil(T / 256) = 65 > 64, the LN_MAX_SLICES branch of ln_slice()
+LN_C = (1, 16, 24, 64, 65, 96, 100, 192, 257, 384, 768)
+LN_T = (1, 3, 4, 5, 64, 65, 130)
+LN_BIG = (16385 + 130, 16)
+KERNEL_DTYPES = ("f32", "bf16", "f16")
+MAX_F16 = 65504.0
+# (ws, hd, heads, shift, H, W); the first six are the cases the kernels arrived with
+ATTN_SHAPES = ((4, 12, 2, 2, 8, 8), (7, 24, 2, 3, 14, 7), (8, 96, 1, 4, 8, 16), (8, 12, 8, 0, 8, 8), (1, 4, 1, 0, 2, 2), (2, 5, 3, 1, 4, 4),
+               (8, 48, 2, 4, 8, 16),      # the reference's third stage: two chunks, the last 16 wide; head 1 starts at channel 48
+               (4, 32, 3, 1, 8, 12),      # an exact chunk; shift 1, several windows along both axes
+               (4, 33, 1, 3, 12, 8),      # one channel over a chunk; shift ws - 1
+               (2, 64, 1, 1, 4, 6),       # two full chunks
+               (3, 5, 3, 1, 6, 9),        # MT / KS = 1 / 1 with padding rows (N = 9)
+               (5, 12, 2, 2, 10, 5),      # MT / KS = 2 / 1 (N = 25)
+               (6, 24, 1, 5, 12, 12),     # MT / KS = 3 / 2 (N = 36), shift ws - 1
+               (8, 96, 2, 7, 16, 8))      # three chunks, two heads, shift ws - 1
+
+
+def ln_keys(dt):
+    """(dt, T, C) of every LayerNorm case of a dtype"""
+    return [(dt, T, C) for C in LN_C for T in LN_T] + ([(dt,) + LN_BIG] if dt == "f32" else [])
 
 
 class AttnCase:
@@ -407,7 +432,11 @@ class AttnCase:
         bias = table[rel_index_rule(ws)].transpose(2, 0, 1)[None, None]
         msk = mask_rule(H, W, ws, shift)[None, :, None]
         aqk = scale * np.einsum("bwhid,bwhjd->bwhij", np.abs(q), np.abs(k))
-        dS = R * (hd + 3) * (aqk + np.abs(bias) + np.abs(msk)) + GX.TINY32
+        # the roundings wa_scores performs: hd products summed (<= hd), per chunk the product with scale and the sum with the chunks
+        # before (2 each), all on the dot product's terms; the table entry added once (1 rounding on |s| + |bias|), then the mask's -100
+        # added once (1 rounding on |s + bias| + 100): neither is multiplied by the depth of the sum
+        nchunk = (hd + 31) // 32
+        dS = R * ((hd + 2 * nchunk + 2) * aqk + 2 * np.abs(bias) + np.abs(msk)) + GX.TINY32
         m = S.max(-1, keepdims=True)
         P = softmax64(S)
         self.spread = float((S.max(-1) - S.min(-1)).max())
@@ -451,6 +480,10 @@ class AttnCase:
         np.add.at(bt, idx, (dSg + R * (N + 1) * np.abs(Sg)).sum((0, 1)).transpose(1, 2, 0).reshape(N * N, nH))
         self.gtable = (gt, bt + ulp32(gt) + GX.TINY32)
         self.label = "winattn %s ws=%d hd=%d heads=%d shift=%d %dx%d" % (dt, ws, hd, nH, shift, H, W)
+
+    def largest_stored(self):
+        """the largest |reference| among the values stored or used as MFMA operands in the activation type (f16: below 65504)"""
+        return float(max(np.abs(self.out[0]).max(), np.abs(self.gqkv[0]).max(), np.abs(self.qkv[..., :3 * self.C]).max()))
 
     def lse_grid(self):
         """(reference, bound) [B, nH, H, W]"""

@@ -1,6 +1,6 @@
 """The invertible rescaling generator (models/modules/Inv_arch.py, Subnet_constructor.DenseBlock, networks.define_G) without a GPU: the
 float64 restatement against the fixture made from the reference's own modules, the state_dict surface, the initialisers, the refusals and
-the C ABI's new symbols."""
+the C ABI's new symbols; then the coupling kernels' bound model against float32 imitations of csrc/invblock.hip, faithful and defective."""
 import ctypes
 import os
 
@@ -167,3 +167,276 @@ def test_bound_model_accepts_a_faithful_float32_imitation_and_rejects_defects():
         assert IR.GX.all_ok(c.check_fwd(out)), IR.GX.first_bad(c.check_fwd(out))
         out[:, :c.n1] = c.x[:, :c.n1] - c.sign * c.f[:, :c.n1]
         assert not IR.GX.all_ok(c.check_fwd(out))
+
+
+# ================================================================================================= the kernels' bound model, without a GPU
+# Float32 numpy imitations of csrc/invblock.hip's four kernels and its jac reduction, written over the kernels' own addressing (a walk over
+# the channels of the widest output, every operand a window `Win` onto that walk), must pass the bound model of invarch_restate.py on
+# every key in f32 / bf16 / f16; each named defect, switched on inside the imitation, must FAIL the unchanged model at the case named for it
+import functools  # noqa: E402
+
+from layers_exact import TORCH, VE, all_ok  # noqa: E402
+
+f32 = np.float32
+GUARD = 64
+
+
+def a32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def stored(v, dt):
+    v = a32(v)
+    return v.astype(np.float64) if dt == "f32" else torch.from_numpy(v).to(TORCH[dt]).double().numpy()
+
+
+def must_pass(cmps):
+    for c in cmps:
+        c.assert_ok()
+
+
+def must_fail(cmps, what):
+    assert not all_ok(cmps), "the defect `%s` passed every comparison" % what
+
+
+# ---- the dispatch formulas of invblock.hip
+def grid1(n, cap=8192):
+    return min(max(-(-n // 256), 1), cap)
+
+
+def wm_groups(n, unit, cap):
+    return min(max(-(-n // unit), 1), cap)
+
+
+def jac_parts(hw, ostride):
+    return wm_groups(hw * ostride, 4096, 64)
+
+
+def ld_win(arr, stride, shift, lo, hi, width, early=0):
+    """ld_win over the whole walk: [npix, width] float32, walk channel c in [lo, hi) = element pix * stride + c + shift - early of the
+    operand, any other channel 0.  (early: the defect's offset; an address before the first element reads the guard)"""
+    npix = arr.shape[0]
+    out = np.zeros((npix, width), dtype=f32)
+    if arr is None:
+        return out
+    flat = np.concatenate([np.full(GUARD, IR.SENTINEL), np.asarray(arr, dtype=np.float64).reshape(-1), np.full(GUARD, IR.SENTINEL)])
+    c = np.arange(max(lo, 0), min(hi, width))
+    out[:, c] = a32(flat[GUARD + np.arange(npix)[:, None] * stride + c[None] + shift - early])
+    return out
+
+
+def vector_load(dt, shift):
+    """ld_win takes its 16-byte load at c0 + shift: the shift is a non-zero multiple of the vector"""
+    return shift != 0 and shift % VE[dt] == 0
+
+
+def tail_store(dest, vals, gxs, n1, n2, cp2, zero_tail=True):
+    """the element-wise store of shift_bwd's gother and affine_bwd's gh / gg [npix, cp2] from walk channel c of gxs: j = c - n1 for c >= n1,
+    and the walk's first n1 channels zero j = gxs - n1 + c, what the walk's end leaves of the padding"""
+    for c in range(gxs):
+        j = gxs - n1 + c if c < n1 else c - n1
+        if j < cp2 and (c >= n1 or zero_tail):
+            dest[:, j] = vals[:, c] if (c >= n1 and j < n2) else 0.0
+
+
+def imit_shift(c, defect=None):
+    """shift_fwd_kernel and shift_bwd_kernel -> (out, (gx, gf, gother))"""
+    n1, n2, dt, npix = c.n1, c.n2, c.dt, c.npix
+    early = VE[dt] if (defect == "vector window load one vector early" and vector_load(dt, -n1)) else 0
+    x = ld_win(c.x, c.cp, 0, 0, n1, c.ostride)
+    f = ld_win(c.f, c.cp1, 0, 0, n1, c.ostride)
+    r = x + f32(c.sign) * f
+    if c.whole:
+        oshift = 0 if defect == "other read at shift 0" else -n1
+        r[:, n1:] = ld_win(c.other, c.cp2, oshift, n1, n1 + n2, c.ostride, early)[:, n1:]
+    out = stored(r, dt)
+    g = ld_win(c.g, c.ostride, 0, 0, n1 + n2 if c.whole else n1, c.cp)
+    gx, gf = np.zeros((npix, c.cp)), np.zeros((npix, c.cp1))
+    gx[:, :n1], gf[:, :n1] = stored(g[:, :n1], dt), stored(f32(c.sign) * g[:, :n1], dt)
+    gother = None
+    if c.whole:
+        gother = np.full((npix, c.cp2), IR.SENTINEL)
+        tail_store(gother, stored(g, dt), c.cp, n1, n2, c.cp2)
+    return out, (gx, gf, gother)
+
+
+def imit_affine(c, defect=None):
+    """affine_fwd_kernel (with its partials), jac_finalize_kernel and affine_bwd_kernel -> ((out, jac), (gx, gh, gg, gother))"""
+    n1, n2, dt, npix, B, hw, vo = c.n1, c.n2, c.dt, c.npix, c.B, c.hw, c.vo
+    cl, ve = f32(c.clamp), VE[dt]
+    early = (lambda shift: ve if (defect == "vector window load one vector early" and vector_load(dt, shift)) else 0)
+    width = c.ostride
+    hi = width if defect == "jac summed over the padded channels" else vo + n2
+    x = ld_win(c.x, c.cp, n1 - vo, vo, vo + n2, width, early(n1 - vo))
+    h = ld_win(c.h, c.cp2, -vo, vo, min(hi, vo + c.cp2), width, early(-vo))
+    g = ld_win(c.g, c.cp2, -vo, vo, vo + n2, width, early(-vo))
+    with np.errstate(over="ignore"):
+        s = cl * (f32(2) / (f32(1) + np.exp(-h)) - f32(1))
+    ex = np.exp(s)
+    v = (x / ex - g) if (c.rev and defect == "rev 1 as x / ex - g") else ((x - g) / ex if c.rev else ex * x + g)
+    r = np.zeros((npix, width), dtype=f32)
+    r[:, vo:vo + n2] = v[:, vo:vo + n2]
+    if c.whole:
+        r[:, :n1] = ld_win(c.other, c.cp1, 0, 0, n1, width)[:, :n1]
+    out = stored(r, dt)
+    # the partials: workgroup j of P takes vectors j * 256 + t, + P * 256, ... of its sample's hw * (ostride / VE); summed in double
+    P, per = jac_parts(hw, width), width // ve
+    sv = s.astype(np.float64)
+    sv[:, :vo], sv[:, hi:] = 0.0, 0.0
+    sv = sv.reshape(B, hw * per, ve).sum(2)
+    group = (np.arange(hw * per) // 256) % P
+    partials = np.stack([np.bincount(group, weights=sv[b], minlength=P) for b in range(B)])
+    src = np.arange(B) % 4 if defect == "jac of sample b from the partials of b mod 4" else np.arange(B)
+    jac = a32(partials[src].sum(1))
+    # ---- backward: walk = the channels of gx [npix, cp]
+    W = c.cp
+    go = ld_win(c.gout, c.gout.shape[1], 0 if c.whole else -n1, n1, n1 + n2, W, early(0 if c.whole else -n1))
+    vv = ld_win(c.v, c.v.shape[1], c.voff - n1, n1, n1 + n2, W, early(c.voff - n1))
+    hb = ld_win(c.h, c.cp2, -n1, n1, n1 + n2, W, early(-n1))
+    with np.errstate(over="ignore"):
+        sg = f32(1) / (f32(1) + np.exp(-hb))
+    exb = np.exp(cl * (f32(2) * sg - f32(1)))
+    de = exb * cl * f32(2) * sg
+    if defect != "gh without (1 - sg)":
+        de = de * (f32(1) - sg)
+    if c.rev:
+        ge = go / exb
+        rx, rg, rh = ge, -ge, -ge * vv * de
+    else:
+        rx, rg, rh = exb * go, go, go * vv * de
+    gx = np.zeros((npix, W))
+    gx[:, n1:n1 + n2] = stored(rx, dt)[:, n1:n1 + n2]
+    gh, gg = np.full((npix, c.cp2), IR.SENTINEL), np.full((npix, c.cp2), IR.SENTINEL)
+    zero_tail = defect != "padding of gh / gg beyond n2 not zeroed"
+    rh_stored = stored(rh, dt)
+    if defect == "gh stored by a fused multiply-convert" and dt == "f16":       # the last product rounded to f16 once, not to float32 first
+        last = (-ge * vv if c.rev else go * vv).astype(np.float64) * de.astype(np.float64)
+        rh_stored = last.astype(np.float16).astype(np.float64)                 # (numpy rounds a double to half in one step)
+    tail_store(gh, rh_stored, W, n1, n2, c.cp2, zero_tail)
+    tail_store(gg, stored(rg, dt), W, n1, n2, c.cp2, zero_tail)
+    gother = None
+    if c.whole:
+        o0 = n1 if defect == "gother from channels [n1, 2 n1)" else 0
+        gother = stored(ld_win(c.gout, c.cp, o0, 0, n1, c.cp1), dt)
+    return (out, jac), (gx, gh, gg, gother)
+
+
+AFFINE_EXTRA = [("f32",) + IR.P64_KEY + (0, True, 1.0), ("f16",) + IR.P64_KEY + (0, True, 1.0)]
+AFFINE_KEYS = [k for dt in IR.KERNEL_DTYPES for k in IR.affine_keys(dt)] + AFFINE_EXTRA
+SHIFT_KEYS = [k for dt in IR.KERNEL_DTYPES for k in IR.shift_keys(dt)]
+
+
+@functools.lru_cache(maxsize=None)
+def affine_case(*key):
+    return IR.AffineCase(*key)
+
+
+@functools.lru_cache(maxsize=None)
+def shift_case(*key):
+    return IR.ShiftCase(*key)
+
+
+def check_affine(c, got):
+    return c.check_fwd(*got[0]) + c.check_bwd(*got[1])
+
+
+def check_shift(c, got):
+    return c.check_fwd(got[0]) + c.check_bwd(*got[1])
+
+
+@pytest.mark.parametrize("dt", IR.KERNEL_DTYPES)
+def test_invblock_imitations_pass(dt):
+    """every affine and shift key of the dtype (and the 64-partial case); no reference value is beyond f16's largest"""
+    for key in [k for k in AFFINE_KEYS if k[0] == dt]:
+        c = affine_case(*key)
+        must_pass(check_affine(c, imit_affine(c)))
+        assert c.largest_stored() < IR.MAX_F16
+    for key in [k for k in SHIFT_KEYS if k[0] == dt]:
+        c = shift_case(*key)
+        must_pass(check_shift(c, imit_shift(c)))
+        assert c.largest_stored() < IR.MAX_F16
+
+
+def test_big_case_imitation_passes():
+    c = IR.AffineCase("f32", *IR.BIG_KEY, 0, True, 1.0)
+    must_pass(check_affine(c, imit_affine(c)))
+
+
+# (defect, kind, key): affine keys (dt, B, hw, n1, n2, rev, whole, clamp), shift keys (dt, npix, n1, n2, sign, whole)
+INV_DEFECTS = [
+    ("other read at shift 0", "shift", ("f32", 70, 3, 9, -1.0, True)),
+    ("other read at shift 0", "shift", ("f16", 257, 8, 24, 1.0, True)),
+    ("vector window load one vector early", "shift", ("f32", 70, 4, 8, -1.0, True)),
+    ("vector window load one vector early", "shift", ("f16", 15, 8, 24, 1.0, True)),
+    ("vector window load one vector early", "affine", ("bf16", 2, 35, 16, 32, 0, True, 1.0)),
+    ("vector window load one vector early", "affine", ("f16", 5, 3, 8, 24, 1, False, 1.0)),
+    ("rev 1 as x / ex - g", "affine", ("f32", 2, 35, 3, 9, 1, True, 1.0)),
+    ("rev 1 as x / ex - g", "affine", ("f16", 16, 9, 19, 13, 1, False, 1.0)),
+    ("jac summed over the padded channels", "affine", ("f32", 1, 257, 3, 9, 0, False, 1.0)),
+    ("jac summed over the padded channels", "affine", ("f16", 5, 3, 19, 13, 1, False, 1.0)),         # 13 of 16 channels
+    ("jac of sample b from the partials of b mod 4", "affine", ("f32", 5, 3, 3, 45, 0, True, 1.0)),
+    ("jac of sample b from the partials of b mod 4", "affine", ("f16", 16, 9, 4, 8, 1, True, 1.0)),
+    ("gh without (1 - sg)", "affine", ("bf16", 2, 35, 3, 45, 0, True, 1.0)),
+    ("gh without (1 - sg)", "affine", ("f16", 1, 257, 16, 32, 1, False, 1.0)),
+    ("gother from channels [n1, 2 n1)", "affine", ("f32", 2, 35, 3, 9, 0, True, 1.0)),
+    ("gother from channels [n1, 2 n1)", "affine", ("f16", 16, 9, 8, 24, 1, True, 0.0)),
+    ("padding of gh / gg beyond n2 not zeroed", "affine", ("f32", 5, 3, 19, 13, 0, True, 1.0)),
+    ("padding of gh / gg beyond n2 not zeroed", "affine", ("f16", 2, 35, 19, 13, 1, False, 1.0)),
+]
+
+
+def test_a_fused_store_breaks_the_two_paths_bit_equality():
+    """found on the GPU by test_element_wise_path_gives_the_vector_path_s_bits[f16]: the compiler merged gh's last product with its f16
+    conversion (one rounding) in the element-wise instantiation of affine_bwd_kernel only.  Either store is within the bound model (see
+    gelem_exact.finish), so what rejects it is the bit comparison of the two paths: the imitation with the fused store passes the model on
+    every f16 key and differs from the faithful one in some bits of gh, and of gh only (the two roundings differ from the single one for
+    about one product in 2**12, so the keys are taken together)"""
+    differ = 0
+    for key in [k for k in AFFINE_KEYS if k[0] == "f16" and k[-1] == 1.0]:
+        c = affine_case(*key)
+        want, got = imit_affine(c), imit_affine(c, "gh stored by a fused multiply-convert")
+        must_pass(check_affine(c, got))
+        for i, (a, b) in enumerate(zip(want[0] + want[1], got[0] + got[1])):
+            assert i == 3 or a is None or np.array_equal(a, b), (key, i)
+        differ += int((want[1][1] != got[1][1]).sum())
+    assert differ > 0
+
+
+@pytest.mark.parametrize("defect,kind,key", INV_DEFECTS)
+def test_invblock_defects_fail(defect, kind, key):
+    if kind == "shift":
+        assert key in SHIFT_KEYS
+        c = shift_case(*key)
+        must_fail(check_shift(c, imit_shift(c, defect)), defect)
+    else:
+        assert key in AFFINE_KEYS
+        c = affine_case(*key)
+        must_fail(check_affine(c, imit_affine(c, defect)), defect)
+
+
+def test_key_tables_reach_every_path():
+    """invblock.hip's dispatch formulas restated (cpad16, VE, the vector-load condition of ld_win, jac_parts, grid1, the no-jac grid) against
+    the key tables: every value the GPU tests are meant to visit is visited"""
+    splits = set(IR.SPLITS)
+    assert {(3, 9), (3, 45)} <= splits                                            # the reference's
+    for dt in IR.KERNEL_DTYPES:
+        ve = VE[dt]
+        assert ve == 16 // {"f32": 4, "bf16": 2, "f16": 2}[dt]
+        vec = {n1 for n1, _ in splits if vector_load(dt, -n1)}                     # the 16-byte load at c0 + shift, shift != 0
+        assert vec >= ({4, 8, 16} if dt == "f32" else {8, 16}) and any(not vector_load(dt, -n1) for n1, _ in splits)
+        assert any(n1 >= ve and vector_load(dt, -n1) for n1 in vec)               # ... whose first vector fails the guard i0 >= 0
+    assert any(n1 > 16 and IR.cpad(n1) == 32 for n1, _ in splits)                  # cp1 = 32: the padding walk of shift_bwd / affine_bwd
+    assert any(IR.cpad(n1 + n2) - n1 < IR.cpad(n2) for n1, n2 in splits)           # ... has channels of gh / gg / gother left to zero
+    assert any(n2 < n1 for n1, n2 in splits) and any(IR.cpad(n1 + n2) == n1 + n2 for n1, n2 in splits)
+    B = {b for b, _ in IR.PIXELS}
+    assert {1, 2} <= B and any(4 < b < 8 for b in B) and any(b >= 16 for b in B)   # jac_finalize: b = w, w + 4, ...: one, two and four trips
+    parts = {jac_parts(hw, IR.cpad(n1 + n2)) for _, hw in IR.PIXELS for n1, n2 in splits}
+    assert {1, 4} <= parts and jac_parts(IR.P64_KEY[1], IR.cpad(IR.P64_KEY[2] + IR.P64_KEY[3])) == 64
+    assert IR.P64_KEY[1] * 48 > 64 * 4096 >= (IR.P64_KEY[1] - 1) * 48              # the smallest hw that reaches the cap
+    assert all(grid1(b * hw * IR.cpad(n1 + n2)) < 8192 for b, hw in IR.PIXELS for n1, n2 in splits)
+    b, hw, n1, n2 = IR.BIG_KEY
+    total = b * hw * IR.cpad(n1 + n2)                                             # the element-wise walk: one element per thread and trip
+    assert grid1(total) == 8192 and total > 8192 * 256                            # a second trip of the three capped kernels
+    assert wm_groups(hw * IR.cpad(n1 + n2), 256, 2048) == 2048 and hw * IR.cpad(n1 + n2) > 2048 * 256    # the no-jac forward's grid
+    assert jac_parts(hw, IR.cpad(n1 + n2)) == 64
+    assert IR.KERNEL_DTYPES == ("f32", "bf16", "f16")

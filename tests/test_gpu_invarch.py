@@ -50,6 +50,16 @@ def report(cmps):
         c.assert_ok()
 
 
+def _worst(worst, cmps):
+    for m in cmps:
+        k = m.what.split()[-1]
+        worst[k] = max(worst.get(k, 0.0), m.worst)
+
+
+def _fractions(what, worst):
+    print("worst fractions %s: %s" % (what, ", ".join("%s %.3f" % kv for kv in worst.items())))
+
+
 def _run_affine(c, misalign=False, want_jac=True):
     _lib, ops, L, stream = _mods()
     dtid = ops.dt_id(GX.TORCH[c.dt])
@@ -83,25 +93,59 @@ def _same_bits(a, b):
 
 @pytest.mark.parametrize("dt", IR.KERNEL_DTYPES)
 def test_affine_kernels_per_element(dt):
-    """forward (with jac) and backward, 70 and 257 pixels, splits 3/9 and 3/45, rev 0 / 1, both `other` forms, clamp 1 and 0, h with 0 and
-    +-20; SENTINEL in every input's padding, every destination pre-filled with SENTINEL and compared whole (padding: exact zeros); a second
-    run gives the same bits"""
+    """forward (with jac) and backward over invarch_restate.PIXELS (70 and 257 pixels; 5 and 16 samples: jac rows b >= 4) x SPLITS (3/9 and
+    3/45; n1 = 4, 8, 16: the vector load at c0 + shift; 19/13: n1 > 16), rev 0 / 1, both `other` forms, clamp 1 and 0, h with 0 and +-20;
+    SENTINEL in every input's padding, every destination pre-filled with SENTINEL and compared whole (padding: exact zeros); a second run
+    gives the same bits.  The worst error-to-bound fraction of each quantity is printed at the end"""
+    worst = {}
     for key in IR.affine_keys(dt):
         c = IR.AffineCase(*key)
         fwd, bwd = _run_affine(c)
-        report(c.check_fwd(*fwd) + c.check_bwd(*bwd))
+        cmps = c.check_fwd(*fwd) + c.check_bwd(*bwd)
+        report(cmps)
+        _worst(worst, cmps)
         fwd2, bwd2 = _run_affine(c)
         assert _same_bits(fwd + bwd, fwd2 + bwd2), c.label + ": two runs differ"
+    _fractions("invblock_affine " + dt, worst)
+
+
+@pytest.mark.parametrize("dt", IR.KERNEL_DTYPES)
+def test_jac_with_64_partials(dt):
+    """one sample of 5462 pixels, split 3/45: hw * 48 > 64 * 4096, so the forward writes 64 partials (the cap) and the finalise's wave sums a
+    full row of lanes"""
+    c = IR.AffineCase(dt, *IR.P64_KEY, 0, True, 1.0)
+    fwd, bwd = _run_affine(c)
+    report(c.check_fwd(*fwd) + c.check_bwd(*bwd))
+    fwd2, bwd2 = _run_affine(c)
+    assert _same_bits(fwd + bwd, fwd2 + bwd2), c.label + ": two runs differ"
+
+
+def test_second_grid_stride_trip_on_the_element_wise_path():
+    """43 700 pixels, split 3/45, f32, base pointers one element past a 16-byte boundary: 43 700 * 48 elements > 8192 * 256 threads, so the
+    grid-stride loops of shift_fwd / shift_bwd / affine_bwd take a second trip, and the no-jac forward's grid is at its cap of 2048; every
+    output whole against the model"""
+    c = IR.AffineCase("f32", *IR.BIG_KEY, 0, True, 1.0)
+    fwd, bwd = _run_affine(c, misalign=True)
+    report(c.check_fwd(*fwd) + c.check_bwd(*bwd))
+    (out_nojac, _), _ = _run_affine(c, misalign=True, want_jac=False)
+    report(c.check_fwd(out_nojac))
+    c = IR.ShiftCase("f32", IR.BIG_KEY[0] * IR.BIG_KEY[1], 3, 45, -1.0, True)
+    out, bwd = _run_shift(c, misalign=True)
+    report(c.check_fwd(out) + c.check_bwd(*bwd))
 
 
 @pytest.mark.parametrize("dt", IR.KERNEL_DTYPES)
 def test_shift_kernels_per_element(dt):
+    worst = {}
     for key in IR.shift_keys(dt):
         c = IR.ShiftCase(*key)
         out, bwd = _run_shift(c)
-        report(c.check_fwd(out) + c.check_bwd(*bwd))
+        cmps = c.check_fwd(out) + c.check_bwd(*bwd)
+        report(cmps)
+        _worst(worst, cmps)
         out2, bwd2 = _run_shift(c)
         assert _same_bits((out,) + bwd, (out2,) + bwd2), c.label + ": two runs differ"
+    _fractions("invblock_shift " + dt, worst)
 
 
 @pytest.mark.parametrize("dt", IR.KERNEL_DTYPES)

@@ -48,15 +48,22 @@ template <typename T, int VE> __device__ __forceinline__ void ld_win(const Win& 
             if (c0 + e >= w.lo && c0 + e < w.hi) v[e] = to_f32(row[i0 + e]);
     }
 }
+// the f32 result as it is stored: the value is pinned in a register before its conversion, so the compiler cannot merge the conversion
+// with the operation before it.  For f16 it otherwise may (v_fma_mixlo_f16: the product rounded to f16 once, not to f32 and then to f16),
+// and it did so in the element-wise instantiation of affine_bwd_kernel only: the two paths' gh then differed in a last bit
+__device__ __forceinline__ float pinned(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
 // dst: the first of VE consecutive elements, 16-byte aligned when VE > 1
 template <typename T, int VE> __device__ __forceinline__ void st_run(T* dst, const float (&v)[VE]) {
     if constexpr (VE > 1) {
         vec16<T> q;
 #pragma unroll
-        for (int e = 0; e < VE; ++e) q.set(e, v[e]);
+        for (int e = 0; e < VE; ++e) q.set(e, pinned(v[e]));
         *reinterpret_cast<decltype(q.v)*>(dst) = q.v;
     } else {
-        dst[0] = from_f32<T>(v[0]);
+        dst[0] = from_f32<T>(pinned(v[0]));
     }
 }
 
@@ -108,7 +115,7 @@ __global__ __launch_bounds__(256) void shift_bwd_kernel(ShiftBwdArgs a) {
 #pragma unroll
             for (int e = 0; e < VE; ++e) {
                 const int c = c0 + e, j = c < a.n1 ? a.gxs - a.n1 + c : c - a.n1;     // (channels < n1 zero what the walk's end leaves of the padding)
-                if (j < a.cp2) q[j] = from_f32<T>(c >= a.n1 && j < a.n2 ? gv[e] : 0.f);
+                if (j < a.cp2) q[j] = from_f32<T>(pinned(c >= a.n1 && j < a.n2 ? gv[e] : 0.f));
             }
         }
     }
@@ -202,7 +209,7 @@ __global__ __launch_bounds__(256) void affine_bwd_kernel(AffBwdArgs a) {
 #pragma unroll
         for (int e = 0; e < VE; ++e) {
             const int c = c0 + e, j = c < a.n1 ? a.gxs - a.n1 + c : c - a.n1;     // (channels < n1 zero what the walk's end leaves of the padding)
-            if (j < a.cp2) { qh[j] = from_f32<T>(rh[e]); qg[j] = from_f32<T>(rg[e]); }
+            if (j < a.cp2) { qh[j] = from_f32<T>(pinned(rh[e])); qg[j] = from_f32<T>(pinned(rg[e])); }
         }
         if (a.gother && c0 < a.cp1) {
             float o[VE];
