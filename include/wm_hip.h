@@ -18,7 +18,8 @@
  *     (wm_debug_* setters) of tools/ and the tests exist only in the -DWM_DEBUG build lib/libwm_hip_dbg.so;
  *     neither build reads an environment variable;
  *   - return value: 0 = ok, <0 = error (WM_E_*); wm_last_error_string() gives the text of
- *     the last error on the calling thread.  No C++ exception crosses the boundary;
+ *     the last error on the calling thread.  No C++ exception crosses the boundary.  A function that can fail
+ *     takes at least one pointer; an int function with scalar parameters only is a query whose int is its answer;
  *   - activations are NHWC ("pixel-major"): element (b,h,w,c) lives at
  *     base[((b*H + h)*W + w) * ld + c], ld >= C the per-pixel channel stride (lets a tensor
  *     be a channel-slice of a wider one).  dtype of activations/packed weights:

@@ -81,6 +81,71 @@ def test_loaded_handles_carry_the_header_signatures():
         "wm_g": (ctypes.c_int, []), "wm_h": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_double, ctypes.c_float])}
 
 
+def test_checked_handles_raise_from_the_status_functions_only():
+    """checked(), for both builds: every declared function typed as the header says, an errcheck on exactly status_functions() -- and none
+    on any function of the raw handles, whose callers assert the return codes"""
+    _lib = _built()
+    sigs, status = _lib.signatures(), _lib.status_functions()
+    release = _lib.checked()
+    with _lib.use_debug_library() as raw_debug:
+        debug = _lib.checked()
+        assert raw_debug is _lib.debug_lib() and _lib.checked() is debug      # created once
+    assert _lib.checked() is release and len({id(h) for h in (release, debug, _lib.lib(), _lib.debug_lib())}) == 4
+    for h in (release, debug):
+        for n, (restype, argtypes) in sigs.items():
+            f = getattr(h, n)
+            assert list(f.argtypes) == argtypes and f.restype is restype, n
+        assert {n for n in sigs if getattr(h, n).errcheck is not None} == status
+    for n in _lib.debug_setters():
+        f = getattr(debug, n)
+        assert list(f.argtypes) == [ctypes.c_int] and f.restype is None and f.errcheck is None, n
+    for h in (_lib.lib(), _lib.debug_lib()):
+        assert not [n for n in list(sigs) + _lib.debug_setters() if hasattr(h, n) and getattr(h, n).errcheck is not None]
+
+
+def test_status_functions_are_the_int_functions_that_take_a_pointer():
+    """the header's rule (Conventions): what can fail takes a pointer; an int function of scalars only is a query and its int the answer"""
+    from video_watermarking_forgery_detection_amd import _lib
+    sigs, status = _lib.signatures(), _lib.status_functions()
+    assert {"wm_adam_hyper", "wm_jpeg_fwd_act", "wm_pack_w3x3_batch"} <= status
+    assert not status & {"wm_abi_version", "wm_fin_rider_enabled", "wm_conv3x3_nparts", "wm_conv3x3_bwd_fused_kernel"}
+    assert not [n for n in status if sigs[n][0] in (ctypes.c_size_t, ctypes.c_char_p)]
+    assert any(r is ctypes.c_size_t for r, _ in sigs.values()) and sigs["wm_last_error_string"][0] is ctypes.c_char_p
+    ints = {n for n, (r, _) in sigs.items() if r is ctypes.c_int}
+    assert status and status < ints
+    assert all(ctypes.c_void_p in sigs[n][1] for n in status) and not [n for n in ints - status if ctypes.c_void_p in sigs[n][1]]
+
+
+def test_checked_handle_raises_where_the_raw_one_returns_the_code():
+    """wm_adam_hyper is host arithmetic (no GPU): step 0 is refused -- the checked handle raises with the function's name and the library's
+    text, the raw one returns WM_E_BADARG; step 1 is served by both with the same eight floats.  Inside use_debug_library() checked() is the
+    debug build's twin, after it the release build's again"""
+    _lib = _built()
+    args = (1e-3, 0.9, 0.999, 1e-8, 0.01)
+
+    def refused(raw, chk):
+        out = (ctypes.c_float * 8)()
+        with pytest.raises(RuntimeError, match=r"wm_adam_hyper failed \(rc=-1\)") as e:
+            chk.wm_adam_hyper(*args, 0, out)
+        assert str(e.value).endswith(": " + raw.wm_last_error_string().decode()) and "wm_adam_hyper: bad arguments" in str(e.value)
+        assert raw.wm_adam_hyper(*args, 0, out) == -1
+        a, b = (ctypes.c_float * 8)(), (ctypes.c_float * 8)()
+        assert raw.wm_adam_hyper(*args, 1, a) == 0 and chk.wm_adam_hyper(*args, 1, b) == 0
+        assert list(a) == list(b) and a[2] == ctypes.c_float(1e-3).value and a[0] > 0
+    release = _lib.checked()
+    refused(_lib.lib(), release)
+    with _lib.use_debug_library() as raw_debug:
+        assert _lib.checked() is not release and getattr(_lib.checked(), _lib.debug_setters()[0]).argtypes == [ctypes.c_int]
+        refused(raw_debug, _lib.checked())
+    assert _lib.checked() is release and _lib.lib() is not raw_debug
+
+
+def test_ops_calls_through_the_checked_handle_only():
+    with open(os.path.join(ROOT, "video_watermarking_forgery_detection_amd", "ops.py")) as f:
+        src = f.read()
+    assert "_lib.check(" not in src and "_lib.lib()" not in src and "_lib.checked()" in src
+
+
 def test_every_direct_call_passes_the_header_arity():
     """ctypes refuses too few arguments but passes surplus ones through: each call of a wm_* attribute with positional arguments in the
     package, tests/ and tools/ passes exactly as many as include/wm_hip.h declares (a wm_debug_* setter: one)"""

@@ -9,6 +9,11 @@ request, by tools/ and by the tests that compare a fused kernel with its unfused
 
 Every handle _load() returns is typed from include/wm_hip.h: each declared function carries the argtypes and restype of its
 prototype, so callers pass plain Python ints, floats, None and ctypes arrays, and a call with too few arguments raises.
+
+Each build has two kinds of handle on the same shared object.  The raw ones (lib(), debug_lib(), what use_debug_library() yields) hand every
+return code back: tools/ and the tests that assert a refusal code call them, with check() where they want the exception.  The checked ones
+(checked(), what ops.py calls through) carry an errcheck on every status function -- status_functions(): returns int and takes a pointer -- that
+raises RuntimeError with the function's own name and wm_last_error_string(); queries (int from scalars only) answer through either kind.
 """
 import contextlib
 import ctypes
@@ -27,6 +32,7 @@ DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libwm_hip_dbg.so")
 _lib = None
 _release = None
 _debug = None
+_twins = {}         # raw handle -> its checked twin
 
 
 # the header's C types -> ctypes.  Closed: a type not listed here is a load error, never an untyped argument
@@ -83,8 +89,16 @@ def debug_setters():
     return sorted(names)
 
 
-def _load(path, debug=False):
-    """a handle on `path` whose functions carry the header's argtypes and restype (debug=True: and the wm_debug_* setters')"""
+@functools.lru_cache(maxsize=None)
+def status_functions():
+    """names of the functions whose int is a status (0 or WM_E_*): those that return int and take a pointer.  An int function of scalars
+    only is a query and its int the answer (include/wm_hip.h, Conventions)"""
+    return frozenset(n for n, (restype, argtypes) in signatures().items() if restype is ctypes.c_int and ctypes.c_void_p in argtypes)
+
+
+def _load(path, debug=False, checked=False):
+    """a handle on `path` whose functions carry the header's argtypes and restype (debug=True: and the wm_debug_* setters').  checked=True:
+    a CDLL of its own (so function objects of its own) whose status functions raise on a non-zero return instead of handing it back"""
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} not found: build it with `python -m video_watermarking_forgery_detection_amd.build` "
@@ -96,17 +110,35 @@ def _load(path, debug=False):
     for name, (restype, argtypes) in sigs.items():
         fn = getattr(h, name)
         fn.restype, fn.argtypes = restype, argtypes
+    if checked:
+        last_error = h.wm_last_error_string
+
+        def raise_on_error(rc, fn, args):
+            if rc == 0:
+                return rc
+            raise RuntimeError(f"{fn.__name__} failed (rc={rc}): {last_error().decode(errors='replace')}")
+        for name in status_functions():
+            getattr(h, name).errcheck = raise_on_error
     return h
 
 
 def lib():
-    """the library every op goes through: the release build unless a use_debug_library() block is open"""
+    """the raw handle on the library every op goes through: the release build unless a use_debug_library() block is open"""
     global _lib, _release
     if _lib is None:
         if _release is None:
             _release = _load(LIB_PATH)
         _lib = _release
     return _lib
+
+
+def checked():
+    """the checked twin of lib(), created once per raw handle: what ops.py calls through"""
+    raw = lib()
+    twin = _twins.get(raw)
+    if twin is None:
+        twin = _twins[raw] = _load(raw._name, debug=raw is _debug, checked=True)
+    return twin
 
 
 def loaded_path():
@@ -123,7 +155,7 @@ def debug_lib():
 
 @contextlib.contextmanager
 def use_debug_library():
-    """inside the block every op runs on the -DWM_DEBUG build, whose wm_debug_* switches the caller may flip; yields its handle"""
+    """inside the block every op runs on the -DWM_DEBUG build, whose wm_debug_* switches the caller may flip; yields its raw handle"""
     global _lib
     prev = lib()
     _lib = debug_lib()

@@ -1,7 +1,9 @@
 """Thin Python bindings over the C ABI (include/wm_hip.h): argument checking,
 output allocation by torch (device memory + streams are torch's job), raw
 pointers into libwm_hip.so.  Every function here launches HIP kernels; none has
-a CPU or PyTorch fallback.
+a CPU or PyTorch fallback.  Every call goes through _lib.checked(): a status
+function that fails raises RuntimeError under its own name, so no call site
+looks at a return code.
 """
 import ctypes
 
@@ -19,6 +21,8 @@ def dt_id(dtype):
         return _DT[dtype]
     except KeyError:
         raise TypeError(f"unsupported activation dtype {dtype} (float32, bfloat16 or float16)") from None
+
+
 JPEG_ROUND, JPEG_SS, JPEG_MASK = 0, 1, 2
 
 
@@ -66,9 +70,8 @@ def jpeg_fwd(x, mode, tables, subsample=0, act16_dtype=None):
     B, _, H, W = x.shape
     a16 = torch.empty(B, H, W, 16, device=x.device, dtype=act16_dtype) if act16_dtype is not None else None
     tb = _host_floats(tables) if tables is not None else None
-    rc = _timed("jpeg_fwd", None, lambda: _lib.lib().wm_jpeg_fwd_act(_p(x), _p(y), _p(a16), dt_id(act16_dtype) if a16 is not None else WM_F32, B, H,
-                                                                     W, mode, tb, subsample, _stream()))
-    _lib.check(rc, "wm_jpeg_fwd")
+    _timed("jpeg_fwd", None, lambda: _lib.checked().wm_jpeg_fwd_act(_p(x), _p(y), _p(a16), dt_id(act16_dtype) if a16 is not None else WM_F32, B, H,
+                                                                    W, mode, tb, subsample, _stream()))
     return (y, a16) if act16_dtype is not None else y
 
 
@@ -79,8 +82,7 @@ def jpeg_bwd(x, gy, mode, tables, subsample=0):
     B, _, H, W = gy.shape
     tb = _host_floats(tables) if tables is not None else None
     xx = x.contiguous() if x is not None else None
-    rc = _timed("jpeg_bwd", None, lambda: _lib.lib().wm_jpeg_bwd(_p(xx), _p(gy), _p(gx), B, H, W, mode, tb, subsample, _stream()))
-    _lib.check(rc, "wm_jpeg_bwd")
+    _timed("jpeg_bwd", None, lambda: _lib.checked().wm_jpeg_bwd(_p(xx), _p(gy), _p(gx), B, H, W, mode, tb, subsample, _stream()))
     return gx
 
 
@@ -94,8 +96,7 @@ def nchw_to_nhwc(x, out, C_off=0, zero_tail=0):
     _need_cuda(x, out)
     x = x.contiguous()
     B, C, H, W = x.shape
-    rc = _lib.lib().wm_nchw_to_nhwc(_p(x), _p(out), B, C, H, W, out.shape[-1], C_off, zero_tail, dtype_id(out), _stream())
-    _lib.check(rc, "wm_nchw_to_nhwc")
+    _lib.checked().wm_nchw_to_nhwc(_p(x), _p(out), B, C, H, W, out.shape[-1], C_off, zero_tail, dtype_id(out), _stream())
     return out
 
 
@@ -106,8 +107,7 @@ def u8_hwc_to_planes(x, scale=1.0 / 255.0):
     x = x.contiguous()
     N, H, W, C = x.shape
     y = torch.empty(N, C, H, W, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_u8_hwc_to_planes(_p(x), _p(y), N, H, W, C, scale, _stream())
-    _lib.check(rc, "wm_u8_hwc_to_planes")
+    _lib.checked().wm_u8_hwc_to_planes(_p(x), _p(y), N, H, W, C, scale, _stream())
     return y
 
 
@@ -115,8 +115,7 @@ def nhwc_to_nchw(x, C, C_off=0):
     _need_cuda(x)
     B, H, W, ld = x.shape
     y = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_nhwc_to_nchw(_p(x), _p(y), B, C, H, W, ld, C_off, dtype_id(x), _stream())
-    _lib.check(rc, "wm_nhwc_to_nchw")
+    _lib.checked().wm_nhwc_to_nchw(_p(x), _p(y), B, C, H, W, ld, C_off, dtype_id(x), _stream())
     return y
 
 
@@ -124,8 +123,7 @@ def broadcast_to_nhwc(v, out, C_off):
     _need_cuda(v, out)
     v = v.contiguous().float()
     B, H, W, ld = out.shape
-    rc = _lib.lib().wm_broadcast_to_nhwc(_p(v), _p(out), B, v.shape[1], H, W, ld, C_off, dtype_id(out), _stream())
-    _lib.check(rc, "wm_broadcast_to_nhwc")
+    _lib.checked().wm_broadcast_to_nhwc(_p(v), _p(out), B, v.shape[1], H, W, ld, C_off, dtype_id(out), _stream())
     return out
 
 
@@ -134,8 +132,7 @@ def concat_tail(msg, img, out, C_off):
     _need_cuda(msg, img, out)
     B, H, W, ld = out.shape
     msg = msg.contiguous().float(); img = img.contiguous().float()
-    rc = _lib.lib().wm_concat_tail(_p(msg), _p(img), _p(out), B, msg.shape[1], H, W, ld, C_off, ld - C_off, dtype_id(out), _stream())
-    _lib.check(rc, "wm_concat_tail")
+    _lib.checked().wm_concat_tail(_p(msg), _p(img), _p(out), B, msg.shape[1], H, W, ld, C_off, ld - C_off, dtype_id(out), _stream())
     return out
 
 
@@ -144,16 +141,14 @@ def concat_full(x, scale, shift, msg, img, out, C):
     _need_cuda(x, msg, img, out)
     B, H, W, ld = out.shape
     msg = msg.contiguous().float(); img = img.contiguous().float()
-    rc = _lib.lib().wm_concat_full(_p(x), x.shape[-1], _p(scale), _p(shift), _p(msg), _p(img), _p(out), B, C, msg.shape[1], H, W, ld, dtype_id(out),
-                                   _stream())
-    _lib.check(rc, "wm_concat_full")
+    _lib.checked().wm_concat_full(_p(x), x.shape[-1], _p(scale), _p(shift), _p(msg), _p(img), _p(out), B, C, msg.shape[1], H, W, ld, dtype_id(out),
+                                  _stream())
     return out
 
 
 def bnrelu_copy(x, scale, shift, out, C_off, C):
     B, H, W, ldx = x.shape
-    rc = _lib.lib().wm_bnrelu_copy(_p(x), ldx, _p(scale), _p(shift), _p(out), out.shape[-1], C_off, B * H * W, C, dtype_id(x), _stream())
-    _lib.check(rc, "wm_bnrelu_copy")
+    _lib.checked().wm_bnrelu_copy(_p(x), ldx, _p(scale), _p(shift), _p(out), out.shape[-1], C_off, B * H * W, C, dtype_id(x), _stream())
     return out
 
 
@@ -164,8 +159,7 @@ def pack_w3x3(w, CoutP, CinP, dtype, perm=None, transpose=False):
     shape = (9, CinP, CoutP) if transpose else (9, CoutP, CinP)
     wp = torch.empty(shape, device=w.device, dtype=dtype)
     pa = _host_ints(perm) if perm is not None else None
-    rc = _lib.lib().wm_pack_w3x3(_p(w), _p(wp), Cout, Cin, CoutP, CinP, pa, 1 if transpose else 0, dtype_id(wp), _stream())
-    _lib.check(rc, "wm_pack_w3x3")
+    _lib.checked().wm_pack_w3x3(_p(w), _p(wp), Cout, Cin, CoutP, CinP, pa, 1 if transpose else 0, dtype_id(wp), _stream())
     return wp
 
 
@@ -238,8 +232,7 @@ class PackPlan:
             return
         if self.jobs is None:
             self._build()
-        rc = _lib.lib().wm_pack_w3x3_batch(_p(self.jobs), self.njobs, self.max_elems, dt_id(self.dtype), _stream())
-        _lib.check(rc, "wm_pack_w3x3_batch")
+        _lib.checked().wm_pack_w3x3_batch(_p(self.jobs), self.njobs, self.max_elems, dt_id(self.dtype), _stream())
         for k, req in self.req.items():
             self.ver[k] = req[0]._version
         self.valid = True
@@ -247,7 +240,7 @@ class PackPlan:
 
 # ----------------------------------------------------------------------------- conv / bn
 def conv3x3_nparts(B, H, W, Cin, CoutP, dtype):
-    return _lib.lib().wm_conv3x3_nparts(B, H, W, Cin, CoutP, dt_id(dtype))
+    return _lib.checked().wm_conv3x3_nparts(B, H, W, Cin, CoutP, dt_id(dtype))
 
 
 class _WmBnBwdFin(ctypes.Structure):   # include/wm_hip.h: WmBnBwdFin
@@ -257,7 +250,7 @@ class _WmBnBwdFin(ctypes.Structure):   # include/wm_hip.h: WmBnBwdFin
 
 
 def fin_rider_enabled():
-    return bool(_lib.lib().wm_fin_rider_enabled())
+    return bool(_lib.checked().wm_fin_rider_enabled())
 
 
 def _fin_rider(fin):
@@ -291,10 +284,9 @@ def conv3x3_fwd(x, wp, bias, in_scale, in_shift, want_stats, Cin=None, reverse=F
     y = torch.empty(B, H, W, CoutP, device=x.device, dtype=x.dtype)
     st = torch.empty(conv3x3_nparts(B, H, W, Cin, CoutP, x.dtype), 2, CoutP, device=x.device, dtype=torch.float32) if want_stats else None
     info = {"B": B, "H": H, "W": W, "Cin": Cin, "CoutP": CoutP, "xform": in_scale is not None, "dtype": x.dtype}
-    rc = _timed("conv3x3_fwd", info, lambda: _lib.lib().wm_conv3x3_fwd(
+    _timed("conv3x3_fwd", info, lambda: _lib.checked().wm_conv3x3_fwd(
         _p(x), ldx, _p(wp), _p(bias), 0 if bias is None else bias.numel(), _p(in_scale), _p(in_shift), _p(y), CoutP, _p(st), B, H, W, Cin, CoutP,
         dtype_id(x), _sweep(reverse), _stream()))
-    _lib.check(rc, "wm_conv3x3_fwd")
     return y, st
 
 
@@ -307,9 +299,8 @@ def conv3x3_fwd_addin(x, wp, in_scale, in_shift, addend, reverse=False):
     y = torch.empty_like(x)
     st = torch.empty(conv3x3_nparts(B, H, W, 64, 64, x.dtype), 2, 64, device=x.device, dtype=torch.float32)
     info = {"B": B, "H": H, "W": W, "Cin": 64, "CoutP": 64, "xform": True, "dtype": x.dtype, "addin": True}
-    rc = _timed("conv3x3_fwd", info, lambda: _lib.lib().wm_conv3x3_fwd_addin(_p(x), _p(wp), _p(in_scale), _p(in_shift), _p(addend), _p(y), _p(st), B,
-                                                                             H, W, dtype_id(x), _sweep(reverse), _stream()))
-    _lib.check(rc, "wm_conv3x3_fwd_addin")
+    _timed("conv3x3_fwd", info, lambda: _lib.checked().wm_conv3x3_fwd_addin(_p(x), _p(wp), _p(in_scale), _p(in_shift), _p(addend), _p(y), _p(st), B,
+                                                                            H, W, dtype_id(x), _sweep(reverse), _stream()))
     return y, st
 
 
@@ -324,9 +315,8 @@ def concat_side_fwd(img, w, bias, msg, dtype, c_msg, L, c_img):
     P = torch.empty(B, H, W, 64, device=img.device, dtype=dtype)
     wside = torch.empty(64 * 32, device=img.device, dtype=dtype)
     mbias = torch.empty(B, 9, 64, device=img.device, dtype=torch.float32)
-    rc = _lib.lib().wm_concat_side_fwd(_p(img), _p(w), _p(bias), _p(msg), _p(wside), _p(mbias), _p(P), B, H, W, Cin, c_msg, L, c_img, dt_id(dtype),
-                                       _stream())
-    _lib.check(rc, "wm_concat_side_fwd")
+    _lib.checked().wm_concat_side_fwd(_p(img), _p(w), _p(bias), _p(msg), _p(wside), _p(mbias), _p(P), B, H, W, Cin, c_msg, L, c_img, dt_id(dtype),
+                                      _stream())
     return P
 
 
@@ -335,19 +325,17 @@ def concat_side_msg_wgrad(dy, msg, dw, accumulate, c_msg, L):
     B, H, W, C = dy.shape
     assert C == 64 and dy.is_contiguous() and dw.is_contiguous() and dw.shape[0] == 64
     msg = msg.contiguous().float()
-    partial = torch.empty(B, _lib.lib().wm_concat_side_partial_rows(), 64, device=dy.device, dtype=torch.float32)
+    partial = torch.empty(B, _lib.checked().wm_concat_side_partial_rows(), 64, device=dy.device, dtype=torch.float32)
     S = torch.empty(B, 9, 64, device=dy.device, dtype=torch.float32)
-    rc = _lib.lib().wm_concat_side_msg_wgrad(_p(dy), _p(msg), _p(partial), _p(S), _p(dw), 1 if accumulate else 0, B, H, W, dw.shape[1], c_msg, L,
-                                             dtype_id(dy), _stream())
-    _lib.check(rc, "wm_concat_side_msg_wgrad")
+    _lib.checked().wm_concat_side_msg_wgrad(_p(dy), _p(msg), _p(partial), _p(S), _p(dw), 1 if accumulate else 0, B, H, W, dw.shape[1], c_msg, L,
+                                            dtype_id(dy), _stream())
 
 
 def bn_finalize(partials, C, CP, count, gamma, beta, running_mean, running_var, momentum, eps):
     dev = partials.device
     out = torch.empty(4, CP, device=dev, dtype=torch.float32)  # scale, shift, mean, invstd
-    rc = _lib.lib().wm_bn_finalize(_p(partials), partials.shape[0], C, CP, count, _p(gamma), _p(beta), _p(running_mean), _p(running_var), momentum,
-                                   eps, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _stream())
-    _lib.check(rc, "wm_bn_finalize")
+    _lib.checked().wm_bn_finalize(_p(partials), partials.shape[0], C, CP, count, _p(gamma), _p(beta), _p(running_mean), _p(running_var), momentum,
+                                  eps, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _stream())
     return out
 
 
@@ -356,18 +344,16 @@ def bn_bwd_coef(g, gvec, y, stats, C, gamma, dgamma, dbeta, accumulate):
     (gamma*invstd, mean(gz), mean(gz*xhat)) for the apply pass."""
     B, H, W, CP = y.shape
     hw = H * W
-    L = _lib.lib()
+    L = _lib.checked()
     nparts = L.wm_bn_bwd_nparts(B * hw)
     dev = y.device
     part = torch.empty(nparts, 2, CP, device=dev, dtype=torch.float32)
     ldg = 0 if g is None else g.shape[-1]
-    rc = L.wm_bn_bwd_reduce(_p(g), ldg, _p(gvec), _p(y), CP, _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(part), B, hw, CP, dtype_id(y),
-                            _stream())
-    _lib.check(rc, "wm_bn_bwd_reduce")
+    L.wm_bn_bwd_reduce(_p(g), ldg, _p(gvec), _p(y), CP, _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(part), B, hw, CP, dtype_id(y),
+                       _stream())
     coef = torch.empty(3, CP, device=dev, dtype=torch.float32)
-    rc = L.wm_bn_bwd_finalize(_p(part), nparts, C, CP, B * hw, _p(gamma), _p(stats[3]), _p(dgamma), _p(dbeta), 1 if accumulate else 0, _p(coef),
-                              _stream())
-    _lib.check(rc, "wm_bn_bwd_finalize")
+    L.wm_bn_bwd_finalize(_p(part), nparts, C, CP, B * hw, _p(gamma), _p(stats[3]), _p(dgamma), _p(dbeta), 1 if accumulate else 0, _p(coef),
+                         _stream())
     return coef
 
 
@@ -376,9 +362,8 @@ def bn_bwd_coef_raw(partials, y, stats, C, gamma, dgamma, dbeta, accumulate):
     (conv3x3_dgrad_bwdstats): no pass over (g, y)."""
     B, H, W, CP = y.shape
     coef = torch.empty(3, CP, device=y.device, dtype=torch.float32)
-    rc = _lib.lib().wm_bn_bwd_finalize_raw(_p(partials), partials.shape[0], C, CP, B * H * W, _p(gamma), _p(stats[2]), _p(stats[3]), _p(dgamma),
-                                           _p(dbeta), 1 if accumulate else 0, _p(coef), _stream())
-    _lib.check(rc, "wm_bn_bwd_finalize_raw")
+    _lib.checked().wm_bn_bwd_finalize_raw(_p(partials), partials.shape[0], C, CP, B * H * W, _p(gamma), _p(stats[2]), _p(stats[3]), _p(dgamma),
+                                          _p(dbeta), 1 if accumulate else 0, _p(coef), _stream())
     return coef
 
 
@@ -388,7 +373,7 @@ def bn_bwd(g, gvec, y, stats, C, gamma, dgamma, dbeta, accumulate, dbias, coef=N
     coef: the result of bn_bwd_coef / bn_bwd_coef_raw when the reduce pass already ran (dgamma / dbeta written there)."""
     B, H, W, CP = y.shape
     hw = H * W
-    L = _lib.lib()
+    L = _lib.checked()
     dev = y.device
     if coef is None:
         coef = bn_bwd_coef(g, gvec, y, stats, C, gamma, dgamma, dbeta, accumulate)
@@ -396,16 +381,15 @@ def bn_bwd(g, gvec, y, stats, C, gamma, dgamma, dbeta, accumulate, dbias, coef=N
     ldg = 0 if g is None else g.shape[-1]
     dy = torch.empty_like(y)
     bpart = torch.empty(nparts, CP, device=dev, dtype=torch.float32) if dbias is not None else None
-    rc = L.wm_bn_bwd_apply(_p(g), ldg, _p(gvec), _p(y), CP, _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(coef), _p(dy), CP, _p(bpart),
-                           B, hw, CP, dtype_id(y), _stream())
-    _lib.check(rc, "wm_bn_bwd_apply")
+    L.wm_bn_bwd_apply(_p(g), ldg, _p(gvec), _p(y), CP, _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(coef), _p(dy), CP, _p(bpart),
+                      B, hw, CP, dtype_id(y), _stream())
     if dbias is not None:
         colsum(bpart, dbias.numel(), CP, dbias, accumulate)
     return dy
 
 
 def conv3x3_wgrad_bnfused_supported(CinX, CoutY, dtype):
-    return bool(_lib.lib().wm_conv3x3_wgrad_bnfused_supported(CinX, CoutY, dt_id(dtype)))
+    return bool(_lib.checked().wm_conv3x3_wgrad_bnfused_supported(CinX, CoutY, dt_id(dtype)))
 
 
 def conv3x3_wgrad_bnfused(x, g, y, stats, coef, dw, accumulate):
@@ -413,18 +397,17 @@ def conv3x3_wgrad_bnfused(x, g, y, stats, coef, dw, accumulate):
     (g, y, stats [4,CP] contiguous, coef [3,CP]) while the tile is staged and never written to memory."""
     B, H, W, ldx = x.shape
     CoutY = y.shape[-1]
-    L = _lib.lib()
+    L = _lib.checked()
     nbytes = L.wm_conv3x3_wgrad_ws_bytes(B, H, W, ldx, CoutY)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
     Cout, Cin = dw.shape[0], dw.shape[1]
     assert dw.is_contiguous() and stats.is_contiguous() and coef.is_contiguous()
-    rc = L.wm_conv3x3_wgrad_bnfused(_p(x), ldx, ldx, _p(g), g.shape[-1], _p(y), CoutY, CoutY, _p(stats), _p(coef), _p(ws), _p(dw),
-                                    1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x), _stream())
-    _lib.check(rc, "wm_conv3x3_wgrad_bnfused")
+    L.wm_conv3x3_wgrad_bnfused(_p(x), ldx, ldx, _p(g), g.shape[-1], _p(y), CoutY, CoutY, _p(stats), _p(coef), _p(ws), _p(dw),
+                               1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x), _stream())
 
 
 def conv3x3_gvfused_supported(CinX, CoutY, dtype):
-    return bool(_lib.lib().wm_conv3x3_gvfused_supported(CinX, CoutY, dt_id(dtype)))
+    return bool(_lib.checked().wm_conv3x3_gvfused_supported(CinX, CoutY, dt_id(dtype)))
 
 
 def conv3x3_wgrad_gvfused(x, in_scale, in_shift, gvec, y, stats, coef, dw, accumulate, fin=None):
@@ -432,16 +415,15 @@ def conv3x3_wgrad_gvfused(x, in_scale, in_shift, gvec, y, stats, coef, dw, accum
     (gvec [B,CP], y, stats [4,CP] contiguous, coef [3,CP]) while the tile is staged."""
     B, H, W, ldx = x.shape
     CoutY = y.shape[-1]
-    L = _lib.lib()
+    L = _lib.checked()
     nbytes = L.wm_conv3x3_wgrad_ws_bytes(B, H, W, ldx, CoutY)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
     Cout, Cin = dw.shape[0], dw.shape[1]
     assert dw.is_contiguous() and stats.is_contiguous() and coef.is_contiguous() and gvec.is_contiguous() and gvec.shape[-1] == CoutY
     fst, fcoef = _fin_rider(fin)
-    rc = L.wm_conv3x3_wgrad_gvfused_fin(_p(x), ldx, ldx, _p(in_scale), _p(in_shift), _p(gvec), _p(y), CoutY, CoutY, _p(stats), _p(coef), _p(ws),
-                                        _p(dw), 1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x),
-                                        ctypes.byref(fst) if fst is not None else None, _stream())
-    _lib.check(rc, "wm_conv3x3_wgrad_gvfused")
+    L.wm_conv3x3_wgrad_gvfused_fin(_p(x), ldx, ldx, _p(in_scale), _p(in_shift), _p(gvec), _p(y), CoutY, CoutY, _p(stats), _p(coef), _p(ws),
+                                   _p(dw), 1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x),
+                                   ctypes.byref(fst) if fst is not None else None, _stream())
     return fcoef
 
 
@@ -451,9 +433,8 @@ def conv3x3_dgrad_gvfused(y, wpt, gvec, stats, coef):
     CinP = wpt.shape[1]
     assert wpt.shape[2] == CoutY and stats.is_contiguous() and coef.is_contiguous() and gvec.is_contiguous()
     dx = torch.empty(B, H, W, CinP, device=y.device, dtype=y.dtype)
-    rc = _lib.lib().wm_conv3x3_dgrad_gvfused(_p(y), CoutY, CoutY, _p(wpt), _p(gvec), _p(stats), _p(coef), _p(dx), B, H, W, CinP, dtype_id(y),
-                                             _stream())
-    _lib.check(rc, "wm_conv3x3_dgrad_gvfused")
+    _lib.checked().wm_conv3x3_dgrad_gvfused(_p(y), CoutY, CoutY, _p(wpt), _p(gvec), _p(stats), _p(coef), _p(dx), B, H, W, CinP, dtype_id(y),
+                                            _stream())
     return dx
 
 
@@ -465,7 +446,7 @@ def _premasked(dx):
 
 
 def conv3x3_dgrad_bwdstats_supported(CoutY, CinP, dtype):
-    return bool(_lib.lib().wm_conv3x3_dgrad_bwdstats_supported(CoutY, CinP, dt_id(dtype)))
+    return bool(_lib.checked().wm_conv3x3_dgrad_bwdstats_supported(CoutY, CinP, dt_id(dtype)))
 
 
 def conv3x3_dgrad_bwdstats(src, wpt, ry, r_scale, r_shift, gvec=None, stats=None, coef=None, reverse=False):
@@ -478,14 +459,13 @@ def conv3x3_dgrad_bwdstats(src, wpt, ry, r_scale, r_shift, gvec=None, stats=None
     assert (gvec is None) == (stats is None) == (coef is None)
     dx = torch.empty(B, H, W, CinP, device=src.device, dtype=src.dtype)
     part = torch.empty(conv3x3_nparts(B, H, W, CoutY, CinP, src.dtype), 2, CinP, device=src.device, dtype=torch.float32)
-    rc = _lib.lib().wm_conv3x3_dgrad_bwdstats(_p(src), lds, CoutY, _p(wpt), _p(gvec), _p(stats), _p(coef), _p(ry), _p(r_scale), _p(r_shift), _p(dx),
-                                              _p(part), B, H, W, CinP, dtype_id(src), _sweep(reverse), _stream())
-    _lib.check(rc, "wm_conv3x3_dgrad_bwdstats")
+    _lib.checked().wm_conv3x3_dgrad_bwdstats(_p(src), lds, CoutY, _p(wpt), _p(gvec), _p(stats), _p(coef), _p(ry), _p(r_scale), _p(r_shift), _p(dx),
+                                             _p(part), B, H, W, CinP, dtype_id(src), _sweep(reverse), _stream())
     return _premasked(dx), part
 
 
 def conv3x3_dgrad_applyfused_supported(CoutY, CinP, dtype):
-    return bool(_lib.lib().wm_conv3x3_dgrad_applyfused_supported(CoutY, CinP, dt_id(dtype)))
+    return bool(_lib.checked().wm_conv3x3_dgrad_applyfused_supported(CoutY, CinP, dt_id(dtype)))
 
 
 def conv3x3_dgrad_applyfused(g, y, stats, coef, wpt, ry=None, r_scale=None, r_shift=None, reverse=False, want_dy=True):
@@ -500,22 +480,21 @@ def conv3x3_dgrad_applyfused(g, y, stats, coef, wpt, ry=None, r_scale=None, r_sh
     dx = torch.empty(B, H, W, CinP, device=y.device, dtype=y.dtype)
     part = torch.empty(conv3x3_nparts(B, H, W, 64, 64, y.dtype), 2, 64, device=y.device, dtype=torch.float32) if ry is not None else None
     info = {"B": B, "H": H, "W": W, "feed": ry is not None, "dtype": y.dtype}
-    rc = _timed("conv3x3_dgrad_applyfused", info, lambda: _lib.lib().wm_conv3x3_dgrad_applyfused(
+    _timed("conv3x3_dgrad_applyfused", info, lambda: _lib.checked().wm_conv3x3_dgrad_applyfused(
         _p(g), _p(y), _p(stats), _p(coef), _p(wpt), _p(dy), _p(dx), _p(ry), _p(r_scale), _p(r_shift), _p(part), B, H, W, CinP, dtype_id(y),
         _sweep(reverse), _stream()))
-    _lib.check(rc, "wm_conv3x3_dgrad_applyfused")
     return dy, _premasked(dx) if ry is not None else dx, part
 
 
 def conv3x3_bwd_fused_supported(dtype, shape=None):
     """the one-kernel backward exists for this dtype (and, given y's shape [B,H,W,64], the tensor fits its 32-bit offsets)"""
     if shape is None:
-        return bool(_lib.lib().wm_conv3x3_bwd_fused_supported(dt_id(dtype)))
-    return bool(_lib.lib().wm_conv3x3_bwd_fused_supported_shape(shape[0], shape[1], shape[2], dt_id(dtype)))
+        return bool(_lib.checked().wm_conv3x3_bwd_fused_supported(dt_id(dtype)))
+    return bool(_lib.checked().wm_conv3x3_bwd_fused_supported_shape(shape[0], shape[1], shape[2], dt_id(dtype)))
 
 
 def conv3x3_bwd_fused_gvec_max_batch():
-    return int(_lib.lib().wm_conv3x3_bwd_fused_gvec_max_batch())
+    return int(_lib.checked().wm_conv3x3_bwd_fused_gvec_max_batch())
 
 
 def conv3x3_bwd_fused(g, y, stats, coef, wpt, xr, in_scale, in_shift, dw, accumulate, reverse=False, fin=None, premasked=False, gvec=None):
@@ -529,7 +508,7 @@ def conv3x3_bwd_fused(g, y, stats, coef, wpt, xr, in_scale, in_shift, dw, accumu
     assert C == 64 and xr.shape == y.shape and y.is_contiguous() and xr.is_contiguous()
     assert (g.shape == y.shape and g.is_contiguous()) if g is not None else (tuple(gvec.shape) == (B, 64) and gvec.is_contiguous() and gvec.dtype == torch.float32)
     assert tuple(wpt.shape) == (9, 64, 64) and stats.is_contiguous() and coef.is_contiguous() and dw.is_contiguous()
-    L = _lib.lib()
+    L = _lib.checked()
     nwg = L.wm_conv3x3_bwd_fused_nwg(B, H, W)
     dx = torch.empty_like(y)
     part = torch.empty(nwg, 2, 64, device=y.device, dtype=torch.float32)
@@ -537,19 +516,17 @@ def conv3x3_bwd_fused(g, y, stats, coef, wpt, xr, in_scale, in_shift, dw, accumu
     ws = torch.empty(nwg * 9 * 64 * 64, device=y.device, dtype=torch.float32)
     Cout, Cin = dw.shape[0], dw.shape[1]
     info = {"B": B, "H": H, "W": W, "dtype": y.dtype, "gvec": gvec is not None}
-    rc = _timed("conv3x3_bwd_fused", info, lambda: L.wm_conv3x3_bwd_fused(
+    _timed("conv3x3_bwd_fused", info, lambda: L.wm_conv3x3_bwd_fused(
         _p(g), _p(gvec), _p(y), _p(stats), _p(coef), _p(wpt), _p(xr), _p(in_scale), _p(in_shift), _p(dx), _p(part), _p(ws), B, H, W, dtype_id(y),
         1 if premasked else 0, _sweep(reverse), _stream()))
-    _lib.check(rc, "wm_conv3x3_bwd_fused")
-    rc = L.wm_conv3x3_bwd_fused_reduce(_p(ws), _p(dw), 1 if accumulate else 0, B, H, W, Cin, Cout, ctypes.byref(fst) if fst is not None else None,
-                                       _stream())
-    _lib.check(rc, "wm_conv3x3_bwd_fused_reduce")
+    L.wm_conv3x3_bwd_fused_reduce(_p(ws), _p(dw), 1 if accumulate else 0, B, H, W, Cin, Cout, ctypes.byref(fst) if fst is not None else None,
+                                  _stream())
     return _premasked(dx), part, fcoef
 
 
 def conv3x3_bwd_fused16_supported(shape, dtype):
     """the one-kernel backward of an image-fed first layer exists for y's shape [B,H,W,64] (whole 8x16 tiles) and dtype"""
-    return bool(_lib.lib().wm_conv3x3_bwd_fused16_supported(shape[0], shape[1], shape[2], dt_id(dtype)))
+    return bool(_lib.checked().wm_conv3x3_bwd_fused16_supported(shape[0], shape[1], shape[2], dt_id(dtype)))
 
 
 def conv3x3_bwd_fused16(g, y, stats, coef, wpt, x, dw, accumulate, reverse=False, premasked=False):
@@ -558,15 +535,14 @@ def conv3x3_bwd_fused16(g, y, stats, coef, wpt, x, dw, accumulate, reverse=False
     B, H, W, C = y.shape
     assert C == 64 and g.shape == y.shape and g.is_contiguous() and y.is_contiguous() and tuple(x.shape) == (B, H, W, 16) and x.is_contiguous()
     assert tuple(wpt.shape) == (9, 16, 64) and stats.is_contiguous() and coef.is_contiguous() and dw.is_contiguous() and dw.shape[0] <= 64 and dw.shape[1] <= 16
-    L = _lib.lib()
+    L = _lib.checked()
     nwg = L.wm_conv3x3_bwd_fused16_nwg(B, H, W)
     dx = torch.empty(B, H, W, 16, device=y.device, dtype=y.dtype)
     ws = torch.empty(nwg * 9 * 16 * 64, device=y.device, dtype=torch.float32)
     info = {"B": B, "H": H, "W": W, "dtype": y.dtype}
-    rc = _timed("conv3x3_bwd_fused16", info, lambda: L.wm_conv3x3_bwd_fused16(
+    _timed("conv3x3_bwd_fused16", info, lambda: L.wm_conv3x3_bwd_fused16(
         _p(g), _p(y), _p(stats), _p(coef), _p(wpt), _p(x), _p(dx), _p(ws), _p(dw), 1 if accumulate else 0, B, H, W, dw.shape[1], dw.shape[0],
         dtype_id(y), 1 if premasked else 0, _sweep(reverse), _stream()))
-    _lib.check(rc, "wm_conv3x3_bwd_fused16")
     return dx
 
 
@@ -576,8 +552,7 @@ def linear_head_fwd(pooled, w, bias, I):
     B, ldp = pooled.shape
     O = w.shape[0]
     out = torch.empty(B, O, device=pooled.device, dtype=torch.float32)
-    rc = _lib.lib().wm_linear_head_fwd(_p(pooled), ldp, _p(w), _p(bias), _p(out), B, I, O, _stream())
-    _lib.check(rc, "wm_linear_head_fwd")
+    _lib.checked().wm_linear_head_fwd(_p(pooled), ldp, _p(w), _p(bias), _p(out), B, I, O, _stream())
     return out
 
 
@@ -588,14 +563,13 @@ def linear_head_bwd(pooled, w, g_out, dw, db, accumulate, CP, inv_hw):
     O, I = w.shape
     g = g_out.contiguous().float()
     gvec = torch.empty(B, CP, device=pooled.device, dtype=torch.float32)
-    rc = _lib.lib().wm_linear_head_bwd(_p(pooled), ldp, _p(w), _p(g), _p(dw), _p(db), 1 if accumulate else 0, _p(gvec), CP, inv_hw, B, I, O,
-                                       _stream())
-    _lib.check(rc, "wm_linear_head_bwd")
+    _lib.checked().wm_linear_head_bwd(_p(pooled), ldp, _p(w), _p(g), _p(dw), _p(db), 1 if accumulate else 0, _p(gvec), CP, inv_hw, B, I, O,
+                                      _stream())
     return gvec
 
 
 def pooled_head_supported(B, CP, I, O):
-    return bool(_lib.lib().wm_pooled_head_supported(B, CP, I, O))
+    return bool(_lib.checked().wm_pooled_head_supported(B, CP, I, O))
 
 
 def pooled_head(out3, I, w, bias, kind, target, messages, gscale, gscale_dev, dw, db, accumulate, inv_hw, C, count, gamma, stats, dgamma, dbeta):
@@ -611,10 +585,9 @@ def pooled_head(out3, I, w, bias, kind, target, messages, gscale, gscale_dev, dw
     gvec = torch.empty(B, CP, device=dev, dtype=torch.float32)
     coef = torch.empty(3, CP, device=dev, dtype=torch.float32)
     msg = messages.contiguous().float() if messages is not None else None
-    rc = _lib.lib().wm_pooled_head(_p(out3), B, CP, I, O, _p(w), _p(bias), kind, float(target), _p(msg), float(gscale), _p(gscale_dev), _p(logits),
-                                   _p(loss), _p(dw), _p(db), 1 if accumulate else 0, _p(gvec), inv_hw, C, float(count), _p(gamma), _p(stats[2]),
-                                   _p(stats[3]), _p(dgamma), _p(dbeta), _p(coef), _stream())
-    _lib.check(rc, "wm_pooled_head")
+    _lib.checked().wm_pooled_head(_p(out3), B, CP, I, O, _p(w), _p(bias), kind, float(target), _p(msg), float(gscale), _p(gscale_dev), _p(logits),
+                                  _p(loss), _p(dw), _p(db), 1 if accumulate else 0, _p(gvec), inv_hw, C, float(count), _p(gamma), _p(stats[2]),
+                                  _p(stats[3]), _p(dgamma), _p(dbeta), _p(coef), _stream())
     return logits, loss, gvec, coef
 
 
@@ -625,8 +598,7 @@ def bce_logits(logits, target, gscale=1.0, want_grad=True, gscale_dev=None):
     x = logits.contiguous().float()
     loss = torch.empty(1, device=x.device, dtype=torch.float32)
     grad = torch.empty_like(x) if want_grad else None
-    rc = _lib.lib().wm_bce_logits(_p(x), float(target), x.numel(), float(gscale), _p(gscale_dev), _p(loss), _p(grad), _stream())
-    _lib.check(rc, "wm_bce_logits")
+    _lib.checked().wm_bce_logits(_p(x), float(target), x.numel(), float(gscale), _p(gscale_dev), _p(loss), _p(grad), _stream())
     return loss, grad
 
 
@@ -636,23 +608,20 @@ def message_loss(decoded, messages, gscale, want_grad=True, gscale_dev=None):
     d = decoded.contiguous().float(); m = messages.contiguous().float()
     out = torch.empty(2, device=d.device, dtype=torch.float32)
     grad = torch.empty_like(d) if want_grad else None
-    rc = _lib.lib().wm_message_loss(_p(d), _p(m), d.numel(), float(gscale), _p(gscale_dev), _p(out), _p(grad), _stream())
-    _lib.check(rc, "wm_message_loss")
+    _lib.checked().wm_message_loss(_p(d), _p(m), d.numel(), float(gscale), _p(gscale_dev), _p(out), _p(grad), _stream())
     return out, grad
 
 
 def hidden_metrics(enc_partials, n_img, msg2, adv, d_cover, d_enc, w_adv, w_enc, w_dec):
     """[7] f32: loss, encoder mse, decoder mse, bitwise error, adversarial bce, D(cover) bce, D(encoded) bce (one launch)"""
     out = torch.empty(7, device=enc_partials.device, dtype=torch.float32)
-    rc = _lib.lib().wm_hidden_metrics(_p(enc_partials), enc_partials.numel(), float(n_img), _p(msg2), _p(adv), _p(d_cover), _p(d_enc), w_adv, w_enc,
-                                      w_dec, _p(out), _stream())
-    _lib.check(rc, "wm_hidden_metrics")
+    _lib.checked().wm_hidden_metrics(_p(enc_partials), enc_partials.numel(), float(n_img), _p(msg2), _p(adv), _p(d_cover), _p(d_enc), w_adv, w_enc,
+                                     w_dec, _p(out), _stream())
     return out
 
 
 def colsum(partials, C, ldp, out, accumulate):
-    rc = _lib.lib().wm_colsum_finalize(_p(partials), partials.shape[0], C, ldp, _p(out), 1 if accumulate else 0, _stream())
-    _lib.check(rc, "wm_colsum_finalize")
+    _lib.checked().wm_colsum_finalize(_p(partials), partials.shape[0], C, ldp, _p(out), 1 if accumulate else 0, _stream())
 
 
 def conv3x3_wgrad(x, CinX, in_scale, in_shift, dy, dw, accumulate, perm_dev=None, reverse=False, fin=None):
@@ -660,19 +629,18 @@ def conv3x3_wgrad(x, CinX, in_scale, in_shift, dy, dw, accumulate, perm_dev=None
     fst, fcoef = _fin_rider(fin)
     B, H, W, ldx = x.shape
     CoutY = dy.shape[-1]
-    L = _lib.lib()
+    L = _lib.checked()
     nbytes = L.wm_conv3x3_wgrad_ws_bytes(B, H, W, CinX, CoutY)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
     Cout, Cin = dw.shape[0], dw.shape[1]
     assert dw.is_contiguous()
-    rc = L.wm_conv3x3_wgrad_fin(_p(x), ldx, CinX, _p(in_scale), _p(in_shift), _p(dy), CoutY, CoutY, _p(ws), _p(dw), 1 if accumulate else 0, B, H, W,
-                                Cin, Cout, _p(perm_dev), dtype_id(x), ctypes.byref(fst) if fst is not None else None, _sweep(reverse), _stream())
-    _lib.check(rc, "wm_conv3x3_wgrad")
+    L.wm_conv3x3_wgrad_fin(_p(x), ldx, CinX, _p(in_scale), _p(in_shift), _p(dy), CoutY, CoutY, _p(ws), _p(dw), 1 if accumulate else 0, B, H, W,
+                           Cin, Cout, _p(perm_dev), dtype_id(x), ctypes.byref(fst) if fst is not None else None, _sweep(reverse), _stream())
     return fcoef
 
 
 def conv3x3_fwd_elu_supported(Cin, CoutP, dtype):
-    return bool(_lib.lib().wm_conv3x3_fwd_elu_supported(Cin, CoutP, dt_id(dtype)))
+    return bool(_lib.checked().wm_conv3x3_fwd_elu_supported(Cin, CoutP, dt_id(dtype)))
 
 
 def conv3x3_fwd_elu(x, wp, bias):
@@ -682,14 +650,13 @@ def conv3x3_fwd_elu(x, wp, bias):
     Cin = wp.shape[2]
     assert wp.shape[1] == 64 and Cin <= ldx
     out = torch.empty(B, H, W, 64, device=x.device, dtype=x.dtype)
-    rc = _lib.lib().wm_conv3x3_fwd_elu(_p(x), ldx, _p(wp), _p(bias), 0 if bias is None else bias.numel(), _p(out), B, H, W, Cin, dtype_id(x), 0,
-                                       _stream())
-    _lib.check(rc, "wm_conv3x3_fwd_elu")
+    _lib.checked().wm_conv3x3_fwd_elu(_p(x), ldx, _p(wp), _p(bias), 0 if bias is None else bias.numel(), _p(out), B, H, W, Cin, dtype_id(x), 0,
+                                      _stream())
     return out
 
 
 def conv3x3_dgrad_elufused_supported(CinP, dtype):
-    return bool(_lib.lib().wm_conv3x3_dgrad_elufused_supported(CinP, dt_id(dtype)))
+    return bool(_lib.checked().wm_conv3x3_dgrad_elufused_supported(CinP, dt_id(dtype)))
 
 
 def conv3x3_dgrad_elufused(g, out, wpt, want_gz=True, dx_stride=None):
@@ -701,12 +668,11 @@ def conv3x3_dgrad_elufused(g, out, wpt, want_gz=True, dx_stride=None):
     CinP = wpt.shape[1] if dx_stride is None else dx_stride
     assert C == 64 and out.shape == g.shape and out.dtype == g.dtype and g.is_contiguous() and out.is_contiguous() and wpt.shape[2] == 64
     assert CinP == wpt.shape[1] or (CinP == 16 and wpt.shape[1] == 32)
-    L = _lib.lib()
+    L = _lib.checked()
     dx = torch.empty(B, H, W, CinP, device=g.device, dtype=g.dtype)
     gz = torch.empty_like(g) if want_gz else None
     part = torch.empty(L.wm_conv3x3_dgrad_elufused_nparts(B, H, W), 64, device=g.device, dtype=torch.float32)
-    rc = L.wm_conv3x3_dgrad_elufused(_p(g), _p(out), _p(wpt), _p(dx), _p(gz), _p(part), B, H, W, CinP, dtype_id(g), 0, _stream())
-    _lib.check(rc, "wm_conv3x3_dgrad_elufused")
+    L.wm_conv3x3_dgrad_elufused(_p(g), _p(out), _p(wpt), _p(dx), _p(gz), _p(part), B, H, W, CinP, dtype_id(g), 0, _stream())
     return dx, gz, part
 
 
@@ -714,13 +680,12 @@ def conv3x3_wgrad_bias(x, gz, dw, accumulate, bias_partials, db, db_accumulate):
     """dw [Cout,Cin,3,3] (+)= the weight gradient from (x, gz); db [Cout] (+)= the column sums of bias_partials, in the same reduction launch"""
     B, H, W, ldx = x.shape
     CoutY = gz.shape[-1]
-    L = _lib.lib()
+    L = _lib.checked()
     ws = torch.empty(L.wm_conv3x3_wgrad_ws_bytes(B, H, W, ldx, CoutY) // 4, device=x.device, dtype=torch.float32)
     Cout, Cin = dw.shape[0], dw.shape[1]
     assert dw.is_contiguous() and db.is_contiguous() and db.numel() == Cout and bias_partials.is_contiguous() and bias_partials.shape[1] == CoutY
-    rc = L.wm_conv3x3_wgrad_bias(_p(x), ldx, ldx, _p(gz), CoutY, CoutY, _p(ws), _p(dw), 1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x),
-                                 _p(bias_partials), bias_partials.shape[0], _p(db), 1 if db_accumulate else 0, _stream())
-    _lib.check(rc, "wm_conv3x3_wgrad_bias")
+    L.wm_conv3x3_wgrad_bias(_p(x), ldx, ldx, _p(gz), CoutY, CoutY, _p(ws), _p(dw), 1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x),
+                            _p(bias_partials), bias_partials.shape[0], _p(db), 1 if db_accumulate else 0, _stream())
 
 
 # ----------------------------------------------------------------------------- heads
@@ -728,12 +693,11 @@ def bnrelu_avgpool_stats(y, scale, shift):
     """global average pool of relu(scale*y+shift) plus, per (sample, channel), the active-pixel count N+ and the sum S+ of y over
     the active pixels.  Returns (pooled [B,CP], (N+ [B,CP], S+ [B,CP]))."""
     B, H, W, CP = y.shape
-    L = _lib.lib()
+    L = _lib.checked()
     S = L.wm_avgpool_slices(H * W)
     ws = torch.empty(B * S * 3 * CP, device=y.device, dtype=torch.float32)
     out3 = torch.empty(3, B, CP, device=y.device, dtype=torch.float32)
-    rc = L.wm_bnrelu_avgpool_stats(_p(y), CP, _p(scale), _p(shift), _p(out3), _p(ws), B, H * W, CP, dtype_id(y), _stream())
-    _lib.check(rc, "wm_bnrelu_avgpool_stats")
+    L.wm_bnrelu_avgpool_stats(_p(y), CP, _p(scale), _p(shift), _p(out3), _p(ws), B, H * W, CP, dtype_id(y), _stream())
     return out3[0], (out3[1], out3[2])
 
 
@@ -743,8 +707,7 @@ def pooled_bwd_rows(gvec, pool_stats):
     npos, ysum = pool_stats
     assert gvec.is_contiguous() and npos.is_contiguous() and ysum.is_contiguous() and npos.shape == gvec.shape
     rows = torch.empty(B, 2, CP, device=gvec.device, dtype=torch.float32)
-    rc = _lib.lib().wm_pooled_bn_bwd_rows(_p(gvec), _p(npos), _p(ysum), B, CP, _p(rows), _stream())
-    _lib.check(rc, "wm_pooled_bn_bwd_rows")
+    _lib.checked().wm_pooled_bn_bwd_rows(_p(gvec), _p(npos), _p(ysum), B, CP, _p(rows), _stream())
     return rows
 
 
@@ -754,20 +717,18 @@ def bn_bwd_coef_pooled(gvec, pool_stats, y, stats, C, gamma, dgamma, dbeta, accu
     npos, ysum = pool_stats
     assert gvec.is_contiguous() and npos.is_contiguous() and ysum.is_contiguous() and tuple(gvec.shape) == (B, CP) == tuple(npos.shape)
     coef = torch.empty(3, CP, device=y.device, dtype=torch.float32)
-    rc = _lib.lib().wm_bn_bwd_finalize_pooled(_p(gvec), _p(npos), _p(ysum), B, C, CP, B * H * W, _p(gamma), _p(stats[2]), _p(stats[3]), _p(dgamma),
-                                              _p(dbeta), 1 if accumulate else 0, _p(coef), _stream())
-    _lib.check(rc, "wm_bn_bwd_finalize_pooled")
+    _lib.checked().wm_bn_bwd_finalize_pooled(_p(gvec), _p(npos), _p(ysum), B, C, CP, B * H * W, _p(gamma), _p(stats[2]), _p(stats[3]), _p(dgamma),
+                                             _p(dbeta), 1 if accumulate else 0, _p(coef), _stream())
     return coef
 
 
 def bnrelu_avgpool(y, scale, shift):
     B, H, W, CP = y.shape
-    L = _lib.lib()
+    L = _lib.checked()
     S = L.wm_avgpool_slices(H * W)
     ws = torch.empty(B * S * CP, device=y.device, dtype=torch.float32)
     out = torch.empty(B, CP, device=y.device, dtype=torch.float32)
-    rc = L.wm_bnrelu_avgpool(_p(y), CP, _p(scale), _p(shift), _p(out), _p(ws), B, H * W, CP, dtype_id(y), _stream())
-    _lib.check(rc, "wm_bnrelu_avgpool")
+    L.wm_bnrelu_avgpool(_p(y), CP, _p(scale), _p(shift), _p(out), _p(ws), B, H * W, CP, dtype_id(y), _stream())
     return out
 
 
@@ -778,9 +739,8 @@ def conv1x1_head_fwd(y, scale, shift, w, bias, act=0, want_act16=False):
     Cout = w.shape[0]
     out = torch.empty(B, Cout, H, W, device=y.device, dtype=torch.float32)
     a16 = torch.empty(B, H, W, 16, device=y.device, dtype=y.dtype) if want_act16 else None
-    rc = _lib.lib().wm_conv1x1_head_fwd_act(_p(y), Cin, _p(scale), _p(shift), _p(w), _p(bias), _p(out), _p(a16), B, H * W, Cin, Cout, act,
-                                            dtype_id(y), _stream())
-    _lib.check(rc, "wm_conv1x1_head_fwd")
+    _lib.checked().wm_conv1x1_head_fwd_act(_p(y), Cin, _p(scale), _p(shift), _p(w), _p(bias), _p(out), _p(a16), B, H * W, Cin, Cout, act,
+                                           dtype_id(y), _stream())
     return (out, a16) if want_act16 else out
 
 
@@ -789,15 +749,14 @@ def conv1x1_head_bwd(y, scale, shift, w, gout, dw, dbias, accumulate, want_bn_pa
     ConvBNRelu that produced y, for bn_bwd_coef_raw: that layer then needs no reduce pass over (g, y))"""
     B, H, W, Cin = y.shape
     Cout = w.shape[0]
-    L = _lib.lib()
+    L = _lib.checked()
     nparts = L.wm_conv1x1_head_nparts(B * H * W)
     part = torch.empty(nparts, Cout * (Cin + 1), device=y.device, dtype=torch.float32)
     bnp = torch.empty(nparts, 2, Cin, device=y.device, dtype=torch.float32) if want_bn_partials and scale is not None else None
     g = torch.empty_like(y)
     gout = gout.contiguous()
-    rc = L.wm_conv1x1_head_bwd(_p(y), Cin, _p(scale), _p(shift), _p(w), _p(gout), _p(g), Cin, _p(part), _p(bnp), B, H * W, Cin, Cout, dtype_id(y),
-                               _stream())
-    _lib.check(rc, "wm_conv1x1_head_bwd")
+    L.wm_conv1x1_head_bwd(_p(y), Cin, _p(scale), _p(shift), _p(w), _p(gout), _p(g), Cin, _p(part), _p(bnp), B, H * W, Cin, Cout, dtype_id(y),
+                          _stream())
     ldp = Cout * (Cin + 1)
     colsum(part, Cout * Cin, ldp, dw, accumulate)
     # the first call folded the rows in place to <= 64 (wm_colsum_finalize treats partials as scratch)
@@ -827,8 +786,7 @@ def head2_fwd(a, na, b, nb, w, bias, act=0):
     Cout = _head2_args("head2_fwd", a, na, b, nb, w, bias)
     B, H, W, lda = a.shape
     out = torch.empty(B, Cout, H, W, device=a.device, dtype=torch.float32)
-    rc = _lib.lib().wm_head2_fwd(_p(a), lda, na, _p(b), b.shape[3], nb, _p(w), _p(bias), _p(out), B, H * W, Cout, int(act), dtype_id(a), _stream())
-    _lib.check(rc, "wm_head2_fwd")
+    _lib.checked().wm_head2_fwd(_p(a), lda, na, _p(b), b.shape[3], nb, _p(w), _p(bias), _p(out), B, H * W, Cout, int(act), dtype_id(a), _stream())
     return out
 
 
@@ -849,17 +807,15 @@ def head2_bwd(a, na, b, nb, w, gout, out=None, dw_acc=None, db_acc=None):
         raise ValueError("head2_bwd: accumulation targets do not match the gradients")
     gout = gout.contiguous()
     out = out.contiguous() if out is not None else None
-    L = _lib.lib()
+    L = _lib.checked()
     nparts = L.wm_head2_nparts(B * H * W)
     part = torch.empty(nparts, Cout * (na + nb + 1), device=a.device, dtype=torch.float64)
     ga, gb = torch.empty_like(a), torch.empty_like(b)
-    rc = L.wm_head2_bwd(_p(a), lda, na, _p(b), b.shape[3], nb, _p(w), _p(gout), _p(out), 0 if out is None else 1, _p(ga), lda, _p(gb), b.shape[3],
-                        _p(part), B, H * W, Cout, dtype_id(a), _stream())
-    _lib.check(rc, "wm_head2_bwd")
+    L.wm_head2_bwd(_p(a), lda, na, _p(b), b.shape[3], nb, _p(w), _p(gout), _p(out), 0 if out is None else 1, _p(ga), lda, _p(gb), b.shape[3],
+                   _p(part), B, H * W, Cout, dtype_id(a), _stream())
     dw = dw_acc if acc else torch.empty(Cout, na + nb, device=a.device, dtype=torch.float32)
     db = db_acc if acc else torch.empty(Cout, device=a.device, dtype=torch.float32)
-    rc = L.wm_head2_finalize(_p(part), nparts, Cout, na + nb, _p(dw), _p(db), 1 if acc else 0, _stream())
-    _lib.check(rc, "wm_head2_finalize")
+    L.wm_head2_finalize(_p(part), nparts, Cout, na + nb, _p(dw), _p(db), 1 if acc else 0, _stream())
     return ga, gb, dw, db
 
 
@@ -871,8 +827,7 @@ def mse_fwd_bwd(a, b, gscale, want_grad=True, gscale_dev=None):
     nparts = max(1, min(1024, (n + 4095) // 4096))
     part = torch.empty(nparts, device=a.device, dtype=torch.float32)
     grad = torch.empty_like(a) if want_grad else None
-    rc = _lib.lib().wm_mse_fwd_bwd(_p(a), _p(b), _p(grad), gscale, _p(gscale_dev), _p(part), nparts, n, _stream())
-    _lib.check(rc, "wm_mse_fwd_bwd")
+    _lib.checked().wm_mse_fwd_bwd(_p(a), _p(b), _p(grad), gscale, _p(gscale_dev), _p(part), nparts, n, _stream())
     return part, grad
 
 
@@ -887,24 +842,21 @@ def image_grad_mse(g, a, b, gscale, C=3, C_off=0, gscale_dev=None):
     nparts = max(1, min(1024, (n + 4095) // 4096))
     out = torch.empty_like(a)
     part = torch.empty(nparts, device=a.device, dtype=torch.float32)
-    rc = _lib.lib().wm_image_grad_mse(_p(g), ld, C_off, _p(a), _p(b), _p(out), gscale, _p(gscale_dev), _p(part), nparts, B, C, H, W, dtype_id(g),
-                                      _stream())
-    _lib.check(rc, "wm_image_grad_mse")
+    _lib.checked().wm_image_grad_mse(_p(g), ld, C_off, _p(a), _p(b), _p(out), gscale, _p(gscale_dev), _p(part), nparts, B, C, H, W, dtype_id(g),
+                                     _stream())
     return out, part
 
 
 def axpy_(a, b, s=1.0):
     assert a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
-    rc = _lib.lib().wm_axpy(_p(a), _p(b), s, a.numel(), _stream())
-    _lib.check(rc, "wm_axpy")
+    _lib.checked().wm_axpy(_p(a), _p(b), s, a.numel(), _stream())
     _wrote(a)
     return a
 
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, decoupled=False, grad_scale=1.0):
-    rc = _lib.lib().wm_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, 1 if decoupled else 0, step, grad_scale,
-                                 _stream())
-    _lib.check(rc, "wm_adam_step")
+    _lib.checked().wm_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, 1 if decoupled else 0, step, grad_scale,
+                                _stream())
     _wrote(p, m, v)
 
 
@@ -915,8 +867,7 @@ def adam_hyper(lr, beta1, beta2, step, eps, weight_decay):
     """the WM_ADAM_HYPER floats a replayed step reads (host arithmetic, no launch): (lr / (1 - beta1^step), sqrt(1 - beta2^step), lr, beta1,
     beta2, eps, weight_decay, 0) -- the first two exactly as wm_adam_step derives them, the rest rounded to f32 as its arguments are"""
     out = (ctypes.c_float * ADAM_HYPER)()
-    rc = _lib.lib().wm_adam_hyper(lr, beta1, beta2, eps, weight_decay, step, out)
-    _lib.check(rc, "wm_adam_hyper")
+    _lib.checked().wm_adam_hyper(lr, beta1, beta2, eps, weight_decay, step, out)
     return tuple(float(x) for x in out)
 
 
@@ -924,8 +875,7 @@ def adam_step_dev(p, g, m, v, hyper_dev, decoupled=False, grad_scale=1.0):
     """adam_step with every number but `decoupled` read from the device tensor hyper_dev [ADAM_HYPER] f32 (adam_hyper's block): what a
     captured step launches -- the caller refreshes hyper_dev before each replay"""
     assert hyper_dev.is_cuda and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= ADAM_HYPER and hyper_dev.is_contiguous()
-    rc = _lib.lib().wm_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), 1 if decoupled else 0, _p(hyper_dev), grad_scale, _stream())
-    _lib.check(rc, "wm_adam_step_dev")
+    _lib.checked().wm_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), 1 if decoupled else 0, _p(hyper_dev), grad_scale, _stream())
     _wrote(p, m, v)
 
 
@@ -954,12 +904,10 @@ class AmpState:
         parts = [nonfinite(g) for g in grads]
         arr = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
         ns = (ctypes.c_int * len(parts))(*[p.numel() for p in parts])
-        rc = _lib.lib().wm_amp_found_inf(arr, ns, len(parts), _p(self.state), k, _stream())
-        _lib.check(rc, "wm_amp_found_inf")
+        _lib.checked().wm_amp_found_inf(arr, ns, len(parts), _p(self.state), k, _stream())
 
     def update(self):
-        rc = _lib.lib().wm_amp_update(_p(self.state), max(1, self.nopt), _stream())
-        _lib.check(rc, "wm_amp_update")
+        _lib.checked().wm_amp_update(_p(self.state), max(1, self.nopt), _stream())
 
     def get_scale(self):
         return float(self.state[0].item())
@@ -990,9 +938,8 @@ def adam_step_amp(p, g, m, v, lr, beta1, beta2, eps, weight_decay, amp, k, decou
     replace the arguments at each replay"""
     if hyper_dev is not None:
         assert hyper_dev.is_cuda and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= ADAM_HYPER and hyper_dev.is_contiguous()
-    rc = _lib.lib().wm_adam_step_amp(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, 1 if decoupled else 0, grad_scale,
-                                     _p(amp.state), k, _p(hyper_dev), _stream())
-    _lib.check(rc, "wm_adam_step_amp")
+    _lib.checked().wm_adam_step_amp(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, 1 if decoupled else 0, grad_scale,
+                                    _p(amp.state), k, _p(hyper_dev), _stream())
     _wrote(p, m, v)
 
 
@@ -1000,8 +947,7 @@ def sumsq(x):
     n = x.numel()
     nparts = max(1, min(1024, (n + 4095) // 4096))
     part = torch.empty(nparts, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_sumsq(_p(x), n, _p(part), nparts, _stream())
-    _lib.check(rc, "wm_sumsq")
+    _lib.checked().wm_sumsq(_p(x), n, _p(part), nparts, _stream())
     return part
 
 
@@ -1010,8 +956,7 @@ def nonfinite(x):
     n = x.numel()
     nparts = max(1, min(1024, (n + 4095) // 4096))
     part = torch.empty(nparts, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_nonfinite(_p(x), n, _p(part), nparts, _stream())
-    _lib.check(rc, "wm_nonfinite")
+    _lib.checked().wm_nonfinite(_p(x), n, _p(part), nparts, _stream())
     return part
 
 
@@ -1021,8 +966,7 @@ def clamp_quant(x):
     _need_cuda(x)
     x = x.contiguous().float()
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_clamp_quant_fwd(_p(x), _p(y), x.numel(), _stream())
-    _lib.check(rc, "wm_clamp_quant_fwd")
+    _lib.checked().wm_clamp_quant_fwd(_p(x), _p(y), x.numel(), _stream())
     return y
 
 
@@ -1058,8 +1002,7 @@ def mix_fwd(xs, w, quant=False):
     xs, w, N, frame = _mix_args("mix_fwd", xs, w, len(xs))
     y = torch.empty_like(xs[0])
     ptrs = (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
-    rc = _lib.lib().wm_mix_fwd(ptrs, len(xs), _p(w), _p(y), N, frame, 1 if quant else 0, _stream())
-    _lib.check(rc, "wm_mix_fwd")
+    _lib.checked().wm_mix_fwd(ptrs, len(xs), _p(w), _p(y), N, frame, 1 if quant else 0, _stream())
     return y
 
 
@@ -1077,8 +1020,7 @@ def mix_bwd(g, w, K, needs=None, out=None):
     g = ts[0]
     gxs = [(out[k] if out is not None else torch.empty_like(g)) if needs[k] else None for k in range(K)]
     ptrs = (ctypes.c_void_p * K)(*[_p(t) for t in gxs])
-    rc = _lib.lib().wm_mix_bwd(_p(g), _p(w), ptrs, K, N, frame, _stream())
-    _lib.check(rc, "wm_mix_bwd")
+    _lib.checked().wm_mix_bwd(_p(g), _p(w), ptrs, K, N, frame, _stream())
     _wrote(*outs_in)
     return gxs
 
@@ -1089,7 +1031,7 @@ def splice_fwd(enc, real=None, prev=None, mask=None, want_fwd=False):
     _need_cuda(enc)
     enc = enc.contiguous()
     B, C, H, W = enc.shape
-    L = _lib.lib()
+    L = _lib.checked()
     fwd = torch.empty_like(enc) if want_fwd else None
     tam = torch.empty_like(enc) if prev is not None else None
     part = None
@@ -1099,8 +1041,7 @@ def splice_fwd(enc, real=None, prev=None, mask=None, want_fwd=False):
     if prev is not None:
         prev = prev.contiguous(); mask = mask.contiguous()
         assert prev.shape == enc.shape and tuple(mask.shape) == (B, 1, H, W) and mask.dtype == torch.float32
-    rc = L.wm_splice_fwd(_p(enc), _p(real), _p(prev), _p(mask), _p(fwd), _p(tam), _p(part), B, C, H * W, _stream())
-    _lib.check(rc, "wm_splice_fwd")
+    L.wm_splice_fwd(_p(enc), _p(real), _p(prev), _p(mask), _p(fwd), _p(tam), _p(part), B, C, H * W, _stream())
     return fwd, tam, part
 
 
@@ -1149,13 +1090,12 @@ def copymove_fwd(enc, mask, shifts, real=None, want_fwd=False):
     sh = sh.contiguous() if sh.is_cuda else sh.to(enc.device)
     enc = enc.contiguous(); mask = mask.contiguous()
     real = real.contiguous() if real is not None else None
-    L = _lib.lib()
+    L = _lib.checked()
     fwd = torch.empty_like(enc) if want_fwd else None
     tam = torch.empty_like(enc)
     ms = torch.empty_like(mask)
     part = torch.empty(2, L.wm_splice_nparts(enc.numel()), device=enc.device, dtype=torch.float64)
-    rc = L.wm_copymove_fwd(_p(enc), _p(real), _p(mask), _p(sh), _p(fwd), _p(tam), _p(ms), _p(part), B, C, H, W, _stream())
-    _lib.check(rc, "wm_copymove_fwd")
+    L.wm_copymove_fwd(_p(enc), _p(real), _p(mask), _p(sh), _p(fwd), _p(tam), _p(ms), _p(part), B, C, H, W, _stream())
     return fwd, tam, ms, part
 
 
@@ -1165,16 +1105,14 @@ def copymove_valid(partials, count):
     if partials.dim() != 2 or partials.shape[0] != 2 or partials.dtype != torch.float64 or not partials.is_contiguous() or count <= 0:
         raise ValueError("copymove_valid: contiguous float64 partials [2, nparts] of copymove_fwd and a positive count expected")
     out = torch.empty(1, device=partials.device, dtype=torch.float32)
-    rc = _lib.lib().wm_copymove_valid(_p(partials), partials.shape[1], float(count), _p(out), _stream())
-    _lib.check(rc, "wm_copymove_valid")
+    _lib.checked().wm_copymove_valid(_p(partials), partials.shape[1], float(count), _p(out), _stream())
     return out
 
 
 def psnr_gate(partials, n, threshold=33.0, w_below=1.0, w_above=0.8):
     """[2] f32 device tensor: (PSNR, forward-loss weight) -- IRNcrop_model.py:379-388, no host sync"""
     out = torch.empty(2, device=partials.device, dtype=torch.float32)
-    rc = _lib.lib().wm_psnr_gate(_p(partials), partials.numel(), float(n), threshold, w_below, w_above, _p(out), _stream())
-    _lib.check(rc, "wm_psnr_gate")
+    _lib.checked().wm_psnr_gate(_p(partials), partials.numel(), float(n), threshold, w_below, w_above, _p(out), _stream())
     return out
 
 
@@ -1190,8 +1128,7 @@ def mse_fwd_bwd_gated(a, b, gscale, gate, gscale_dev=None):
     nparts = max(1, min(1024, (n + 4095) // 4096))
     part = torch.empty(nparts, device=a.device, dtype=torch.float32)
     grad = torch.empty_like(a)
-    rc = _lib.lib().wm_mse_fwd_bwd_gated(_p(a), _p(b), _p(grad), gscale, _p(gate), _p(gscale_dev), _p(part), nparts, n, _stream())
-    _lib.check(rc, "wm_mse_fwd_bwd_gated")
+    _lib.checked().wm_mse_fwd_bwd_gated(_p(a), _p(b), _p(grad), gscale, _p(gate), _p(gscale_dev), _p(part), nparts, n, _stream())
     return part, grad
 
 
@@ -1206,9 +1143,8 @@ def bce_logits_target(p, target, gscale=1.0, want_grad=True, chain_sigmoid=False
     part = torch.empty(nparts, device=p.device, dtype=torch.float32)
     loss = torch.empty(1, device=p.device, dtype=torch.float32)
     grad = torch.empty_like(p) if want_grad else None
-    rc = _lib.lib().wm_bce_logits_target(_p(p), _p(target), n, gscale, _p(gscale_dev), _p(part), nparts, _p(loss), _p(grad),
-                                         1 if chain_sigmoid else 0, _stream())
-    _lib.check(rc, "wm_bce_logits_target")
+    _lib.checked().wm_bce_logits_target(_p(p), _p(target), n, gscale, _p(gscale_dev), _p(part), nparts, _p(loss), _p(grad),
+                                        1 if chain_sigmoid else 0, _stream())
     return loss, grad
 
 
@@ -1220,8 +1156,7 @@ def masked_axpy_(a, g, mask):
     if not (a.dtype == g.dtype == mask.dtype == torch.float32) or not (a.is_contiguous() and g.is_contiguous() and mask.is_contiguous()):
         raise ValueError("masked_axpy_: contiguous float32 tensors expected (a is updated in place)")
     B, C, H, W = a.shape
-    rc = _lib.lib().wm_masked_axpy(_p(a), _p(g), _p(mask), B, C, H * W, _stream())
-    _lib.check(rc, "wm_masked_axpy")
+    _lib.checked().wm_masked_axpy(_p(a), _p(g), _p(mask), B, C, H * W, _stream())
     _wrote(a)
     return a
 
@@ -1231,8 +1166,7 @@ def mask_threshold(p, threshold=0.5):
     _need_cuda(p)
     p = p.contiguous().float()
     out = torch.empty(p.shape, device=p.device, dtype=torch.uint8)
-    rc = _lib.lib().wm_mask_threshold(_p(p), threshold, _p(out), p.numel(), _stream())
-    _lib.check(rc, "wm_mask_threshold")
+    _lib.checked().wm_mask_threshold(_p(p), threshold, _p(out), p.numel(), _stream())
     return out
 
 
@@ -1244,12 +1178,10 @@ def clip_grad_norm_(flats, max_norm, parts=None):
     arr = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
     ns = (ctypes.c_int * len(parts))(*[p.numel() for p in parts])
     out = torch.empty(2, device=flats[0].device, dtype=torch.float32)
-    L = _lib.lib()
-    rc = L.wm_clip_coef(arr, ns, len(parts), float(max_norm), _p(out), _stream())
-    _lib.check(rc, "wm_clip_coef")
+    L = _lib.checked()
+    L.wm_clip_coef(arr, ns, len(parts), float(max_norm), _p(out), _stream())
     for f in flats:
-        rc = L.wm_scale_dev(_p(f), f.numel(), _p(out), _stream())
-        _lib.check(rc, "wm_scale_dev")
+        L.wm_scale_dev(_p(f), f.numel(), _p(out), _stream())
     return out
 
 
@@ -1306,8 +1238,7 @@ def _planes(x):
 def stencil3(x, w9):
     x, N, H, W = _planes(x)
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_stencil3_fwd(_p(x), _p(y), N, H, W, _host_floats(w9), _stream())
-    _lib.check(rc, "wm_stencil3_fwd")
+    _lib.checked().wm_stencil3_fwd(_p(x), _p(y), N, H, W, _host_floats(w9), _stream())
     return y
 
 
@@ -1315,16 +1246,14 @@ def median_fwd(x, k, want_idx=True):
     x, N, H, W = _planes(x)
     y = torch.empty_like(x)
     idx = torch.empty(x.shape, device=x.device, dtype=torch.int8) if want_idx else None
-    rc = _lib.lib().wm_median_fwd(_p(x), _p(y), _p(idx), N, H, W, k, _stream())
-    _lib.check(rc, "wm_median_fwd")
+    _lib.checked().wm_median_fwd(_p(x), _p(y), _p(idx), N, H, W, k, _stream())
     return y, idx
 
 
 def median_bwd(gy, idx, k):
     gy, N, H, W = _planes(gy)
     gx = torch.empty_like(gy)
-    rc = _lib.lib().wm_median_bwd(_p(gy), _p(idx), _p(gx), N, H, W, k, _stream())
-    _lib.check(rc, "wm_median_bwd")
+    _lib.checked().wm_median_bwd(_p(gy), _p(idx), _p(gx), N, H, W, k, _stream())
     return gx
 
 
@@ -1334,8 +1263,7 @@ def resample_fwd(x, rect, out_hw, kind, clamp01=False):
     h0, hs, w0, ws = rect
     OH, OW = out_hw
     y = torch.empty(x.shape[0], x.shape[1], OH, OW, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_resample_fwd(_p(x), _p(y), N, H, W, h0, hs, w0, ws, OH, OW, kind, 1 if clamp01 else 0, _stream())
-    _lib.check(rc, "wm_resample_fwd")
+    _lib.checked().wm_resample_fwd(_p(x), _p(y), N, H, W, h0, hs, w0, ws, OH, OW, kind, 1 if clamp01 else 0, _stream())
     return y
 
 
@@ -1349,11 +1277,9 @@ def resample_bwd(gy, y_clamped, in_hw, rect, kind, separable=True):
     yc = y_clamped.contiguous() if y_clamped is not None else None
     if separable:
         tmp = torch.empty(N, OH, W, device=gy.device, dtype=torch.float32)
-        rc = _lib.lib().wm_resample_bwd_sep(_p(gy), _p(yc), _p(gx), _p(tmp), N, H, W, h0, hs, w0, ws, OH, OW, kind, _stream())
-        _lib.check(rc, "wm_resample_bwd_sep")
+        _lib.checked().wm_resample_bwd_sep(_p(gy), _p(yc), _p(gx), _p(tmp), N, H, W, h0, hs, w0, ws, OH, OW, kind, _stream())
         return gx
-    rc = _lib.lib().wm_resample_bwd(_p(gy), _p(yc), _p(gx), N, H, W, h0, hs, w0, ws, OH, OW, kind, _stream())
-    _lib.check(rc, "wm_resample_bwd")
+    _lib.checked().wm_resample_bwd(_p(gy), _p(yc), _p(gx), N, H, W, h0, hs, w0, ws, OH, OW, kind, _stream())
     return gx
 
 
@@ -1361,8 +1287,7 @@ def quant(x):
     _need_cuda(x)
     x = x.contiguous().float()
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_quant_fwd(_p(x), _p(y), x.numel(), _stream())
-    _lib.check(rc, "wm_quant_fwd")
+    _lib.checked().wm_quant_fwd(_p(x), _p(y), x.numel(), _stream())
     return y
 
 
@@ -1372,9 +1297,8 @@ def bnrelu_maxpool2(y, scale, shift, C, act_out=None, act_c0=0):
     full-resolution map into act_out[..., act_c0:act_c0+C] (the skip half of a concat buffer)."""
     B, H, W, ld = y.shape
     pooled = torch.empty(B, H // 2, W // 2, C, device=y.device, dtype=y.dtype)
-    rc = _lib.lib().wm_bnrelu_maxpool2(_p(y), ld, _p(scale), _p(shift), _p(pooled), C, _p(act_out), 0 if act_out is None else act_out.shape[-1],
-                                       act_c0, B, H, W, C, dtype_id(y), _stream())
-    _lib.check(rc, "wm_bnrelu_maxpool2")
+    _lib.checked().wm_bnrelu_maxpool2(_p(y), ld, _p(scale), _p(shift), _p(pooled), C, _p(act_out), 0 if act_out is None else act_out.shape[-1],
+                                      act_c0, B, H, W, C, dtype_id(y), _stream())
     return pooled
 
 
@@ -1387,14 +1311,13 @@ def maxpool2_bwd(y, scale, shift, gpooled, g_skip, g_skip_c0, C):
     if g_skip is not None:
         ldgs = g_skip.shape[-1]
         gs_ptr = g_skip.data_ptr() + g_skip_c0 * g_skip.element_size()
-    rc = _lib.lib().wm_maxpool2_bwd(_p(y), ld, _p(scale), _p(shift), _p(gpooled), gpooled.shape[-1], gs_ptr, ldgs, _p(g), C, B, H, W, C, dtype_id(y),
-                                    _stream())
-    _lib.check(rc, "wm_maxpool2_bwd")
+    _lib.checked().wm_maxpool2_bwd(_p(y), ld, _p(scale), _p(shift), _p(gpooled), gpooled.shape[-1], gs_ptr, ldgs, _p(g), C, B, H, W, C, dtype_id(y),
+                                   _stream())
     return g
 
 
 def upconv2x2_mfma_supported(Cin, Cout, dtype):
-    return bool(_lib.lib().wm_upconv2x2_mfma_supported(Cin, Cout, dt_id(dtype)))
+    return bool(_lib.checked().wm_upconv2x2_mfma_supported(Cin, Cout, dt_id(dtype)))
 
 
 def upconv2x2_pack(w, dtype=torch.bfloat16):
@@ -1402,8 +1325,7 @@ def upconv2x2_pack(w, dtype=torch.bfloat16):
     Cin, Cout = w.shape[0], w.shape[1]
     wf = torch.empty(4 * Cout, Cin, device=w.device, dtype=dtype)
     wb = torch.empty(Cin, 4 * Cout, device=w.device, dtype=dtype)
-    rc = _lib.lib().wm_upconv2x2_pack(_p(w), _p(wf), _p(wb), Cin, Cout, dt_id(dtype), _stream())
-    _lib.check(rc, "wm_upconv2x2_pack")
+    _lib.checked().wm_upconv2x2_pack(_p(w), _p(wf), _p(wb), Cin, Cout, dt_id(dtype), _stream())
     return wf, wb
 
 
@@ -1413,13 +1335,11 @@ def upconv2x2_fwd(x, scale, shift, w, bias, out, c0):
     Cin, Cout = w.shape[0], w.shape[1]
     if upconv2x2_mfma_supported(Cin, Cout, x.dtype):
         wf, _ = upconv2x2_pack(w, x.dtype)
-        rc = _lib.lib().wm_upconv2x2_fwd_mfma(_p(x), ldx, _p(scale), _p(shift), _p(wf), _p(bias), _p(out), out.shape[-1], c0, B, H, W, Cin, Cout,
-                                              dtype_id(x), _stream())
-        _lib.check(rc, "wm_upconv2x2_fwd_mfma")
+        _lib.checked().wm_upconv2x2_fwd_mfma(_p(x), ldx, _p(scale), _p(shift), _p(wf), _p(bias), _p(out), out.shape[-1], c0, B, H, W, Cin, Cout,
+                                             dtype_id(x), _stream())
         return out
-    rc = _lib.lib().wm_upconv2x2_fwd(_p(x), ldx, _p(scale), _p(shift), _p(w), _p(bias), _p(out), out.shape[-1], c0, B, H, W, Cin, Cout, dtype_id(x),
-                                     _stream())
-    _lib.check(rc, "wm_upconv2x2_fwd")
+    _lib.checked().wm_upconv2x2_fwd(_p(x), ldx, _p(scale), _p(shift), _p(w), _p(bias), _p(out), out.shape[-1], c0, B, H, W, Cin, Cout, dtype_id(x),
+                                    _stream())
     return out
 
 
@@ -1427,27 +1347,24 @@ def upconv2x2_bwd(x, scale, shift, w, gy, c0, dw, dbias, accumulate):
     """returns gx [B,H,W,Cin]; writes dw [Cin,Cout,2,2], dbias [Cout]."""
     B, H, W, ldx = x.shape
     Cin, Cout = w.shape[0], w.shape[1]
-    L = _lib.lib()
+    L = _lib.checked()
     if upconv2x2_mfma_supported(Cin, Cout, x.dtype):
         _, wb = upconv2x2_pack(w, x.dtype)
         gx = torch.empty(B, H, W, Cin, device=x.device, dtype=x.dtype)
-        rc = L.wm_upconv2x2_dgrad_mfma(_p(gy), gy.shape[-1], c0, _p(wb), _p(gx), Cin, B, H, W, Cin, Cout, dtype_id(x), _stream())
-        _lib.check(rc, "wm_upconv2x2_dgrad_mfma")
+        L.wm_upconv2x2_dgrad_mfma(_p(gy), gy.shape[-1], c0, _p(wb), _p(gx), Cin, B, H, W, Cin, Cout, dtype_id(x), _stream())
         ns = L.wm_upconv2x2_wgrad_nsplit(B, H, W, Cin, Cout)
         part = torch.empty(ns, Cin, 4 * Cout, device=x.device, dtype=torch.float32)
         bpart = torch.empty(ns, 4 * Cout, device=x.device, dtype=torch.float32)
-        rc = L.wm_upconv2x2_wgrad_mfma(_p(x), ldx, _p(scale), _p(shift), _p(gy), gy.shape[-1], c0, _p(part), _p(bpart), _p(dw), _p(dbias),
-                                       1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x), _stream())
-        _lib.check(rc, "wm_upconv2x2_wgrad_mfma")
+        L.wm_upconv2x2_wgrad_mfma(_p(x), ldx, _p(scale), _p(shift), _p(gy), gy.shape[-1], c0, _p(part), _p(bpart), _p(dw), _p(dbias),
+                                  1 if accumulate else 0, B, H, W, Cin, Cout, dtype_id(x), _stream())
         return gx
     chunks = L.wm_upconv2x2_dw_chunks(B, H, W)
     N = 4 * Cout
     part = torch.empty(chunks, (Cin + 1) * N, device=x.device, dtype=torch.float32)
     w_t = w.permute(2, 3, 1, 0).reshape(N, Cin).contiguous()
     gx = torch.empty(B, H, W, Cin, device=x.device, dtype=x.dtype)
-    rc = L.wm_upconv2x2_bwd(_p(x), ldx, _p(scale), _p(shift), _p(w_t), _p(gy), gy.shape[-1], c0, _p(gx), Cin, _p(part), B, H, W, Cin, Cout,
-                            dtype_id(x), _stream())
-    _lib.check(rc, "wm_upconv2x2_bwd")
+    L.wm_upconv2x2_bwd(_p(x), ldx, _p(scale), _p(shift), _p(w_t), _p(gy), gy.shape[-1], c0, _p(gx), Cin, _p(part), B, H, W, Cin, Cout,
+                       dtype_id(x), _stream())
     red = torch.empty((Cin + 1) * N, device=x.device, dtype=torch.float32)
     colsum(part, (Cin + 1) * N, (Cin + 1) * N, red, False)
     gw = red[:Cin * N].view(Cin, Cout, 2, 2)
@@ -1471,8 +1388,7 @@ def diffjpeg_fwd(x, rounding, factor):
     x = x.contiguous()
     y = torch.empty_like(x)
     B, _, H, W = x.shape
-    rc = _lib.lib().wm_diffjpeg_fwd(_p(x), _p(y), B, H, W, rounding, factor, _stream())
-    _lib.check(rc, "wm_diffjpeg_fwd")
+    _lib.checked().wm_diffjpeg_fwd(_p(x), _p(y), B, H, W, rounding, factor, _stream())
     return y
 
 
@@ -1481,8 +1397,7 @@ def diffjpeg_bwd(x, gy, rounding, factor):
     x = x.contiguous(); gy = gy.contiguous()
     gx = torch.empty_like(gy)
     B, _, H, W = x.shape
-    rc = _lib.lib().wm_diffjpeg_bwd(_p(x), _p(gy), _p(gx), B, H, W, rounding, factor, _stream())
-    _lib.check(rc, "wm_diffjpeg_bwd")
+    _lib.checked().wm_diffjpeg_bwd(_p(x), _p(gy), _p(gx), B, H, W, rounding, factor, _stream())
     return gx
 
 
@@ -1510,8 +1425,7 @@ def gconv_pack(w, rows, cols, transpose, dtype):
     w = w.contiguous()
     Cout, Cin, KH, KW = w.shape
     wp = torch.empty(KH * KW, rows, cols, device=w.device, dtype=dtype)
-    rc = _lib.lib().wm_gconv_pack(_p(w), _p(wp), Cout, Cin, KH, KW, rows, cols, 1 if transpose else 0, dt_id(dtype), _stream())
-    _lib.check(rc, "wm_gconv_pack")
+    _lib.checked().wm_gconv_pack(_p(w), _p(wp), Cout, Cin, KH, KW, rows, cols, 1 if transpose else 0, dt_id(dtype), _stream())
     return wp
 
 
@@ -1529,9 +1443,8 @@ def gconv_fwd(x, wp, bias, out_hw, KH, KW, stride, pad, dgrad=False, dilation=1)
         raise ValueError("bias must be f32 with one entry per (padded) output channel")
     OH, OW = out_hw
     out = torch.empty(B, OH, OW, NC, device=x.device, dtype=x.dtype)
-    rc = _lib.lib().wm_gconv_fwd(_p(x), _p(wp), _p(bias), _p(out), B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, 1 if dgrad else 0, dt_id(x.dtype),
-                                 _stream())
-    _lib.check(rc, "wm_gconv_fwd")
+    _lib.checked().wm_gconv_fwd(_p(x), _p(wp), _p(bias), _p(out), B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, 1 if dgrad else 0, dt_id(x.dtype),
+                                _stream())
     return out
 
 
@@ -1546,9 +1459,8 @@ def gconv_dil_fwd(x, wp, bias, out_hw, KH, KW, stride, pad, dilation, dgrad=Fals
         raise ValueError("bias must be f32 with one entry per (padded) output channel")
     OH, OW = out_hw
     out = torch.empty(B, OH, OW, NC, device=x.device, dtype=x.dtype)
-    rc = _lib.lib().wm_gconv_dil_fwd(_p(x), _p(wp), _p(bias), _p(out), B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, int(dilation),
-                                     1 if dgrad else 0, dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_gconv_dil_fwd")
+    _lib.checked().wm_gconv_dil_fwd(_p(x), _p(wp), _p(bias), _p(out), B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad, int(dilation),
+                                    1 if dgrad else 0, dt_id(x.dtype), _stream())
     return out
 
 
@@ -1561,7 +1473,7 @@ def gconv_wgrad(dout, x, Cout, Cin, KH, KW, stride, pad, want_bias=True, dw_acc=
     _, IH, IW, KC = x.shape
     if x.shape[0] != B or x.dtype != dout.dtype:
         raise ValueError("gconv_wgrad: operands disagree")
-    L = _lib.lib()
+    L = _lib.checked()
     partial = torch.empty(L.wm_gconv_wgrad_scratch_floats(B, OH, OW, KC, NC, KH, KW), device=x.device,
                           dtype=torch.float32)
     acc = dw_acc is not None
@@ -1571,13 +1483,11 @@ def gconv_wgrad(dout, x, Cout, Cin, KH, KW, stride, pad, want_bias=True, dw_acc=
     dw = dw_acc if acc else torch.empty(Cout, Cin, KH, KW, device=x.device, dtype=torch.float32)
     db = (db_acc if acc else torch.empty(Cout, device=x.device, dtype=torch.float32)) if want_bias else None
     if dilation != 1 or dil_entry:
-        rc = L.wm_gconv_dil_wgrad(_p(dout), _p(x), _p(partial), _p(dw), _p(db), 1 if acc else 0, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad,
-                                  int(dilation), Cout, Cin, dt_id(x.dtype), _stream())
-        _lib.check(rc, "wm_gconv_dil_wgrad")
+        L.wm_gconv_dil_wgrad(_p(dout), _p(x), _p(partial), _p(dw), _p(db), 1 if acc else 0, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad,
+                             int(dilation), Cout, Cin, dt_id(x.dtype), _stream())
         return dw, db
-    rc = _lib.lib().wm_gconv_wgrad(_p(dout), _p(x), _p(partial), _p(dw), _p(db), 1 if acc else 0, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad,
-                                   Cout, Cin, dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_gconv_wgrad")
+    _lib.checked().wm_gconv_wgrad(_p(dout), _p(x), _p(partial), _p(dw), _p(db), 1 if acc else 0, B, IH, IW, KC, OH, OW, NC, KH, KW, stride, pad,
+                                  Cout, Cin, dt_id(x.dtype), _stream())
     return dw, db
 
 
@@ -1589,14 +1499,12 @@ def gcolsum(x, creal, out_acc=None, f64=False):
     if out_acc is not None and (not out_acc.is_contiguous() or out_acc.numel() != creal or out_acc.dtype != torch.float32):
         raise ValueError("gcolsum: accumulation target does not match")
     out = out_acc if out_acc is not None else torch.empty(creal, device=x.device, dtype=torch.float32)
-    L = _lib.lib()
+    L = _lib.checked()
     if f64:
-        rc = L.wm_gcolsum_f64(_p(x), x.numel() // C, C, _p(out), creal, 0 if out_acc is None else 1, dt_id(x.dtype), _stream())
-        _lib.check(rc, "wm_gcolsum_f64")
+        L.wm_gcolsum_f64(_p(x), x.numel() // C, C, _p(out), creal, 0 if out_acc is None else 1, dt_id(x.dtype), _stream())
         return out
     scratch = torch.empty(L.wm_gcolsum_scratch_floats(x.numel() // C, C), device=x.device, dtype=torch.float32)
-    rc = L.wm_gcolsum(_p(x), x.numel() // C, C, _p(out), creal, 0 if out_acc is None else 1, _p(scratch), dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_gcolsum")
+    L.wm_gcolsum(_p(x), x.numel() // C, C, _p(out), creal, 0 if out_acc is None else 1, _p(scratch), dt_id(x.dtype), _stream())
     return out
 
 
@@ -1604,8 +1512,7 @@ def unary_fwd(x, kind):
     _need_cuda(x)
     x = x.contiguous()
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_unary_fwd(_p(x), _p(y), x.numel(), ACT_KINDS[kind], dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_unary_fwd")
+    _lib.checked().wm_unary_fwd(_p(x), _p(y), x.numel(), ACT_KINDS[kind], dt_id(x.dtype), _stream())
     return y
 
 
@@ -1613,8 +1520,7 @@ def unary_bwd(x, gy, kind):
     _need_cuda(x, gy)
     gy = gy.contiguous()
     gx = torch.empty_like(x)
-    rc = _lib.lib().wm_unary_bwd(_p(x), _p(gy), _p(gx), x.numel(), ACT_KINDS[kind], dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_unary_bwd")
+    _lib.checked().wm_unary_bwd(_p(x), _p(gy), _p(gx), x.numel(), ACT_KINDS[kind], dt_id(x.dtype), _stream())
     return gx
 
 
@@ -1629,11 +1535,10 @@ def unary_bwd_colsum(x, gy, kind, creal, db_acc=None):
     if db_acc is not None and (not db_acc.is_contiguous() or db_acc.numel() != creal or db_acc.dtype != torch.float32):
         raise ValueError("unary_bwd_colsum: accumulation target does not match")
     db = db_acc if db_acc is not None else torch.empty(creal, device=x.device, dtype=torch.float32)
-    L = _lib.lib()
+    L = _lib.checked()
     part = torch.empty(L.wm_unary_bwd_colsum_scratch_floats(npix, C), device=x.device, dtype=torch.float32)
-    rc = L.wm_unary_bwd_colsum(_p(x), _p(gy), _p(gx), npix, C, ACT_BWD_KINDS[kind], _p(part), _p(db), creal, 0 if db_acc is None else 1,
-                               dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_unary_bwd_colsum")
+    L.wm_unary_bwd_colsum(_p(x), _p(gy), _p(gx), npix, C, ACT_BWD_KINDS[kind], _p(part), _p(db), creal, 0 if db_acc is None else 1,
+                          dt_id(x.dtype), _stream())
     return gx, db
 
 
@@ -1643,8 +1548,7 @@ def add_scaled(a, b, alpha=1.0):
         raise ValueError("add_scaled: operands disagree")
     a, b = a.contiguous(), b.contiguous()
     out = torch.empty_like(a)
-    rc = _lib.lib().wm_add_scaled(_p(a), _p(b), _p(out), a.numel(), alpha, dt_id(a.dtype), _stream())
-    _lib.check(rc, "wm_add_scaled")
+    _lib.checked().wm_add_scaled(_p(a), _p(b), _p(out), a.numel(), alpha, dt_id(a.dtype), _stream())
     return out
 
 
@@ -1655,8 +1559,7 @@ def qfatt_fwd(x, res, gamma, beta):
     gamma, beta = gamma.contiguous(), beta.contiguous()
     assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.shape == beta.shape and gamma.shape[0] == B
     out = torch.empty_like(x)
-    rc = _lib.lib().wm_qfatt_fwd(_p(x), _p(res), _p(gamma), _p(beta), _p(out), B, H * W, C, gamma.shape[1], dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_qfatt_fwd")
+    _lib.checked().wm_qfatt_fwd(_p(x), _p(res), _p(gamma), _p(beta), _p(out), B, H * W, C, gamma.shape[1], dt_id(x.dtype), _stream())
     return out
 
 
@@ -1667,10 +1570,9 @@ def qfatt_bwd(g, res, gamma):
     gres = torch.empty_like(g)
     gg = torch.zeros_like(gamma)
     gb = torch.zeros_like(gamma)
-    L = _lib.lib()
+    L = _lib.checked()
     scratch = torch.empty(L.wm_qfatt_bwd_scratch_floats(B, H * W, gamma.shape[1]), device=g.device, dtype=torch.float32)
-    rc = L.wm_qfatt_bwd(_p(g), _p(res), _p(gamma), _p(gres), _p(gg), _p(gb), _p(scratch), B, H * W, C, gamma.shape[1], dt_id(g.dtype), _stream())
-    _lib.check(rc, "wm_qfatt_bwd")
+    L.wm_qfatt_bwd(_p(g), _p(res), _p(gamma), _p(gres), _p(gg), _p(gb), _p(scratch), B, H * W, C, gamma.shape[1], dt_id(g.dtype), _stream())
     return gres, gg, gb
 
 
@@ -1678,8 +1580,7 @@ def gpool_fwd(x):
     x = _nhwc(x)
     B, H, W, C = x.shape
     out = torch.empty(B, C, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_gpool_fwd(_p(x), _p(out), B, H * W, C, dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_gpool_fwd")
+    _lib.checked().wm_gpool_fwd(_p(x), _p(out), B, H * W, C, dt_id(x.dtype), _stream())
     return out
 
 
@@ -1688,8 +1589,7 @@ def gpool_bwd(g, shape, dtype):
     B, H, W, C = shape
     g = g.contiguous().float()
     gx = torch.empty(B, H, W, C, device=g.device, dtype=dtype)
-    rc = _lib.lib().wm_gpool_bwd(_p(g), _p(gx), B, H * W, C, dt_id(dtype), _stream())
-    _lib.check(rc, "wm_gpool_bwd")
+    _lib.checked().wm_gpool_bwd(_p(g), _p(gx), B, H * W, C, dt_id(dtype), _stream())
     return gx
 
 
@@ -1703,8 +1603,7 @@ def pad_nchw_to_nhwc(x, pads, mode, dtype):
     B, C, H, W = x.shape
     l, r, t, b = pads
     out = torch.empty(B, H + t + b, W + l + r, cpad(C), device=x.device, dtype=dtype)
-    rc = _lib.lib().wm_pad_nchw_to_nhwc(_p(x), _p(out), B, C, H, W, l, r, t, b, mode, out.shape[3], dt_id(dtype), _stream())
-    _lib.check(rc, "wm_pad_nchw_to_nhwc")
+    _lib.checked().wm_pad_nchw_to_nhwc(_p(x), _p(out), B, C, H, W, l, r, t, b, mode, out.shape[3], dt_id(dtype), _stream())
     return out
 
 
@@ -1713,8 +1612,7 @@ def pad_nchw_to_nhwc_bwd(gp, shape, pads, mode):
     B, C, H, W = shape
     l, r, t, b = pads
     gx = torch.empty(B, C, H, W, device=gp.device, dtype=torch.float32)
-    rc = _lib.lib().wm_pad_nchw_to_nhwc_bwd(_p(gp), _p(gx), B, C, H, W, l, r, t, b, mode, gp.shape[3], dt_id(gp.dtype), _stream())
-    _lib.check(rc, "wm_pad_nchw_to_nhwc_bwd")
+    _lib.checked().wm_pad_nchw_to_nhwc_bwd(_p(gp), _p(gx), B, C, H, W, l, r, t, b, mode, gp.shape[3], dt_id(gp.dtype), _stream())
     return gx
 
 
@@ -1722,8 +1620,7 @@ def gunpack_nchw(x, C, H, W):
     x = _nhwc(x)
     B, PH, PW, CP = x.shape
     out = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_gunpack_nchw(_p(x), _p(out), B, C, H, W, PH, PW, CP, dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_gunpack_nchw")
+    _lib.checked().wm_gunpack_nchw(_p(x), _p(out), B, C, H, W, PH, PW, CP, dt_id(x.dtype), _stream())
     return out
 
 
@@ -1733,8 +1630,7 @@ def gunpack_nchw_bwd(g, shape, dtype):
     B, C, H, W = g.shape
     _, PH, PW, CP = shape
     gx = torch.empty(B, PH, PW, CP, device=g.device, dtype=dtype)
-    rc = _lib.lib().wm_gunpack_nchw_bwd(_p(g), _p(gx), B, C, H, W, PH, PW, CP, dt_id(dtype), _stream())
-    _lib.check(rc, "wm_gunpack_nchw_bwd")
+    _lib.checked().wm_gunpack_nchw_bwd(_p(g), _p(gx), B, C, H, W, PH, PW, CP, dt_id(dtype), _stream())
     return gx
 
 
@@ -1746,10 +1642,9 @@ def spectral_norm_fwd(w, u, v, do_iter):
     assert u.numel() == M and v.numel() == N and u.is_contiguous() and v.is_contiguous() and u.dtype == torch.float32 and v.dtype == torch.float32
     sigma = torch.empty(1, device=w.device, dtype=torch.float32)
     wsn = torch.empty_like(w)
-    L = _lib.lib()
+    L = _lib.checked()
     scratch = torch.empty(L.wm_spectral_norm_scratch_floats(M, N), device=w.device, dtype=torch.float32)
-    rc = L.wm_spectral_norm_fwd(_p(w), _p(u), _p(v), _p(sigma), _p(wsn), _p(scratch), M, N, 1 if do_iter else 0, _stream())
-    _lib.check(rc, "wm_spectral_norm_fwd")
+    L.wm_spectral_norm_fwd(_p(w), _p(u), _p(v), _p(sigma), _p(wsn), _p(scratch), M, N, 1 if do_iter else 0, _stream())
     return wsn, sigma
 
 
@@ -1759,8 +1654,7 @@ def spectral_norm_bwd(g, wsn, u, v, sigma):
     M, N = g.shape[0], g.numel() // g.shape[0]
     partial = torch.empty(256, device=g.device, dtype=torch.float32)
     gw = torch.empty_like(g)
-    rc = _lib.lib().wm_spectral_norm_bwd(_p(g), _p(wsn), _p(u), _p(v), _p(sigma), _p(partial), _p(gw), M, N, 0, _stream())
-    _lib.check(rc, "wm_spectral_norm_bwd")
+    _lib.checked().wm_spectral_norm_bwd(_p(g), _p(wsn), _p(u), _p(v), _p(sigma), _p(partial), _p(gw), M, N, 0, _stream())
     return gw
 
 
@@ -1769,9 +1663,9 @@ def bayar_constrain_(w, torch_order=False):
     plane sums in the order torch.sum takes on the CPU instead of left to right (the reference's float32 result bit for bit)"""
     _need_cuda(w)
     assert w.dtype == torch.float32 and w.is_contiguous() and w.shape[-2:] == (5, 5)
-    L = _lib.lib()
-    rc = (L.wm_bayar_constrain_torch_order if torch_order else L.wm_bayar_constrain)(_p(w), w.shape[0] * w.shape[1], _stream())
-    _lib.check(rc, "wm_bayar_constrain")
+    L = _lib.checked()
+    constrain = L.wm_bayar_constrain_torch_order if torch_order else L.wm_bayar_constrain
+    constrain(_p(w), w.shape[0] * w.shape[1], _stream())
     return w
 
 
@@ -1790,8 +1684,7 @@ def reflect_pad_fwd(x, pad):
     if pad < 0 or pad > min(H, W) - 1:
         raise ValueError(f"reflect_pad_fwd: pad {pad} needs min(H, W) - 1 >= pad, got {tuple(x.shape)}")
     out = torch.empty(B, H + 2 * pad, W + 2 * pad, CP, device=x.device, dtype=x.dtype)
-    rc = _lib.lib().wm_reflect_pad_fwd(_p(x), _p(out), B, H, W, CP, pad, dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_reflect_pad_fwd")
+    _lib.checked().wm_reflect_pad_fwd(_p(x), _p(out), B, H, W, CP, pad, dt_id(x.dtype), _stream())
     return out
 
 
@@ -1804,8 +1697,7 @@ def reflect_pad_bwd(g, pad):
     if pad < 0 or H < 1 or W < 1 or pad > min(H, W) - 1:
         raise ValueError(f"reflect_pad_bwd: {tuple(g.shape)} is no reflection-padded tensor of pad {pad}")
     gx = torch.empty(B, H, W, CP, device=g.device, dtype=g.dtype)
-    rc = _lib.lib().wm_reflect_pad_bwd(_p(g), _p(gx), B, H, W, CP, pad, dt_id(g.dtype), _stream())
-    _lib.check(rc, "wm_reflect_pad_bwd")
+    _lib.checked().wm_reflect_pad_bwd(_p(g), _p(gx), B, H, W, CP, pad, dt_id(g.dtype), _stream())
     return gx
 
 
@@ -1825,9 +1717,8 @@ def haar(x, C, fac, up, by_wavelet=False):
             raise ValueError(f"haar analysis needs even height / width and {C} channels, got {tuple(x.shape)}")
         H, W = XH // 2, XW // 2
         out = torch.empty(B, H, W, cpad(4 * C), device=x.device, dtype=x.dtype)
-    rc = _lib.lib().wm_haar(_p(x), _p(out), B, H, W, C, CPin, out.shape[3], fac, (1 if up else 0) | (2 if by_wavelet else 0), dt_id(x.dtype),
-                            _stream())
-    _lib.check(rc, "wm_haar")
+    _lib.checked().wm_haar(_p(x), _p(out), B, H, W, C, CPin, out.shape[3], fac, (1 if up else 0) | (2 if by_wavelet else 0), dt_id(x.dtype),
+                           _stream())
     return out
 
 
@@ -1837,8 +1728,7 @@ def chan_copy_(dst, doff, src, soff, n):
     if dst.shape[:3] != src.shape[:3] or dst.dtype != src.dtype:
         raise ValueError("chan_copy_: pixel grids / dtypes disagree")
     npix = dst.shape[0] * dst.shape[1] * dst.shape[2]
-    rc = _lib.lib().wm_chan_copy(_p(src), _p(dst), npix, src.shape[3], soff, dst.shape[3], doff, n, dt_id(dst.dtype), _stream())
-    _lib.check(rc, "wm_chan_copy")
+    _lib.checked().wm_chan_copy(_p(src), _p(dst), npix, src.shape[3], soff, dst.shape[3], doff, n, dt_id(dst.dtype), _stream())
     return dst
 
 
@@ -1854,9 +1744,8 @@ def chan_place(dstride, a, aoff, adst, na, b=None, boff=0, bdst=0, nb=0):
         raise ValueError("chan_place: the channel stride must be a multiple of 16")
     out = torch.empty(*a.shape[:3], dstride, device=a.device, dtype=a.dtype)
     npix = a.shape[0] * a.shape[1] * a.shape[2]
-    rc = _lib.lib().wm_chan_place(_p(a), a.shape[3], aoff, adst, na, _p(b), b.shape[3] if b is not None else 0, boff, bdst, nb, _p(out), dstride,
-                                  npix, dt_id(a.dtype), _stream())
-    _lib.check(rc, "wm_chan_place")
+    _lib.checked().wm_chan_place(_p(a), a.shape[3], aoff, adst, na, _p(b), b.shape[3] if b is not None else 0, boff, bdst, nb, _p(out), dstride,
+                                 npix, dt_id(a.dtype), _stream())
     return out
 
 
@@ -1866,8 +1755,7 @@ def coupling_fwd(x, s, t, clamp, eps, rev):
         raise ValueError("coupling_fwd: operands disagree")
     x, s, t = x.contiguous(), s.contiguous(), t.contiguous()
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_coupling_fwd(_p(x), _p(s), _p(t), _p(y), x.numel(), clamp, eps, 1 if rev else 0, dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_coupling_fwd")
+    _lib.checked().wm_coupling_fwd(_p(x), _p(s), _p(t), _p(y), x.numel(), clamp, eps, 1 if rev else 0, dt_id(x.dtype), _stream())
     return y
 
 
@@ -1875,8 +1763,7 @@ def coupling_bwd(g, v, s, clamp, eps, rev):
     _need_cuda(g, v, s)
     g = g.contiguous()
     gx, gs, gt = torch.empty_like(g), torch.empty_like(g), torch.empty_like(g)
-    rc = _lib.lib().wm_coupling_bwd(_p(g), _p(v), _p(s), _p(gx), _p(gs), _p(gt), g.numel(), clamp, eps, 1 if rev else 0, dt_id(g.dtype), _stream())
-    _lib.check(rc, "wm_coupling_bwd")
+    _lib.checked().wm_coupling_bwd(_p(g), _p(v), _p(s), _p(gx), _p(gs), _p(gt), g.numel(), clamp, eps, 1 if rev else 0, dt_id(g.dtype), _stream())
     return gx, gs, gt
 
 
@@ -1900,8 +1787,7 @@ def invblock_shift_fwd(x, f, n1, n2, sign, other=None):
     """x[..., :n1] + sign * f as its own tensor [.., cpad(n1)], or, with other [.., cpad(n2)], as cat(that, other[..., :n2]) [.., cpad(n1+n2)]"""
     x, (f, other), npix = _invblock_args("invblock_shift_fwd", x, n1, n2, f=(f, cpad(n1)), other=(other, cpad(n2)))
     out = torch.empty(*x.shape[:3], cpad(n1 + n2) if other is not None else cpad(n1), device=x.device, dtype=x.dtype)
-    rc = _lib.lib().wm_invblock_shift(_p(x), x.shape[3], _p(f), _p(other), _p(out), npix, n1, n2, float(sign), dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_invblock_shift")
+    _lib.checked().wm_invblock_shift(_p(x), x.shape[3], _p(f), _p(other), _p(out), npix, n1, n2, float(sign), dt_id(x.dtype), _stream())
     return out
 
 
@@ -1912,9 +1798,8 @@ def invblock_shift_bwd(g, n1, n2, sign, whole, xstride):
         raise ValueError(f"invblock_shift_bwd: gradient stride {g.shape[3]} / x stride {xstride} do not match splits {n1}, {n2}")
     new = lambda c: torch.empty(*g.shape[:3], c, device=g.device, dtype=g.dtype)       # noqa: E731
     gx, gf, gother = new(xstride), new(cpad(n1)), (new(cpad(n2)) if whole else None)
-    rc = _lib.lib().wm_invblock_shift_bwd(_p(g), 1 if whole else 0, _p(gx), xstride, _p(gf), _p(gother), g.shape[0] * g.shape[1] * g.shape[2],
-                                          n1, n2, float(sign), dt_id(g.dtype), _stream())
-    _lib.check(rc, "wm_invblock_shift_bwd")
+    _lib.checked().wm_invblock_shift_bwd(_p(g), 1 if whole else 0, _p(gx), xstride, _p(gf), _p(gother), g.shape[0] * g.shape[1] * g.shape[2],
+                                         n1, n2, float(sign), dt_id(g.dtype), _stream())
     return gx, gf, gother
 
 
@@ -1928,10 +1813,9 @@ def invblock_affine_fwd(x, h, g, n1, n2, clamp, rev, other=None, want_jac=False)
     jac = scratch = None
     if want_jac:
         jac = torch.empty(B, device=x.device, dtype=torch.float32)
-        scratch = torch.empty(max(int(_lib.lib().wm_invblock_scratch_doubles(B, hw, n1, n2)), 1), device=x.device, dtype=torch.float64)
-    rc = _lib.lib().wm_invblock_affine(_p(x), x.shape[3], _p(h), _p(g), _p(other), _p(out), _p(jac), _p(scratch), B, hw, n1, n2, float(clamp),
-                                       1 if rev else 0, dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_invblock_affine")
+        scratch = torch.empty(max(int(_lib.checked().wm_invblock_scratch_doubles(B, hw, n1, n2)), 1), device=x.device, dtype=torch.float64)
+    _lib.checked().wm_invblock_affine(_p(x), x.shape[3], _p(h), _p(g), _p(other), _p(out), _p(jac), _p(scratch), B, hw, n1, n2, float(clamp),
+                                      1 if rev else 0, dt_id(x.dtype), _stream())
     return out, jac
 
 
@@ -1944,10 +1828,9 @@ def invblock_affine_bwd(gout, v, voff, h, n1, n2, clamp, rev, whole, xstride):
         raise ValueError("invblock_affine_bwd: operands disagree with the splits %d, %d" % (n1, n2))
     new = lambda c: torch.empty(*gout.shape[:3], c, device=gout.device, dtype=gout.dtype)       # noqa: E731
     gx, gh, gg, gother = new(xstride), new(cpad(n2)), new(cpad(n2)), (new(cpad(n1)) if whole else None)
-    rc = _lib.lib().wm_invblock_affine_bwd(_p(gout), 1 if whole else 0, _p(v), v.shape[3], voff, _p(h), _p(gx), xstride, _p(gh), _p(gg), _p(gother),
-                                           gout.shape[0] * gout.shape[1] * gout.shape[2], n1, n2, float(clamp), 1 if rev else 0,
-                                           dt_id(gout.dtype), _stream())
-    _lib.check(rc, "wm_invblock_affine_bwd")
+    _lib.checked().wm_invblock_affine_bwd(_p(gout), 1 if whole else 0, _p(v), v.shape[3], voff, _p(h), _p(gx), xstride, _p(gh), _p(gg), _p(gother),
+                                          gout.shape[0] * gout.shape[1] * gout.shape[2], n1, n2, float(clamp), 1 if rev else 0,
+                                          dt_id(gout.dtype), _stream())
     return gx, gh, gg, gother
 
 
@@ -1975,12 +1858,11 @@ def instnorm_stats(x, C, eps=1e-5):
     zeros in the padding channels; sums in double, fixed order"""
     x = _instnorm_args("instnorm_stats", x, C, None, None, None)
     B, H, W, CP = x.shape
-    L = _lib.lib()
+    L = _lib.checked()
     part = torch.empty(L.wm_instnorm_scratch_doubles(B, H * W, CP), device=x.device, dtype=torch.float64)
     mean = torch.empty(B, CP, device=x.device, dtype=torch.float32)
     rstd = torch.empty(B, CP, device=x.device, dtype=torch.float32)
-    rc = L.wm_instnorm_stats(_p(x), _p(part), _p(mean), _p(rstd), B, H * W, C, CP, float(eps), dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_instnorm_stats")
+    L.wm_instnorm_stats(_p(x), _p(part), _p(mean), _p(rstd), B, H * W, C, CP, float(eps), dt_id(x.dtype), _stream())
     return mean, rstd
 
 
@@ -1989,9 +1871,8 @@ def instnorm_apply(x, C, mean, rstd, gamma=None, beta=None, act=None):
     x = _instnorm_args("instnorm_apply", x, C, gamma, beta, act)
     B, H, W, CP = x.shape
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_instnorm_apply(_p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(y), B, H * W, C, CP, INSTNORM_ACTS[act], dt_id(x.dtype),
-                                      _stream())
-    _lib.check(rc, "wm_instnorm_apply")
+    _lib.checked().wm_instnorm_apply(_p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(y), B, H * W, C, CP, INSTNORM_ACTS[act], dt_id(x.dtype),
+                                     _stream())
     return y
 
 
@@ -2011,7 +1892,7 @@ def instnorm_bwd(x, dy, C, mean, rstd, gamma=None, beta=None, act=None, want_par
     if dy.shape != x.shape or dy.dtype != x.dtype:
         raise ValueError("instnorm_bwd: the output gradient does not match the input")
     B, H, W, CP = x.shape
-    L = _lib.lib()
+    L = _lib.checked()
     part = torch.empty(L.wm_instnorm_scratch_doubles(B, H * W, CP), device=x.device, dtype=torch.float64)
     mg = torch.empty(B, CP, device=x.device, dtype=torch.float32)
     mgx = torch.empty(B, CP, device=x.device, dtype=torch.float32)
@@ -2020,18 +1901,16 @@ def instnorm_bwd(x, dy, C, mean, rstd, gamma=None, beta=None, act=None, want_par
         dgamma = torch.empty(C, device=x.device, dtype=torch.float32)
         dbeta = torch.empty(C, device=x.device, dtype=torch.float32)
     act_id, dt = INSTNORM_ACTS[act], dt_id(x.dtype)
-    rc = L.wm_instnorm_bwd_sums(_p(x), _p(dy), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(part), _p(mg), _p(mgx), _p(dgamma), _p(dbeta), B, H * W, C,
-                                CP, act_id, dt, _stream())
-    _lib.check(rc, "wm_instnorm_bwd_sums")
+    L.wm_instnorm_bwd_sums(_p(x), _p(dy), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(part), _p(mg), _p(mgx), _p(dgamma), _p(dbeta), B, H * W, C,
+                           CP, act_id, dt, _stream())
     dx = torch.empty_like(x)
-    rc = L.wm_instnorm_bwd_apply(_p(x), _p(dy), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(mg), _p(mgx), _p(dx), B, H * W, C, CP, act_id, dt, _stream())
-    _lib.check(rc, "wm_instnorm_bwd_apply")
+    L.wm_instnorm_bwd_apply(_p(x), _p(dy), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(mg), _p(mgx), _p(dx), B, H * W, C, CP, act_id, dt, _stream())
     return dx, dgamma, dbeta
 
 
 def instnorm_splits(hw):
     """workgroups that share one (sample) plane of hw pixels in the instance-norm kernels"""
-    return _lib.lib().wm_instnorm_splits(hw)
+    return _lib.checked().wm_instnorm_splits(hw)
 
 
 # ----------------------------------------------------------------------------- LayerNorm and Swin window attention (csrc/swin.hip)
@@ -2054,8 +1933,7 @@ def layernorm_fwd(x, C, gamma, beta, eps=1e-5):
     y = torch.empty_like(x)
     mean = torch.empty(B * H * W, device=x.device, dtype=torch.float32)
     rstd = torch.empty(B * H * W, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().wm_layernorm_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), B * H * W, C, CP, float(eps), dt_id(x.dtype), _stream())
-    _lib.check(rc, "wm_layernorm_fwd")
+    _lib.checked().wm_layernorm_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), B * H * W, C, CP, float(eps), dt_id(x.dtype), _stream())
     return y, mean, rstd
 
 
@@ -2068,16 +1946,15 @@ def layernorm_bwd(x, dy, C, gamma, mean, rstd, want_params=True):
     if dy.shape != x.shape or dy.dtype != x.dtype:
         raise ValueError("layernorm_bwd: the output gradient does not match the input")
     B, H, W, CP = x.shape
-    L = _lib.lib()
+    L = _lib.checked()
     dx = torch.empty_like(x)
     dgamma = dbeta = part = None
     if want_params:
         part = torch.empty(L.wm_layernorm_scratch_doubles(B * H * W, C), device=x.device, dtype=torch.float64)
         dgamma = torch.empty(C, device=x.device, dtype=torch.float32)
         dbeta = torch.empty(C, device=x.device, dtype=torch.float32)
-    rc = L.wm_layernorm_bwd(_p(x), _p(dy), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta), _p(part), B * H * W, C, CP, dt_id(x.dtype),
-                            _stream())
-    _lib.check(rc, "wm_layernorm_bwd")
+    L.wm_layernorm_bwd(_p(x), _p(dy), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta), _p(part), B * H * W, C, CP, dt_id(x.dtype),
+                       _stream())
     return dx, dgamma, dbeta
 
 
@@ -2098,9 +1975,8 @@ def winattn_fwd(qkv, table, C, num_heads, ws, shift, scale):
     B, H, W, CP3 = qkv.shape
     out = torch.empty(B, H, W, cpad(C), device=qkv.device, dtype=qkv.dtype)
     lse = torch.empty(B, num_heads, H, W, device=qkv.device, dtype=torch.float32)
-    rc = _lib.lib().wm_winattn_fwd(_p(qkv), _p(table), _p(out), _p(lse), B, H, W, C, num_heads, ws, shift, float(scale), CP3, cpad(C), dt_id(qkv.dtype),
-                                   _stream())
-    _lib.check(rc, "wm_winattn_fwd")
+    _lib.checked().wm_winattn_fwd(_p(qkv), _p(table), _p(out), _p(lse), B, H, W, C, num_heads, ws, shift, float(scale), CP3, cpad(C), dt_id(qkv.dtype),
+                                  _stream())
     return out, lse
 
 
@@ -2113,13 +1989,12 @@ def winattn_bwd(g_out, qkv, table, lse, C, num_heads, ws, shift, scale):
     B, H, W, CP3 = qkv.shape
     if tuple(g_out.shape) != (B, H, W, cpad(C)) or g_out.dtype != qkv.dtype:
         raise ValueError("winattn_bwd: the output gradient does not match the forward's output")
-    L = _lib.lib()
+    L = _lib.checked()
     g_qkv = torch.empty_like(qkv)
     g_table = torch.empty_like(table)
     scratch = torch.empty(L.wm_winattn_scratch_floats(B, H, W, num_heads, ws), device=qkv.device, dtype=torch.float32)
-    rc = L.wm_winattn_bwd(_p(g_out), _p(qkv), _p(table), _p(lse), _p(g_qkv), _p(g_table), _p(scratch), B, H, W, C, num_heads, ws, shift, float(scale),
-                          CP3, cpad(C), dt_id(qkv.dtype), _stream())
-    _lib.check(rc, "wm_winattn_bwd")
+    L.wm_winattn_bwd(_p(g_out), _p(qkv), _p(table), _p(lse), _p(g_qkv), _p(g_table), _p(scratch), B, H, W, C, num_heads, ws, shift, float(scale),
+                     CP3, cpad(C), dt_id(qkv.dtype), _stream())
     return g_qkv, g_table
 
 
@@ -2138,8 +2013,7 @@ def smooth_l1(a, b, beta=1.0, want_grad=True):
     part = torch.empty(_nparts(n), device=a.device, dtype=torch.float32)
     loss = torch.empty(1, device=a.device, dtype=torch.float32)
     grad = torch.empty_like(a) if want_grad else None
-    rc = _lib.lib().wm_smooth_l1(_p(a), _p(b), n, beta, _p(part), part.numel(), _p(loss), _p(grad), _stream())
-    _lib.check(rc, "wm_smooth_l1")
+    _lib.checked().wm_smooth_l1(_p(a), _p(b), n, beta, _p(part), part.numel(), _p(loss), _p(grad), _stream())
     return loss, grad
 
 
@@ -2151,8 +2025,7 @@ def bce_prob(p, target, want_grad=True):
     part = torch.empty(_nparts(n), device=p.device, dtype=torch.float32)
     loss = torch.empty(1, device=p.device, dtype=torch.float32)
     grad = torch.empty_like(p) if want_grad else None
-    rc = _lib.lib().wm_bce_prob(_p(p), target, n, _p(part), part.numel(), _p(loss), _p(grad), _stream())
-    _lib.check(rc, "wm_bce_prob")
+    _lib.checked().wm_bce_prob(_p(p), target, n, _p(part), part.numel(), _p(loss), _p(grad), _stream())
     return loss, grad
 
 
@@ -2166,8 +2039,7 @@ def cross_entropy(logits, labels, want_grad=True):
     B, K = logits.shape
     loss = torch.empty(1, device=logits.device, dtype=torch.float32)
     grad = torch.empty_like(logits) if want_grad else None
-    rc = _lib.lib().wm_cross_entropy(_p(logits), _p(labels), B, K, K, _p(loss), _p(grad), _stream())
-    _lib.check(rc, "wm_cross_entropy")
+    _lib.checked().wm_cross_entropy(_p(logits), _p(labels), B, K, K, _p(loss), _p(grad), _stream())
     return loss, grad
 
 
@@ -2175,8 +2047,7 @@ def clamp01_fwd(x):
     _need_cuda(x)
     x = x.contiguous().float()
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_clamp01_fwd(_p(x), _p(y), x.numel(), _stream())
-    _lib.check(rc, "wm_clamp01_fwd")
+    _lib.checked().wm_clamp01_fwd(_p(x), _p(y), x.numel(), _stream())
     return y
 
 
@@ -2187,8 +2058,7 @@ def clamp01_bwd(x, g):
     x = x.contiguous().float()          # (the kernel walks both flat: a view's storage is not its elements)
     g = g.contiguous().float()
     gx = torch.empty_like(g)
-    rc = _lib.lib().wm_clamp01_bwd(_p(x), _p(g), _p(gx), g.numel(), _stream())
-    _lib.check(rc, "wm_clamp01_bwd")
+    _lib.checked().wm_clamp01_bwd(_p(x), _p(g), _p(gx), g.numel(), _stream())
     return gx
 
 
@@ -2198,8 +2068,7 @@ def psnr255(a, b):
     a, b = a.contiguous().float(), b.contiguous().float()
     n = a.numel()
     part = torch.empty(_nparts(n), device=a.device, dtype=torch.float64)
-    rc = _lib.lib().wm_psnr255_partials(_p(a), _p(b), n, _p(part), part.numel(), _stream())
-    _lib.check(rc, "wm_psnr255_partials")
+    _lib.checked().wm_psnr255_partials(_p(a), _p(b), n, _p(part), part.numel(), _stream())
     return psnr_gate(part, n)[0:1]
 
 
@@ -2229,14 +2098,12 @@ def ssim(a, b, size_average=True, want_grad=False):
     want_grad: -> (value, dplanes [3,B,C,H,W]), the derivative planes ssim_bwd(dplanes, a, b, ...) turns into the gradient wrt a"""
     a, b = _ssim_args(a, b)
     B, C, H, W = a.shape
-    L = _lib.lib()
+    L = _lib.checked()
     part = torch.empty(B * L.wm_ssim_nparts(C, H, W), device=a.device, dtype=torch.float64)
     dpl = torch.empty((3,) + tuple(a.shape), device=a.device, dtype=torch.float32) if want_grad else None
     out = torch.empty(1 + B, device=a.device, dtype=torch.float32)
-    rc = _timed("ssim_fwd", None, lambda: L.wm_ssim_fwd(_p(a), _p(b), B, C, H, W, ssim_window(), _p(part), _p(dpl), _stream()))
-    _lib.check(rc, "wm_ssim_fwd")
-    rc = L.wm_ssim_finalize(_p(part), B, C, H, W, _p(out), _stream())
-    _lib.check(rc, "wm_ssim_finalize")
+    _timed("ssim_fwd", None, lambda: L.wm_ssim_fwd(_p(a), _p(b), B, C, H, W, ssim_window(), _p(part), _p(dpl), _stream()))
+    L.wm_ssim_finalize(_p(part), B, C, H, W, _p(out), _stream())
     val = out[0] if size_average else out[1:]
     return (val, dpl) if want_grad else val
 
@@ -2250,9 +2117,8 @@ def ssim_bwd(dplanes, a, b, gout=None, per_image=False, gscale=1.0, gscale_dev=N
     B, C, H, W = a.shape
     assert dplanes.shape == (3,) + tuple(a.shape) and dplanes.is_contiguous() and dplanes.dtype == torch.float32
     gout, out = _loss_bwd_args("ssim_bwd", a, gout, gscale_dev, out, accumulate, B if per_image else 1)
-    rc = _timed("ssim_bwd", None, lambda: _lib.lib().wm_ssim_bwd(_p(dplanes), _p(a), _p(b), _p(out), B, C, H, W, ssim_window(), _p(gout),
-                                                                 1 if per_image else 0, gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
-    _lib.check(rc, "wm_ssim_bwd")
+    _timed("ssim_bwd", None, lambda: _lib.checked().wm_ssim_bwd(_p(dplanes), _p(a), _p(b), _p(out), B, C, H, W, ssim_window(), _p(gout),
+                                                                1 if per_image else 0, gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
     _wrote(out)
     return out
 
@@ -2266,11 +2132,9 @@ def psnr(a, b, max_val):
     n = a.numel()
     part = torch.empty(_nparts(n), device=a.device, dtype=torch.float64)
     out = torch.empty(1, device=a.device, dtype=torch.float32)
-    L = _lib.lib()
-    rc = _timed("psnr", None, lambda: L.wm_psnr_partials(_p(a), _p(b), n, _p(part), part.numel(), _stream()))
-    _lib.check(rc, "wm_psnr_partials")
-    rc = L.wm_psnr_finalize(_p(part), part.numel(), float(n), float(max_val), _p(out), _stream())
-    _lib.check(rc, "wm_psnr_finalize")
+    L = _lib.checked()
+    _timed("psnr", None, lambda: L.wm_psnr_partials(_p(a), _p(b), n, _p(part), part.numel(), _stream()))
+    L.wm_psnr_finalize(_p(part), part.numel(), float(n), float(max_val), _p(out), _stream())
     return out
 
 
@@ -2286,12 +2150,11 @@ def confusion_counts(pred, gt, thr_pred, thr_gt):
     pred, gt = pred.contiguous(), gt.contiguous()
     B = pred.shape[0]
     per = pred.numel() // B
-    L = _lib.lib()
+    L = _lib.checked()
     part = torch.empty(B * L.wm_confusion_nparts(per) * 4, device=pred.device, dtype=torch.int64)
     out = torch.empty(1 + B, 4, device=pred.device, dtype=torch.int64)
-    rc = _timed("confusion_counts", None, lambda: L.wm_confusion_counts(_p(pred), int(pred.dtype == torch.uint8), _p(gt), int(gt.dtype == torch.uint8),
-                                                                        thr_pred, thr_gt, B, per, _p(part), _p(out), _stream()))
-    _lib.check(rc, "wm_confusion_counts")
+    _timed("confusion_counts", None, lambda: L.wm_confusion_counts(_p(pred), int(pred.dtype == torch.uint8), _p(gt), int(gt.dtype == torch.uint8),
+                                                                   thr_pred, thr_gt, B, per, _p(part), _p(out), _stream()))
     return out
 
 
@@ -2299,8 +2162,7 @@ def scale_dev_(x, scale_dev):
     """x *= scale_dev[0] (a device scalar)"""
     _need_cuda(x, scale_dev)
     assert x.is_contiguous() and x.dtype == torch.float32 and scale_dev.dtype == torch.float32
-    rc = _lib.lib().wm_scale_dev(_p(x), x.numel(), _p(scale_dev), _stream())
-    _lib.check(rc, "wm_scale_dev")
+    _lib.checked().wm_scale_dev(_p(x), x.numel(), _p(scale_dev), _stream())
     _wrote(x)
     return x
 
@@ -2318,6 +2180,16 @@ def _loss_bwd_args(name, x, gout, gscale_dev, out, accumulate, n_gout=1, same_sh
         out = torch.empty_like(x)
     assert (out.shape == x.shape if same_shape else out.numel() == x.numel()) and out.is_contiguous() and out.dtype == torch.float32
     return gout, out
+
+
+def _loss_bwd_args2(name, xs, want, out, gout, gscale_dev, accumulate):
+    """_loss_bwd_args of a loss with two inputs xs: (gout contiguous, [the gradient buffer of each side that want names, None for the other])"""
+    g = []
+    for x, w, o in zip(xs, want, out):
+        if w:
+            gout, o = _loss_bwd_args(name, x, gout, gscale_dev, o, accumulate)
+        g.append(o if w else None)
+    return gout, g
 
 
 # ----------------------------------------------------------------------------- Dice loss (csrc/dice.hip)
@@ -2341,9 +2213,8 @@ def _dice_pair(name, a, b):
 def _dice_finalize(L, part, B, C, per, smooth, red, ignore_index, weight, device):
     coef = torch.empty(B * C, 2, device=device, dtype=torch.float64)
     loss = torch.empty(B if red == DICE_REDUCTIONS["none"] else 1, device=device, dtype=torch.float32)
-    rc = L.wm_dice_finalize(_p(part), B, C, per, float(smooth), red, -1 if ignore_index is None else int(ignore_index), _p(weight), _p(coef),
-                            _p(loss), _stream())
-    _lib.check(rc, "wm_dice_finalize")
+    L.wm_dice_finalize(_p(part), B, C, per, float(smooth), red, -1 if ignore_index is None else int(ignore_index), _p(weight), _p(coef),
+                       _p(loss), _stream())
     return loss, coef
 
 
@@ -2356,10 +2227,9 @@ def dice_binary_fwd(p, target, smooth=1.0, pw=2.0, reduction="mean"):
     if B == 0 or p.numel() != target.numel() or p.numel() == 0:
         raise ValueError("dice_binary: two non-empty tensors of one size expected")
     per = p.numel() // B
-    L = _lib.lib()
+    L = _lib.checked()
     part = torch.empty(B * L.wm_dice_nparts(per) * 3, device=p.device, dtype=torch.float64)
-    rc = _timed("dice_sums", None, lambda: L.wm_dice_sums(_p(p), _p(target), B, per, float(pw), _p(part), _stream()))
-    _lib.check(rc, "wm_dice_sums")
+    _timed("dice_sums", None, lambda: L.wm_dice_sums(_p(p), _p(target), B, per, float(pw), _p(part), _stream()))
     return _dice_finalize(L, part, B, 1, per, smooth, red, None, None, p.device)
 
 
@@ -2372,9 +2242,8 @@ def dice_binary_bwd(p, target, coef, pw=2.0, reduction="mean", gout=None, gscale
     p, target = _dice_pair("dice_binary_bwd", p, target)
     B = p.shape[0]
     gout, out = _loss_bwd_args("dice_binary_bwd", p, gout, gscale_dev, out, accumulate, B if red == DICE_REDUCTIONS["none"] else 1, same_shape=False)
-    rc = _timed("dice_bwd", None, lambda: _lib.lib().wm_dice_bwd(_p(p), _p(target), _p(coef), _p(out), B, p.numel() // B, float(pw), red, _p(gout),
-                                                                 gscale, _p(gscale_dev), 1 if chain_sigmoid else 0, 1 if accumulate else 0, _stream()))
-    _lib.check(rc, "wm_dice_bwd")
+    _timed("dice_bwd", None, lambda: _lib.checked().wm_dice_bwd(_p(p), _p(target), _p(coef), _p(out), B, p.numel() // B, float(pw), red, _p(gout),
+                                                                gscale, _p(gscale_dev), 1 if chain_sigmoid else 0, 1 if accumulate else 0, _stream()))
     _wrote(out)
     return out
 
@@ -2405,10 +2274,9 @@ def dice_softmax_fwd(logits, target, smooth=1.0, pw=2.0, reduction="mean", ignor
     (loss, coef [B*C,2] float64).  The softmax over the classes is formed inside the kernel and never written"""
     red = _dice_reduction(reduction)
     logits, target, weight, B, C, HW = _dice_softmax_args(logits, target, weight)
-    L = _lib.lib()
+    L = _lib.checked()
     part = torch.empty(B * C * L.wm_dice_nparts(HW) * 3, device=logits.device, dtype=torch.float64)
-    rc = _timed("dice_softmax_sums", None, lambda: L.wm_dice_softmax_sums(_p(logits), _p(target), B, C, HW, float(pw), _p(part), _stream()))
-    _lib.check(rc, "wm_dice_softmax_sums")
+    _timed("dice_softmax_sums", None, lambda: L.wm_dice_softmax_sums(_p(logits), _p(target), B, C, HW, float(pw), _p(part), _stream()))
     return _dice_finalize(L, part, B, C, HW, smooth, red, ignore_index, weight, logits.device)
 
 
@@ -2418,10 +2286,9 @@ def dice_softmax_bwd(logits, target, coef, pw=2.0, reduction="mean", ignore_inde
     red = _dice_reduction(reduction)
     logits, target, weight, B, C, HW = _dice_softmax_args(logits, target, weight)
     gout, out = _loss_bwd_args("dice_softmax_bwd", logits, gout, gscale_dev, out, accumulate, B if red == DICE_REDUCTIONS["none"] else 1, same_shape=False)
-    rc = _timed("dice_softmax_bwd", None, lambda: _lib.lib().wm_dice_softmax_bwd(
+    _timed("dice_softmax_bwd", None, lambda: _lib.checked().wm_dice_softmax_bwd(
         _p(logits), _p(target), _p(coef), _p(out), B, C, HW, float(pw), red, -1 if ignore_index is None else int(ignore_index), _p(weight), _p(gout),
         gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
-    _lib.check(rc, "wm_dice_softmax_bwd")
     _wrote(out)
     return out
 
@@ -2459,13 +2326,11 @@ def recon_loss_fwd(x, t, kind="l_char", eps=1e-6):
     """ReconstructionLoss(eps=eps)(x, t, kind): mean over the batch of the per-sample SUM of f(x - t), f = d^2 (l2), sqrt(d^2 + eps)
     (l_char) or d (l1: the reference's signed sum, without abs) -> a [1] device tensor.  Two launches, no host sync"""
     B, per, k = _recon_args("recon_loss", x, t, kind)
-    L = _lib.lib()
+    L = _lib.checked()
     part = torch.empty(B * L.wm_recon_nparts(per), device=x.device, dtype=torch.float64)
     loss = torch.empty(1, device=x.device, dtype=torch.float32)
-    rc = _timed("recon_sums", None, lambda: L.wm_recon_sums(_p(x), _p(t), B, per, k, float(eps), _p(part), _stream()))
-    _lib.check(rc, "wm_recon_sums")
-    rc = L.wm_recon_finalize(_p(part), B, per, _p(loss), _stream())
-    _lib.check(rc, "wm_recon_finalize")
+    _timed("recon_sums", None, lambda: L.wm_recon_sums(_p(x), _p(t), B, per, k, float(eps), _p(part), _stream()))
+    L.wm_recon_finalize(_p(part), B, per, _p(loss), _stream())
     return loss
 
 
@@ -2474,9 +2339,8 @@ def recon_loss_bwd(x, t, kind="l_char", eps=1e-6, gout=None, gscale=1.0, gscale_
     write, or with accumulate to add into (one launch, no axpy)"""
     B, per, k = _recon_args("recon_loss_bwd", x, t, kind)
     gout, out = _loss_bwd_args("recon_loss_bwd", x, gout, gscale_dev, out, accumulate)
-    rc = _timed("recon_bwd", None, lambda: _lib.lib().wm_recon_bwd(_p(x), _p(t), _p(out), B, per, k, float(eps), _p(gout), gscale, _p(gscale_dev),
-                                                                   1 if accumulate else 0, _stream()))
-    _lib.check(rc, "wm_recon_bwd")
+    _timed("recon_bwd", None, lambda: _lib.checked().wm_recon_bwd(_p(x), _p(t), _p(out), B, per, k, float(eps), _p(gout), gscale, _p(gscale_dev),
+                                                                  1 if accumulate else 0, _stream()))
     _wrote(out)
     return out
 
@@ -2500,13 +2364,11 @@ def _gradloss_args(name, a):
 def gradient_loss(a):
     """GradientLoss()(a): mean |a[..., :-1] - a[..., 1:]| + mean |a[..., :-1, :] - a[..., 1:, :]| -> a [1] device tensor; H, W >= 2"""
     N, H, W = _gradloss_args("gradient_loss", a)
-    L = _lib.lib()
+    L = _lib.checked()
     part = torch.empty(N * max(1, L.wm_gradloss_nparts(H, W)) * 2, device=a.device, dtype=torch.float64)
     loss = torch.empty(1, device=a.device, dtype=torch.float32)
-    rc = _timed("gradloss_sums", None, lambda: L.wm_gradloss_sums(_p(a), N, H, W, _p(part), _stream()))
-    _lib.check(rc, "wm_gradloss_sums")
-    rc = L.wm_gradloss_finalize(_p(part), N, H, W, _p(loss), _stream())
-    _lib.check(rc, "wm_gradloss_finalize")
+    _timed("gradloss_sums", None, lambda: L.wm_gradloss_sums(_p(a), N, H, W, _p(part), _stream()))
+    L.wm_gradloss_finalize(_p(part), N, H, W, _p(loss), _stream())
     return loss
 
 
@@ -2514,9 +2376,8 @@ def gradient_loss_bwd(a, gout=None, gscale=1.0, gscale_dev=None, out=None, accum
     """gradient wrt a of gscale * gscale_dev[0] * gout[0] * gradient_loss(a); the subgradient of |.| at 0 is 0, as torch's"""
     N, H, W = _gradloss_args("gradient_loss_bwd", a)
     gout, out = _loss_bwd_args("gradient_loss_bwd", a, gout, gscale_dev, out, accumulate)
-    rc = _timed("gradloss_bwd", None, lambda: _lib.lib().wm_gradloss_bwd(_p(a), _p(out), N, H, W, _p(gout), gscale, _p(gscale_dev),
-                                                                         1 if accumulate else 0, _stream()))
-    _lib.check(rc, "wm_gradloss_bwd")
+    _timed("gradloss_bwd", None, lambda: _lib.checked().wm_gradloss_bwd(_p(a), _p(out), N, H, W, _p(gout), gscale, _p(gscale_dev),
+                                                                        1 if accumulate else 0, _stream()))
     _wrote(out)
     return out
 
@@ -2533,16 +2394,14 @@ def exclusion_fwd(img1, img2, level=3):
     means[l, d, i2*C1 + i1] = mean of s1^2 s2^2 over level l's differences in direction d (0 = gradx, 1 = grady) of img1's channel i1 and
     img2's i2.  1 <= level <= 3, 1 <= C1, C2 <= 4, H and W >= 2 << (level - 1) (the library refuses anything else).  Two launches, no host sync"""
     B, C1, C2, H, W, level = _excl_args("exclusion", img1, img2, level)
-    L = _lib.lib()
+    L = _lib.checked()
     n = max(1, level) * 2 * C1 * C2
     part = torch.empty(n * max(1, L.wm_excl_nparts(B, H, W)), device=img1.device, dtype=torch.float64)
-    rc = _timed("excl_fwd", None, lambda: L.wm_excl_fwd(_p(img1), _p(img2), B, C1, C2, H, W, level, _p(part), _stream()))
-    _lib.check(rc, "wm_excl_fwd")
+    _timed("excl_fwd", None, lambda: L.wm_excl_fwd(_p(img1), _p(img2), B, C1, C2, H, W, level, _p(part), _stream()))
     means = torch.empty(level, 2, C1 * C2, device=img1.device, dtype=torch.float64)
     coef = torch.empty_like(means)
     loss = torch.empty(1, device=img1.device, dtype=torch.float32)
-    rc = L.wm_excl_finalize(_p(part), B, C1, C2, H, W, level, _p(means), _p(coef), _p(loss), _stream())
-    _lib.check(rc, "wm_excl_finalize")
+    L.wm_excl_finalize(_p(part), B, C1, C2, H, W, level, _p(means), _p(coef), _p(loss), _stream())
     return loss, means, coef
 
 
@@ -2561,14 +2420,9 @@ def exclusion_bwd(img1, img2, coef, level=3, want=(True, True), gout=None, gscal
         return None, None
     _need_cuda(coef)
     assert coef.dtype == torch.float64 and coef.is_contiguous() and coef.numel() == level * 2 * C1 * C2
-    g = []
-    for x, w, o in zip((img1, img2), want, out):
-        if w:
-            gout, o = _loss_bwd_args("exclusion_bwd", x, gout, gscale_dev, o, accumulate)
-        g.append(o if w else None)
-    rc = _timed("excl_bwd", None, lambda: _lib.lib().wm_excl_bwd(_p(img1), _p(img2), _p(coef), _p(g[0]), _p(g[1]), B, C1, C2, H, W, level, _p(gout),
-                                                                 gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
-    _lib.check(rc, "wm_excl_bwd")
+    gout, g = _loss_bwd_args2("exclusion_bwd", (img1, img2), want, out, gout, gscale_dev, accumulate)
+    _timed("excl_bwd", None, lambda: _lib.checked().wm_excl_bwd(_p(img1), _p(img2), _p(coef), _p(g[0]), _p(g[1]), B, C1, C2, H, W, level, _p(gout),
+                                                                gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
     _wrote(*g)
     return g[0], g[1]
 
@@ -2587,8 +2441,7 @@ def ssim3_map_fwd(x, y):
     """SSIM_Loss()(x, y): the [B,C,H,W] map clamp((1 - SSIM_n / SSIM_d) / 2, 0, 1) from reflect-padded 3 x 3 box statistics.  One launch"""
     N, H, W = _ssim3_args("ssim3_map_fwd", x, y)
     out = torch.empty_like(x)
-    rc = _timed("ssim3_fwd", None, lambda: _lib.lib().wm_ssim3_fwd(_p(x), _p(y), _p(out), None, N, H, W, _stream()))
-    _lib.check(rc, "wm_ssim3_fwd")
+    _timed("ssim3_fwd", None, lambda: _lib.checked().wm_ssim3_fwd(_p(x), _p(y), _p(out), None, N, H, W, _stream()))
     return out
 
 
@@ -2596,14 +2449,9 @@ def _ssim3_bwd(name, x, y, g, want, gout, gscale, gscale_dev, out, accumulate):
     N, H, W = _ssim3_args(name, x, y)
     if not (want[0] or want[1]):
         return None, None
-    res = []
-    for t, w, o in zip((x, y), want, out):
-        if w:
-            gout, o = _loss_bwd_args(name, t, gout, gscale_dev, o, accumulate)
-        res.append(o if w else None)
-    rc = _timed("ssim3_bwd", None, lambda: _lib.lib().wm_ssim3_bwd(_p(x), _p(y), _p(g), _p(res[0]), _p(res[1]), N, H, W, _p(gout), gscale,
-                                                                   _p(gscale_dev), 1 if accumulate else 0, _stream()))
-    _lib.check(rc, "wm_ssim3_bwd")
+    gout, res = _loss_bwd_args2(name, (x, y), want, out, gout, gscale_dev, accumulate)
+    _timed("ssim3_bwd", None, lambda: _lib.checked().wm_ssim3_bwd(_p(x), _p(y), _p(g), _p(res[0]), _p(res[1]), N, H, W, _p(gout), gscale,
+                                                                  _p(gscale_dev), 1 if accumulate else 0, _stream()))
     _wrote(*res)
     return res[0], res[1]
 
@@ -2620,13 +2468,11 @@ def ssim3_map_bwd(x, y, g, want=(True, True), gscale=1.0, gscale_dev=None, out=(
 def ssim3_mean_fwd(x, y):
     """mean(SSIM_Loss()(x, y)) -> a [1] device tensor; the map is never written.  Two launches, no host sync"""
     N, H, W = _ssim3_args("ssim3_mean", x, y)
-    L = _lib.lib()
+    L = _lib.checked()
     part = torch.empty(max(1, L.wm_ssim3_nparts(N, H, W)), device=x.device, dtype=torch.float64)
     loss = torch.empty(1, device=x.device, dtype=torch.float32)
-    rc = _timed("ssim3_fwd", None, lambda: L.wm_ssim3_fwd(_p(x), _p(y), None, _p(part), N, H, W, _stream()))
-    _lib.check(rc, "wm_ssim3_fwd")
-    rc = L.wm_ssim3_finalize(_p(part), N, H, W, _p(loss), _stream())
-    _lib.check(rc, "wm_ssim3_finalize")
+    _timed("ssim3_fwd", None, lambda: L.wm_ssim3_fwd(_p(x), _p(y), None, _p(part), N, H, W, _stream()))
+    L.wm_ssim3_finalize(_p(part), N, H, W, _p(loss), _stream())
     return loss
 
 
@@ -2652,15 +2498,13 @@ def _pixloss_fwd(name, kind, a, b=None, mask=None):
     _f32_cuda(name, a, b, mask)
     if a.numel() == 0 or any(t is not None and t.shape != a.shape for t in (b, mask)):
         raise ValueError(name + ": non-empty tensors of one shape expected")
-    L, n = _lib.lib(), a.numel()
+    L, n = _lib.checked(), a.numel()
     part = torch.empty(2 * L.wm_pixloss_nparts(n), device=a.device, dtype=torch.float64)
     coef = torch.empty(2, device=a.device, dtype=torch.float64)
     loss = torch.empty(1, device=a.device, dtype=torch.float32)
     k = PIXLOSS_KINDS[kind]
-    rc = _timed("pixloss_sums", None, lambda: L.wm_pixloss_sums(k, _p(a), _p(b), _p(mask), n, _p(part), _stream()))
-    _lib.check(rc, "wm_pixloss_sums")
-    rc = L.wm_pixloss_finalize(k, _p(part), n, _p(coef), _p(loss), _stream())
-    _lib.check(rc, "wm_pixloss_finalize")
+    _timed("pixloss_sums", None, lambda: L.wm_pixloss_sums(k, _p(a), _p(b), _p(mask), n, _p(part), _stream()))
+    L.wm_pixloss_finalize(k, _p(part), n, _p(coef), _p(loss), _stream())
     return loss, coef
 
 
@@ -2668,16 +2512,11 @@ def _pixloss_bwd(name, kind, a, b, mask, coef, want, gout, gscale, gscale_dev, a
     _f32_cuda(name, a, b, mask)
     _need_cuda(coef)
     assert coef.dtype == torch.float64 and coef.is_contiguous() and coef.numel() == 2
-    res = []
-    for w, o in zip(want, out):
-        if w:
-            gout, o = _loss_bwd_args(name, a, gout, gscale_dev, o, accumulate)
-        res.append(o if w else None)
+    gout, res = _loss_bwd_args2(name, (a, a), want, out, gout, gscale_dev, accumulate)
     if res[0] is None and res[1] is None:
         return None, None
-    rc = _timed("pixloss_bwd", None, lambda: _lib.lib().wm_pixloss_bwd(PIXLOSS_KINDS[kind], _p(a), _p(b), _p(mask), _p(coef), _p(res[0]), _p(res[1]),
-                                                                       a.numel(), _p(gout), gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
-    _lib.check(rc, "wm_pixloss_bwd")
+    _timed("pixloss_bwd", None, lambda: _lib.checked().wm_pixloss_bwd(PIXLOSS_KINDS[kind], _p(a), _p(b), _p(mask), _p(coef), _p(res[0]), _p(res[1]),
+                                                                      a.numel(), _p(gout), gscale, _p(gscale_dev), 1 if accumulate else 0, _stream()))
     _wrote(*res)
     return res[0], res[1]
 
@@ -2753,7 +2592,7 @@ def adv_loss(x, objective, label=None, mask=None, real_label=1.0, want_grad=Fals
     the mask resized to x's H x W bilinearly (align_corners=False, no antialiasing) -- sampled inside the loss kernel, never written.  No
     gradient flows to the mask: it is data"""
     obj, lab, dims = _adv_args("adv_loss", x, objective, label, mask)
-    L = _lib.lib()
+    L = _lib.checked()
     n = x.numel()
     part = torch.empty(L.wm_advloss_nparts(n), device=x.device, dtype=torch.float64)
     loss = torch.empty(1, device=x.device, dtype=torch.float32)
@@ -2762,11 +2601,9 @@ def adv_loss(x, objective, label=None, mask=None, real_label=1.0, want_grad=Fals
         gout, grad = _loss_bwd_args("adv_loss", x, gout, gscale_dev, grad_out, grad_out is not None)
     elif grad_out is not None or gout is not None:
         raise ValueError("adv_loss: grad_out / gout need want_grad=True")
-    rc = _timed("advloss_elem", None, lambda: L.wm_advloss_elem(obj, _p(x), n, lab, _p(mask), *dims, float(real_label), _p(part), _p(grad), _p(gout),
-                                                                float(gscale), _p(gscale_dev), 1 if grad_out is not None else 0, _stream()))
-    _lib.check(rc, "wm_advloss_elem")
-    rc = L.wm_advloss_finalize(_p(part), n, _p(loss), _stream())
-    _lib.check(rc, "wm_advloss_finalize")
+    _timed("advloss_elem", None, lambda: L.wm_advloss_elem(obj, _p(x), n, lab, _p(mask), *dims, float(real_label), _p(part), _p(grad), _p(gout),
+                                                           float(gscale), _p(gscale_dev), 1 if grad_out is not None else 0, _stream()))
+    L.wm_advloss_finalize(_p(part), n, _p(loss), _stream())
     if not want_grad:
         return loss
     _wrote(grad)
@@ -2790,7 +2627,7 @@ def cw_margin(logits, target, is_targeted, kappa=0.0, want_grad=False, gscale=1.
         raise TypeError("cw_margin: target must be a contiguous int64 tensor [B]")
     if check_target and bool(((target < 0) | (target >= K)).any()):
         raise ValueError("cw_margin: target outside [0, %d)" % K)
-    L = _lib.lib()
+    L = _lib.checked()
     terms = torch.empty(B, device=logits.device, dtype=torch.float64)
     loss = torch.empty(1, device=logits.device, dtype=torch.float32)
     grad = None
@@ -2798,10 +2635,9 @@ def cw_margin(logits, target, is_targeted, kappa=0.0, want_grad=False, gscale=1.
         gout, grad = _loss_bwd_args("cw_margin", logits, gout, gscale_dev, grad_out, grad_out is not None)
     elif grad_out is not None or gout is not None:
         raise ValueError("cw_margin: grad_out / gout need want_grad=True")
-    rc = _timed("cw_margin", None, lambda: L.wm_cw_margin(_p(logits), _p(target), B, K, 1 if is_targeted else 0, float(kappa), _p(terms), _p(loss),
-                                                          _p(grad), _p(gout), float(gscale), _p(gscale_dev), 1 if grad_out is not None else 0,
-                                                          _stream()))
-    _lib.check(rc, "wm_cw_margin")
+    _timed("cw_margin", None, lambda: L.wm_cw_margin(_p(logits), _p(target), B, K, 1 if is_targeted else 0, float(kappa), _p(terms), _p(loss),
+                                                     _p(grad), _p(gout), float(gscale), _p(gscale_dev), 1 if grad_out is not None else 0,
+                                                     _stream()))
     if not want_grad:
         return loss
     _wrote(grad)
@@ -2829,8 +2665,7 @@ def rng_fill(state, n, dist=RNG_UNIFORM):
     _need_cuda(state)
     assert state.dtype == torch.int64 and state.numel() >= 2
     out = torch.empty(int(n), device=state.device, dtype=torch.float32)
-    rc = _lib.lib().wm_rng_fill(_p(state), _p(out), int(n), dist, _stream())
-    _lib.check(rc, "wm_rng_fill")
+    _lib.checked().wm_rng_fill(_p(state), _p(out), int(n), dist, _stream())
     return out
 
 
@@ -2850,8 +2685,7 @@ def noise_fwd(op, x, a, b, state, cover=None):
         assert cover.shape == x.shape
     rec = _rng_args(x, state)
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_noise_fwd(op, _p(x), _p(cover), _p(y), x.numel(), a, b, _p(state), _p(rec), _stream())
-    _lib.check(rc, "wm_noise_fwd")
+    _lib.checked().wm_noise_fwd(op, _p(x), _p(cover), _p(y), x.numel(), a, b, _p(state), _p(rec), _stream())
     _wrote(state)
     return y, rec
 
@@ -2866,8 +2700,7 @@ def noise_bwd(op, g, a, b, rec, x=None, want_cover=False):
         x = x.contiguous().float()
     gx = torch.empty_like(g)
     gc = torch.empty_like(g) if want_cover and op == NOISE_DROP else None
-    rc = _lib.lib().wm_noise_bwd(op, _p(x), _p(g), _p(gx), _p(gc), g.numel(), a, b, _p(rec), _stream())
-    _lib.check(rc, "wm_noise_bwd")
+    _lib.checked().wm_noise_bwd(op, _p(x), _p(g), _p(gx), _p(gc), g.numel(), a, b, _p(rec), _stream())
     return gx, gc
 
 
@@ -2879,8 +2712,7 @@ def dropout_fwd(x, cover, keep_min, keep_span, state):
     assert cover.shape == x.shape
     rec = _rng_args(x, state)
     y = torch.empty_like(x)
-    rc = _lib.lib().wm_dropout_fwd(_p(x), _p(cover), _p(y), N, H, W, keep_min, keep_span, _p(state), _p(rec), _stream())
-    _lib.check(rc, "wm_dropout_fwd")
+    _lib.checked().wm_dropout_fwd(_p(x), _p(cover), _p(y), N, H, W, keep_min, keep_span, _p(state), _p(rec), _stream())
     _wrote(state)
     return y, rec
 
@@ -2889,8 +2721,7 @@ def dropout_bwd(g, keep_min, keep_span, rec, want_cover=False):
     g, N, H, W = _planes(g)
     gx = torch.empty_like(g)
     gc = torch.empty_like(g) if want_cover else None
-    rc = _lib.lib().wm_dropout_bwd(_p(g), _p(gx), _p(gc), N, H, W, keep_min, keep_span, _p(rec), _stream())
-    _lib.check(rc, "wm_dropout_bwd")
+    _lib.checked().wm_dropout_bwd(_p(g), _p(gx), _p(gc), N, H, W, keep_min, keep_span, _p(rec), _stream())
     return gx, gc
 
 
@@ -2900,8 +2731,7 @@ def _jpeg_drop(name, x, keep):
     x = x.contiguous().float()
     y = torch.empty_like(x)
     k = _host_ints(keep)
-    rc = getattr(_lib.lib(), name)(_p(x), _p(y), x.shape[0], x.shape[2], x.shape[3], k, _stream())
-    _lib.check(rc, name)
+    getattr(_lib.checked(), name)(_p(x), _p(y), x.shape[0], x.shape[2], x.shape[3], k, _stream())
     return y
 
 
