@@ -16,6 +16,22 @@
 // zero-padded convolution with a symmetric window is the same convolution), horizontal then vertical pass, and
 //   grad = g * (w*Dp + 2x . w*Dq + y . w*Dr)
 // with g the upstream weight of the pixel's image (constant per image, so it multiplies after the convolution).  44,928 B of LDS.
+//
+// The float32 arithmetic, operation by operation (what tests/ssim_exact.py counts its roundings from; a compiler may contract a product
+// and the sum after it into one fma, which only removes a rounding):
+//   window sums   x^2, y^2, xy: one product each, before the window.  A window sum is 11 fmas along the row (taps in ascending order, from
+//                 0) and 11 fmas down the column over those row sums: 22 roundings, the same chain for every pixel wherever its tile lies.
+//   S             pm = p m, pp = p p, mm = m m; s1 = q - pp, s2 = q2 - mm, s12 = r - pm; A1 = 2 pm + C1, A2 = 2 s12 + C2 (times 2 is exact;
+//                 C1, C2 the float32 of 0.01^2, 0.03^2); B1 = (pp + mm) + C1, B2 = (s1 + s2) + C2; S = (A1 A2) / (B1 B2).
+//   planes        inv = 1 / (B1 B2), i1 = 1 / B1, i2 = 1 / B2 (three correctly rounded reciprocals);
+//                 dS/dp = ((2 m) (A2 - A1)) inv - ((2 p) S) (i1 - i2);  dS/dq = -(S i2);  dS/dr = (2 A1) inv.
+//   values        S is added to a double per thread; workgroup partials and the finalise stay in double; one division by the count and one
+//                 rounding to float32 per value.
+//   gradient      each plane's window sum as above (22); g = float32(gscale / (C H W [B])) formed in double on the host, then times
+//                 gscale_dev[0], then times gout[b] (one rounding each that is present);
+//                 v = g ((a0 + (2 x) a1) + y a2); accumulate: grad + v.
+//   PSNR          d = a - b in float32; d d and every sum in double; mse = float32(sum / n);
+//                 (20 logf(max_val)) / logf(10) - (10 logf(mse)) / logf(10).
 #include "wm_common.h"
 #include "wm_reduce.h"
 
