@@ -247,10 +247,10 @@ def test_host_step_logic_without_a_gpu():
 
 
 def test_flat_adam_state_interchanges_with_torch_optim_adam():
-    """training-state files (base_model.py:129-150 of the reference hold torch.optim.Adam state_dicts): _FlatAdam emits and accepts
+    """training-state files (base_model.py:129-150 of the reference hold torch.optim.Adam state_dicts): FlatAdam emits and accepts
     that layout -- per-parameter {step, exp_avg, exp_avg_sq} in parameters() order, one param group -- and still reads round 1's flat one"""
     from video_watermarking_forgery_detection_amd.hidden_models import Decoder, Discriminator
-    from video_watermarking_forgery_detection_amd.hidden_models.hidden import _FlatAdam
+    from video_watermarking_forgery_detection_amd.optim import FlatAdam
     from video_watermarking_forgery_detection_amd.options import HiDDenConfiguration
     cfg = HiDDenConfiguration(H=16, W=16)
     torch.manual_seed(0)
@@ -264,7 +264,7 @@ def test_flat_adam_state_interchanges_with_torch_optim_adam():
             p.grad = torch.randn_like(p)
         topt.step()
     sd = topt.state_dict()
-    flat = _FlatAdam(nets)
+    flat = FlatAdam(nets)
     flat.load_state_dict(sd)
     assert flat.step_count == 3 and flat.param_groups[0]["lr"] == 2e-3 and tuple(flat.param_groups[0]["betas"]) == (0.8, 0.99)
     assert flat.param_groups[0]["weight_decay"] == 0.01
@@ -285,11 +285,11 @@ def test_flat_adam_state_interchanges_with_torch_optim_adam():
         assert float(back["state"][i]["step"]) == 3.0
     # a state with a different parameter list is refused, not silently truncated
     with pytest.raises(ValueError):
-        _FlatAdam(nets[:1]).load_state_dict(sd)
+        FlatAdam(nets[:1]).load_state_dict(sd)
     # round 1's flat layout is still readable
     legacy = {"step": 5, "param_groups": [{"lr": 1e-4, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.0}],
               "exp_avg": [t.clone() for t in flat._m], "exp_avg_sq": [t.clone() for t in flat._v]}
-    f2 = _FlatAdam(nets)
+    f2 = FlatAdam(nets)
     f2.load_state_dict(legacy)
     assert f2.step_count == 5 and f2.param_groups[0]["lr"] == 1e-4 and torch.equal(f2._m[1], flat._m[1])
 
@@ -299,7 +299,7 @@ def test_flat_adam_refuses_torch_state_of_an_adam_variant_it_does_not_run(varian
     """a torch.optim.Adam state_dict with amsgrad=True (which carries max_exp_avg_sq) or maximize=True is refused: continuing it as plain
     Adam would silently change the optimiser"""
     from video_watermarking_forgery_detection_amd.hidden_models import Discriminator
-    from video_watermarking_forgery_detection_amd.hidden_models.hidden import _FlatAdam
+    from video_watermarking_forgery_detection_amd.optim import FlatAdam
     from video_watermarking_forgery_detection_amd.options import HiDDenConfiguration
     torch.manual_seed(1)
     net = Discriminator(HiDDenConfiguration(H=16, W=16))
@@ -310,7 +310,7 @@ def test_flat_adam_refuses_torch_state_of_an_adam_variant_it_does_not_run(varian
         p.grad = torch.randn_like(p)
     topt.step()
     sd = topt.state_dict()
-    flat = _FlatAdam([net])
+    flat = FlatAdam([net])
     with pytest.raises(ValueError, match=variant):
         flat.load_state_dict(sd)
     assert flat.step_count == 0 and flat.param_groups[0]["lr"] == 1e-3

@@ -98,6 +98,36 @@ def test_flat_adamw_against_torch():
         G.FlatAdamW(nn.Linear(2, 2), 1e-3)           # parameters on the CPU
 
 
+def test_flat_adamw_is_flat_adam_over_one_flat_parameters():
+    """FlatAdamW(net) and optim.FlatAdam([FlatParameters(net2)], decoupled=True) from equal weights on equal inputs: the same launches, so
+    parameters and both moment buffers agree bit for bit; and what FlatAdamW.state_dict writes loads into a FlatAdam exactly"""
+    from video_watermarking_forgery_detection_amd import glayers as G
+    from video_watermarking_forgery_detection_amd.optim import FlatAdam, FlatParameters
+    torch.manual_seed(0)
+    net = nn.Sequential(nn.Linear(13, 7), nn.Linear(7, 3)).to(DEV)
+    net2 = nn.Sequential(nn.Linear(13, 7), nn.Linear(7, 3))
+    net2.load_state_dict(net.state_dict())
+    net2.to(DEV)
+    hyper = dict(lr=1e-2, betas=(0.8, 0.95), weight_decay=0.05)
+    a = G.FlatAdamW(net, **hyper)
+    fp = FlatParameters(net2)
+    b = FlatAdam([fp], decoupled=True, **hyper)
+    for it in range(3):
+        x = detgen.normal((5, 13), 20 + it).to(DEV)
+        a.zero_grad(); b.zero_grad()
+        (net(x) ** 2).sum().backward()
+        (net2(x) ** 2).sum().backward()
+        a.step(); b.step()
+        assert torch.equal(a.flat, fp.flat_params) and torch.equal(a._m[0], b._m[0]) and torch.equal(a._v[0], b._v[0]), it
+    assert int(torch.count_nonzero(a._m[0])) > 0 and a.step_count == b.step_count == 3
+    sd = a.state_dict()
+    assert torch.is_tensor(sd["exp_avg"]) and sd["step"] == 3                 # FlatAdamW's own layout: single flat tensors
+    c = FlatAdam([FlatParameters(nn.Sequential(nn.Linear(13, 7), nn.Linear(7, 3)).to(DEV))], decoupled=True)
+    c.load_state_dict(sd)
+    assert c.step_count == 3 and c.param_groups[0] == a.param_groups[0]
+    assert torch.equal(c._m[0], a._m[0]) and torch.equal(c._v[0], a._v[0])
+
+
 def test_literal_step_against_the_cpu_composition():
     from video_watermarking_forgery_detection_amd.models.IRNrhi_literal import IRNrhiLiteralModel
     torch.manual_seed(1)

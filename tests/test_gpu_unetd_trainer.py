@@ -1,7 +1,7 @@
 """UNetDiscriminator as the trained tamper localiser (train.localizer_arch: unetd; models/IRNrhi_model.py).
 
   * Two training steps of the model's own localiser-step code (unetd_localiser_step: forward, BCEWithLogits on the sigmoid output, backward
-    into the flat gradient buffer, _FlatAdam) against tests/golden/unetd_step.npz -- the REFERENCE's UNetDiscriminator under
+    into the flat gradient buffer, FlatAdam) against tests/golden/unetd_step.npz -- the REFERENCE's UNetDiscriminator under
     nn.BCEWithLogitsLoss and torch.optim.Adam in float64 (tests/golden/make_golden_unetd_step.py).  Bound per quantity: MARGIN = 4 x the
     reference's own float32-vs-float64 deviation of that quantity, stored by the generator, at least 2 float32 ulp of its largest |value|
     (tests/unetd_restate.py); never calibrated on the device.  Step 2 catches a wrong Adam hook-up (moments, step count) and a lost u / v.
@@ -38,10 +38,10 @@ def _mod():
 def make_trainee(dtype=torch.float32, fused=True, lr=S.LR):
     """(net, flat, optimizer) built the way IRNrhiModel builds them, with the fixture's parameters"""
     from video_watermarking_forgery_detection_amd import glayers as G
-    from video_watermarking_forgery_detection_amd.hidden_models.hidden import _FlatAdam
+    from video_watermarking_forgery_detection_amd.optim import FlatAdam
     net = R.fill_net(_mod().build_unetd_localizer("cpu", dtype, 16, fused), S.NAME).to(DEV).train()
     flat = G.FlatParameters(net)
-    return net, flat, _FlatAdam([flat], lr=lr)
+    return net, flat, FlatAdam([flat], lr=lr)
 
 
 def two_steps(fused=True, sync=None, x=None, steps=2):

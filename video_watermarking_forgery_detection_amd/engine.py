@@ -21,6 +21,7 @@ import types
 import torch
 
 from . import ops
+from .optim import flatten_parameters
 
 
 class Act:
@@ -378,16 +379,7 @@ class FlatModule:
                 off += p.numel()
         if ok:
             return
-        flat = torch.empty(n, device=dev, dtype=torch.float32)
-        gflat = torch.zeros(n, device=dev, dtype=torch.float32)
-        off = 0
-        for p in params:
-            k = p.numel()
-            v = flat[off:off + k].view_as(p)
-            v.copy_(p.data)
-            p.data = v
-            p.grad = gflat[off:off + k].view_as(p)
-            off += k
+        flat, gflat = flatten_parameters(params)
         object.__setattr__(self, "_flat", flat)
         object.__setattr__(self, "_gflat", gflat)
         if not getattr(self, "_wm_load_hook", False):

@@ -10,13 +10,12 @@ through `to_nhwc` / `to_nchw`.  There is no CPU or PyTorch fallback: every Funct
 """
 import math
 
-import weakref
-
 import torch
 import torch.nn as nn
 from torch.autograd import Function
 
 from . import ops
+from .optim import CapturedStep, FlatAdam, FlatParameters, _flat_grad   # noqa: F401 -- (G.CapturedStep, G.FlatParameters: re-exported)
 
 cpad = ops.cpad
 
@@ -32,21 +31,6 @@ def _pad_bias(bias, n):
 
 
 _PLAN = None
-_FLAT_GRADS = {}      # parameter data_ptr -> (weakref flat parameters, weakref flat gradients, offset, numel) of a live FlatAdamW
-
-
-def _flat_grad(ptr, numel):
-    """the slice of a live FlatAdamW's gradient buffer that belongs to the parameter at address `ptr` (None if there is none: the
-    optimiser was collected -- its addresses may have been reused -- or the tensor is not a parameter of one)"""
-    e = _FLAT_GRADS.get(ptr)
-    if e is None:
-        return None
-    flat, grad = e[0](), e[1]()
-    if flat is None or grad is None or e[3] != numel or flat.data_ptr() + 4 * e[2] != ptr:
-        if flat is None or grad is None:
-            del _FLAT_GRADS[ptr]
-        return None
-    return grad[e[2]:e[2] + e[3]]
 
 
 def set_pack_plan(plan):
@@ -985,84 +969,31 @@ def clamp01(x):
     return _Clamp01Fn.apply(x)
 
 
-class FlatParameters:
-    """The trainable parameters of an nn.Module of this toolkit in ONE flat f32 buffer (`flat_params`; each nn.Parameter becomes a view of
-    it) with their gradients in a second (`flat_grads`; each .grad a view of it, autograd accumulates in place), registered so that the
-    convolution backward kernels ADD a parameter's gradient straight into the buffer (_flat_grad).  Frozen parameters (requires_grad False:
-    UNetDiscriminator's SRMConv2D.weight) stay where they are.  `flat_params`, `flat_grads` and parameters() are what the flat optimisers
-    (FlatAdamW here, hidden_models.hidden._FlatAdam), gradient clipping and distributed.GradSync drive; zero_grad() is one memset."""
-
-    def __init__(self, module, who="FlatParameters"):
-        ps = [p for p in module.parameters() if p.requires_grad]
-        if not ps or not all(p.is_cuda and p.dtype == torch.float32 for p in ps):
-            raise RuntimeError(f"{who}: parameters must be float32 CUDA tensors (move the module to the GPU first)")
-        n = sum(p.numel() for p in ps)
-        dev = ps[0].device
-        self.module = module
-        self.flat_params = torch.empty(n, device=dev, dtype=torch.float32)
-        self.flat_grads = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.params, o = ps, 0
-        with torch.no_grad():
-            for p in ps:
-                k = p.numel()
-                self.flat_params[o:o + k].copy_(p.detach().reshape(-1))
-                p.data = self.flat_params[o:o + k].view(p.shape)
-                p.grad = self.flat_grads[o:o + k].view(p.shape)
-                _FLAT_GRADS[p.data_ptr()] = (weakref.ref(self.flat_params), weakref.ref(self.flat_grads), o, k)
-                o += k
-
-    def parameters(self):
-        return iter(self.params)
-
-    def zero_grad(self):
-        self.flat_grads.zero_()
-
-
-class FlatAdamW:
-    """torch.optim.AdamW over ONE flat f32 buffer holding every trainable parameter of `module` (each nn.Parameter becomes a view of
-    it, each .grad a view of a flat gradient buffer autograd accumulates into): zero_grad = one memset, clip_grad_norm_ = one norm,
-    step = one launch of the library's Adam kernel with decoupled weight decay.  While the optimiser lives, the convolution backward
-    kernels ADD a registered parameter's gradient straight into the flat buffer and hand autograd None for it (_conv_backward): use
-    loss.backward(); torch.autograd.grad(loss, parameters) would see None for those parameters and still change the buffer."""
+class FlatAdamW(FlatAdam):
+    """torch.optim.AdamW over ONE flat f32 buffer holding every trainable parameter of `module` (optim.FlatAdam, decoupled, over one
+    FlatParameters: each nn.Parameter becomes a view of the buffer, each .grad a view of a flat gradient buffer autograd accumulates into):
+    zero_grad = one memset, clip_grad_norm_ = one norm, step = one launch of the library's Adam kernel.  While the optimiser lives, the
+    convolution backward kernels ADD a registered parameter's gradient straight into the flat buffer and hand autograd None for it
+    (_conv_backward): use loss.backward(); torch.autograd.grad(loss, parameters) would see None for those and still change the buffer."""
 
     def __init__(self, module, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
-        fp = FlatParameters(module, "FlatAdamW")
-        self.flat, self.grad, self.params = fp.flat_params, fp.flat_grads, fp.params
-        n, dev = self.flat.numel(), self.flat.device
-        self.m = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.v = torch.zeros(n, device=dev, dtype=torch.float32)
-        # one param group, torch's keys: what BaseModel's learning-rate handling and the schedulers (models/lr_scheduler.py) read and write
-        self.param_groups = [{"lr": lr, "initial_lr": lr, "betas": betas, "eps": eps, "weight_decay": weight_decay}]
-        self.t = 0
+        super().__init__([FlatParameters(module, "FlatAdamW")], lr, betas, eps, weight_decay, decoupled=True)
+        self._ensure()   # the moments now: this optimiser steps OUTSIDE a CapturedStep, and its first step may follow the capture
 
-    lr = property(lambda self: self.param_groups[0]["lr"], lambda self, x: self.param_groups[0].__setitem__("lr", x))
-    betas = property(lambda self: self.param_groups[0]["betas"], lambda self, x: self.param_groups[0].__setitem__("betas", x))
-    eps = property(lambda self: self.param_groups[0]["eps"], lambda self, x: self.param_groups[0].__setitem__("eps", x))
-    weight_decay = property(lambda self: self.param_groups[0]["weight_decay"], lambda self, x: self.param_groups[0].__setitem__("weight_decay", x))
-
-    def reset_state(self):
-        """AdamW from the start again (zero moments, step 0): a scheduler's restart with clear_state.  Two memsets in stream order."""
-        self.m.zero_()
-        self.v.zero_()
-        self.t = 0
+    flat = property(lambda self: self.modules[0].flat_params)
+    grad = property(lambda self: self.modules[0].flat_grads)
 
     def state_dict(self):
-        """the training state BaseModel.save_training_state stores: step count, the param group, the two flat moment buffers (on the CPU)"""
-        return {"step": self.t, "param_groups": [dict(self.param_groups[0])], "exp_avg": self.m.detach().cpu().clone(),
-                "exp_avg_sq": self.v.detach().cpu().clone()}
-
-    def load_state_dict(self, sd):
-        if sd["exp_avg"].numel() != self.m.numel():
-            raise ValueError(f"optimizer state holds {sd['exp_avg'].numel()} values, the module has {self.m.numel()}")
-        self.t = int(sd["step"])
-        self.param_groups[0].update(sd["param_groups"][0])
-        self.m.copy_(sd["exp_avg"])
-        self.v.copy_(sd["exp_avg_sq"])
+        """the training state BaseModel.save_training_state stores: step count, the param group, the two flat moment buffers (on the CPU).
+        FlatAdam.load_state_dict reads it back"""
+        return {"step": self._steps(), "param_groups": [dict(self.param_groups[0])], "exp_avg": self._m[0].detach().cpu().clone(),
+                "exp_avg_sq": self._v[0].detach().cpu().clone()}
 
     def zero_grad(self):
-        self.grad.zero_()
-        for p in self.params:           # autograd may have replaced a view (first accumulation into a None grad)
-            if p.grad is None or p.grad.data_ptr() < self.grad.data_ptr() or p.grad.data_ptr() >= self.grad.data_ptr() + 4 * self.grad.numel():
+        g = self.grad
+        g.zero_()
+        for p in self.modules[0].params:           # autograd may have replaced a view (first accumulation into a None grad)
+            if p.grad is None or p.grad.data_ptr() < g.data_ptr() or p.grad.data_ptr() >= g.data_ptr() + 4 * g.numel():
                 raise RuntimeError("FlatAdamW: a parameter's .grad no longer views the flat gradient buffer (do not set grads to None)")
 
     def clip_grad_norm_(self, max_norm):
@@ -1070,76 +1001,6 @@ class FlatAdamW:
         return ops.clip_grad_norm_([self.grad], float(max_norm))
 
     def step(self):
-        self.t += 1
-        ops.adam_step(self.flat, self.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.t, decoupled=True)
+        super().step()
         if _PLAN is not None:
             _PLAN.refresh()        # every registered packed weight from the new values, one launch
-
-
-class CapturedStep:
-    """A launch-bound step (the invertible embedder issues ~20,000 kernels of 3-20 us per forward + reverse + backward) captured ONCE into a
-    hipGraph and replayed: `fn()` must be shape-static, read its inputs from tensors that are updated in place (copy_), and not synchronise
-    with the host (no .item() / float()).  Gradients land in the parameters' existing .grad tensors (FlatAdamW's flat buffer), so
-    zero_grad belongs INSIDE fn and the optimiser step -- whose bias correction depends on the host's step count -- outside:
-
-        step = CapturedStep(lambda: fwd_bwd(x_static))      # two eager warm-up calls on a side stream, then the capture
-        for batch in data: x_static.copy_(batch); step.replay(); opt.step()
-
-    step.result holds what fn returned at capture (tensors that every replay overwrites).  Hand results out through that return value, or
-    .detach() what fn stores elsewhere: an fn that keeps the autograd graph of its previous call alive (it rebinds an outer name, a dict
-    entry, an attribute ... to a tensor that requires grad) is REFUSED with a RuntimeError before anything is captured.  Why: a graph that
-    outlives its call keeps the AccumulateGrad node of every parameter it used alive, and the next call's graph picks those nodes up
-    again, so they never die -- and a node runs on the stream that was current when it was CREATED.  When the first call ran eagerly on
-    the default stream, the captured backward therefore makes the legacy default stream wait on an event of the capturing stream;
-    CUDA invalidates such a capture with an error, hipStreamEndCapture on ROCm 7.2 ended it in a segmentation fault
-    (gpurun_out/inn3.log, round 2; tools/dbg_capture.py).  The check: before the last warm-up call the AccumulateGrad node of every CUDA
-    parameter is tagged (Node.metadata); a node with no graph holding it dies with the tag, so a tag that is still there after the call's
-    result has been dropped proves a leaked graph."""
-
-    def __init__(self, fn, warmup=2):
-        if not torch.cuda.is_available():
-            raise RuntimeError("CapturedStep: GPU only")
-        import gc
-        warmup = max(int(warmup), 2)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        tag, key = object(), "wm_captured_step_probe"
-        params = []
-
-        def accumulator(p):
-            return torch.autograd.graph.get_gradient_edge(p).node
-
-        with torch.cuda.stream(side):
-            for i in range(warmup):
-                if i == warmup - 1:
-                    gc.collect()
-                    params = [o for o in gc.get_objects() if isinstance(o, torch.nn.Parameter) and o.is_cuda and o.requires_grad]
-                    for p in params:
-                        accumulator(p).metadata[key] = tag
-                r = fn()
-                del r
-            gc.collect()
-            leaked = [p for p in params if accumulator(p).metadata.get(key) is tag]
-        torch.cuda.current_stream().wait_stream(side)
-        if leaked:
-            raise RuntimeError(
-                f"CapturedStep: fn keeps the autograd graph of its previous call alive (the AccumulateGrad nodes of {len(leaked)} of {len(params)} "
-                "parameters survive the call): it stores a tensor that requires grad outside itself (an outer variable, a dict entry, an "
-                "attribute).  Return such tensors from fn (step.result) or .detach() them; capturing this fn can crash the process inside "
-                "hipStreamEndCapture")
-        self.graph = torch.cuda.CUDAGraph()
-        # (the cyclic collector stays off while the stream captures: a dead cycle it frees may own device memory or another hipGraph, and
-        # releasing those is illegal during a capture -- hidden_models/hidden.py::_StepGraph)
-        gc.collect()
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
-            with torch.cuda.graph(self.graph):
-                self.result = fn()
-        finally:
-            if gc_was_on:
-                gc.enable()
-
-    def replay(self):
-        self.graph.replay()
-        return self.result

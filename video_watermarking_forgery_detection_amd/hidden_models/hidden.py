@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 from .. import engine, ops
 from ..noise_layers._device_rng import accepts_cover
+from ..optim import FlatAdam, no_gc
 from ..options import HiDDenConfiguration
 from .discriminator import Discriminator
 from .encoder_decoder import EncoderDecoder
@@ -73,156 +74,6 @@ class StepLosses(collections.abc.Mapping):
 
     def __repr__(self):
         return repr(self._resolve())
-
-
-class _FlatAdam:
-    """torch.optim.Adam defaults (hidden.py:24-25) over flat parameter buffers, one kernel per buffer.
-    Exposes `param_groups` / `state_dict` enough for BaseModel-style lr handling and checkpoints."""
-
-    def __init__(self, modules, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False):
-        self.modules = list(modules)
-        self.param_groups = [{"lr": lr, "initial_lr": lr, "betas": betas, "eps": eps, "weight_decay": weight_decay}]
-        self.decoupled = decoupled
-        self.step_count = 0
-        self._m = None
-        self._v = None
-        self.capturing = False  # True while a step is being CAPTURED into a hipGraph (_StepGraph): step() leaves step_count to the graph's owner,
-        self.hyper_dev = None   # and launches the kernel that reads lr, betas, eps, weight_decay (and, without a scaler, the step-count-dependent
-                                # constants) from this [ops.ADAM_HYPER] f32 device tensor, which the owner refreshes before each replay
-
-    def _ensure(self):
-        if self._m is None:
-            self._m = [torch.zeros_like(m.flat_params) for m in self.modules]
-            self._v = [torch.zeros_like(m.flat_params) for m in self.modules]
-
-    def zero_grad(self):
-        for m in self.modules:
-            m.flat_grads.zero_()
-
-    def attach_amp(self, amp):
-        """run under a device-side GradScaler (ops.AmpState): the gradients arrive multiplied by its scale, the step divides it
-        out, is skipped when they hold an inf / nan, and takes its bias corrections from the scaler's per-optimiser step count"""
-        self.amp, self.amp_slot = amp, amp.slot()
-
-    def step(self, grad_scale=1.0):
-        self._ensure()
-        if not self.capturing:
-            self.step_count += 1
-        g = self.param_groups[0]
-        amp = getattr(self, "amp", None)
-        if amp is not None:   # scaler.step(optimizer), IRNcrop_model.py:413-414
-            amp.found_inf(self.amp_slot, [mod.flat_grads for mod in self.modules])
-            for mod, m, v in zip(self.modules, self._m, self._v):
-                ops.adam_step_amp(mod.flat_params, mod.flat_grads, m, v, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
-                                  amp, self.amp_slot, decoupled=self.decoupled, grad_scale=grad_scale, hyper_dev=self.hyper_dev)
-            return
-        if self.hyper_dev is not None:   # being captured: the numbers of step t come from device memory at replay time
-            for mod, m, v in zip(self.modules, self._m, self._v):
-                ops.adam_step_dev(mod.flat_params, mod.flat_grads, m, v, self.hyper_dev, decoupled=self.decoupled, grad_scale=grad_scale)
-            return
-        for mod, m, v in zip(self.modules, self._m, self._v):
-            ops.adam_step(mod.flat_params, mod.flat_grads, m, v, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
-                          g["weight_decay"], self.step_count, decoupled=self.decoupled, grad_scale=grad_scale)
-
-    def reset_state(self):
-        """Adam from the start again: zero moments, step 0 -- what the reference's schedulers do to a torch optimiser at a restart with
-        clear_state (lr_scheduler.py:22-23: `optimizer.state = defaultdict(dict)`).  Memsets on the current stream in the existing buffers,
-        no host synchronisation; a captured step needs no recapture (it reads the moments through the same pointers and takes its
-        bias corrections from the host's step count at each replay, _StepGraph._hyper_refresh -- under a scaler from the scaler's device-side
-        count, zeroed here too)."""
-        if self._m is not None:
-            for t in self._m + self._v:
-                t.zero_()
-        self.step_count = 0
-        if getattr(self, "amp", None) is not None:
-            self.amp.state[12 + self.amp_slot:13 + self.amp_slot].zero_()
-
-    def hyper(self, step):
-        """the current param group and the constants adam_step derives from the step count (host arithmetic): what a captured step's
-        replay needs in hyper_dev"""
-        g = self.param_groups[0]
-        return ops.adam_hyper(g["lr"], g["betas"][0], g["betas"][1], step, g["eps"], g["weight_decay"])
-
-    def _params(self):
-        return [p for mod in self.modules for p in mod.parameters()]
-
-    def state_dict(self):
-        """torch.optim.Adam's layout (what the reference's `{iter}.state` files hold, base_model.py:129-150): per-parameter
-        {step, exp_avg, exp_avg_sq} sliced out of the flat moment buffers in parameters() order, one param group."""
-        self._ensure()
-        state, i = {}, 0
-        steps = self.amp.step_count(self.amp_slot) if getattr(self, "amp", None) is not None else self.step_count
-        for mod, m, v in zip(self.modules, self._m, self._v):
-            off = 0
-            for p in mod.parameters():
-                n = p.numel()
-                state[i] = {"step": torch.tensor(float(steps)), "exp_avg": m[off:off + n].view_as(p).detach().cpu().clone(),
-                            "exp_avg_sq": v[off:off + n].view_as(p).detach().cpu().clone()}
-                off += n
-                i += 1
-        g = dict(self.param_groups[0])
-        group = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": g["weight_decay"], "amsgrad": False,
-                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "decoupled_weight_decay": bool(self.decoupled), "initial_lr": g.get("initial_lr", g["lr"]), "params": list(range(i))}
-        return {"state": state if steps else {}, "param_groups": [group]}
-
-    def load_state_dict(self, sd):
-        """accepts torch.optim.Adam / AdamW state_dicts (the reference's files) and this class's round-1 flat layout"""
-        self._ensure()
-        if "state" not in sd:   # round-1 layout: {step, param_groups, exp_avg[list], exp_avg_sq[list]}
-            self._set_steps(int(sd["step"]))
-            self._update_group(sd["param_groups"][0])
-            for t, src in zip(self._m, sd["exp_avg"]):
-                t.copy_(src)
-            for t, src in zip(self._v, sd["exp_avg_sq"]):
-                t.copy_(src)
-            return
-        groups = sd["param_groups"]
-        if len(groups) != 1:
-            raise ValueError("expected one param group (torch.optim.Adam over one parameter list)")
-        for k in ("amsgrad", "maximize"):   # variants the kernel does not run: refused rather than continued as plain Adam
-            if groups[0].get(k, False):
-                raise ValueError(f"optimizer state uses {k}=True; the flat Adam step implements neither amsgrad nor maximize")
-        params = self._params()
-        ids = list(groups[0].get("params", range(len(params))))
-        if len(ids) != len(params):
-            raise ValueError(f"optimizer state has {len(ids)} parameters, the networks have {len(params)}")
-        self._update_group(groups[0])
-        state = sd["state"]
-        steps = set()
-        i = 0
-        for mod, m, v in zip(self.modules, self._m, self._v):
-            off = 0
-            for p in mod.parameters():
-                n = p.numel()
-                st = state.get(ids[i], state.get(str(ids[i])))
-                if st is None:   # torch keeps no entry for a parameter that never received a gradient
-                    m[off:off + n].zero_(); v[off:off + n].zero_()
-                else:
-                    if tuple(st["exp_avg"].shape) != tuple(p.shape):
-                        raise ValueError(f"optimizer state of parameter {i} has shape {tuple(st['exp_avg'].shape)}, expected {tuple(p.shape)}")
-                    m[off:off + n].copy_(st["exp_avg"].reshape(-1))
-                    v[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
-                    steps.add(int(float(st["step"])))
-                off += n
-                i += 1
-        if len(steps) > 1:
-            raise ValueError(f"per-parameter step counts differ ({sorted(steps)}): the fused flat-buffer step keeps one count")
-        self._set_steps(steps.pop() if steps else 0)
-
-    def _set_steps(self, n):
-        """the loaded step count: on the host, and -- under a scaler -- in the device slot adam_amp_kernel takes its bias correction's t from
-        (a resumed f16 run otherwise stepped with t = 1 on warm moments: bc1 = 0.1, bc2 = 0.001 instead of ~1)"""
-        self.step_count = n
-        if getattr(self, "amp", None) is not None:
-            self.amp.set_step_count(self.amp_slot, n)
-
-    def _update_group(self, g):
-        for k in ("lr", "betas", "eps", "weight_decay", "initial_lr"):
-            if k in g:
-                self.param_groups[0][k] = tuple(g[k]) if k == "betas" else g[k]
-        if "decoupled_weight_decay" in g:
-            self.decoupled = bool(g["decoupled_weight_decay"])
 
 
 def _noise_fwd(noiser, enc, cover):
@@ -327,15 +178,8 @@ class _StepGraph:
                 o.capturing = True
                 o.hyper_dev = self.hyper[ops.ADAM_HYPER * i:ops.ADAM_HYPER * (i + 1)]
             graph = torch.cuda.CUDAGraph()
-            # Python's cyclic collector must not run inside the capture: whatever dead cycle it finds may own device memory, events or
-            # another hipGraph, and releasing those calls HIP functions that are illegal while a stream captures (the process aborts --
-            # seen in round 4 with the previous test's model in a cycle).  torch 2.10's graph.__enter__ no longer collects first.
-            import gc
-            gc.collect()
-            gc_was_on = gc.isenabled()
-            gc.disable()
             try:
-                with torch.cuda.graph(graph):
+                with no_gc(), torch.cuda.graph(graph):
                     self.result = h._step_launches(self.img, self.msg)
             except Exception as e:   # noqa: BLE001 -- whatever stopped the capture (nothing was executed: the model is as it was before)
                 import warnings
@@ -344,8 +188,6 @@ class _StepGraph:
                 warnings.warn("hipGraph capture of the training step failed; this and the following steps are enqueued eagerly (same launches, "
                               "same results, more host time per step): " + self.failed)
             finally:
-                if gc_was_on:
-                    gc.enable()
                 for o in opts:
                     o.hyper_dev, o.capturing = None, False
             if self.failed is not None:
@@ -419,8 +261,8 @@ class Hidden:
         enc, dec = self.encoder_decoder.encoder, self.encoder_decoder.decoder
         for m in (enc, dec, self.discriminator):
             m.flatten_parameters_()
-        self.optimizer_enc_dec = _FlatAdam([enc, dec])
-        self.optimizer_discrim = _FlatAdam([self.discriminator])
+        self.optimizer_enc_dec = FlatAdam([enc, dec])
+        self.optimizer_discrim = FlatAdam([self.discriminator])
         if configuration.use_vgg:
             raise NotImplementedError("use_vgg: the reference's vgg_loss module is absent from its tree")
         self.vgg_loss = None

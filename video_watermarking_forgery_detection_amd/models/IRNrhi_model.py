@@ -28,7 +28,6 @@ import torch.nn.functional as F
 from .. import engine, ops
 from .. import glayers as G
 from ..hidden_models import Hidden
-from ..hidden_models.hidden import _FlatAdam
 from ..network.UNet import UNet
 from ..noise_layers import Combined, Crop, GaussianBlur, Hybrid, Identity, Jpeg, JpegMask, JpegSS, MiddleBlur, Resize
 from ..noise_layers._device_rng import call_fwd
@@ -36,6 +35,7 @@ from ..noise_layers.dropout import Dropout
 from ..noise_layers.gaussian import Gaussian
 from ..noise_layers.jpeg_compression import JpegCompression
 from ..noise_layers.salt_pepper_noise import SaltPepper
+from ..optim import FlatAdam
 from ..options import HiDDenConfiguration
 from .base_model import BaseModel
 from .lr_scheduler import build_schedulers
@@ -117,7 +117,7 @@ def unetd_localiser_step(net, flat, optimizer, x, mask, weight=1.0, dice_weight=
     the attacked batch exists (IRNcrop_model.py:376-378,391-393,407-416): forward through autograd, weight * BCEWithLogits on the SIGMOID
     output (+ dice_weight * BinaryDiceLoss), both seeded with the scaler's device-side scale; backward through the network into `flat`
     (glayers.FlatParameters of net: the convolution kernels add into it) and into x; all-reduce of the flat gradient (one bucket); joint
-    clipping (clip: callable(list of flat gradients)); one step of `optimizer` (_FlatAdam over [flat]).
+    clipping (clip: callable(list of flat gradients)); one step of `optimizer` (FlatAdam over [flat]).
     -> (loss, dice or None, pred [B,1,H,W] detached, the gradient wrt x -- still multiplied by the scaler's scale, like the seeds)"""
     flat.zero_grad()
     x = x.detach().requires_grad_(True)
@@ -336,12 +336,11 @@ class IRNrhiModel(BaseModel):
                                                        _get(train_opt, 'localizer_fused_head', default=True))
                 # every trainable parameter in one flat buffer (the frozen SRMConv2D.weight stays out): one Adam launch, one clip, one bucket
                 self.localizer_flat = G.FlatParameters(self.localizer)
-                self.optimizer_localizer = _FlatAdam([self.localizer_flat], lr=lr, betas=betas, weight_decay=wd)
             else:
                 self.localizer = UNet(3, 1, 32).to(self.device)
                 engine.set_compute_dtype(self.localizer, dtype)
                 self.localizer.flatten_parameters_()
-                self.optimizer_localizer = _FlatAdam([self.localizer], lr=lr, betas=betas, weight_decay=wd)
+            self.optimizer_localizer = FlatAdam([self.localizer_flat or self.localizer], lr=lr, betas=betas, weight_decay=wd)
             if self.amp is not None:
                 self.optimizer_localizer.attach_amp(self.amp)
             self.optimizers.append(self.optimizer_localizer)
@@ -352,7 +351,7 @@ class IRNrhiModel(BaseModel):
         # train.lr_scheme (MultiStepLR | CosineAnnealingLR_Restart, the reference's keys: lr_steps, lr_gamma, restarts, restart_weights,
         # clear_state, T_period, eta_min; IRNrhi_model.py:340-356): one scheduler per optimiser, stepped by update_learning_rate(step,
         # warmup_iter) before each optimize_parameters (train.py).  Absent: no scheduler, lr_G throughout.  A replayed step follows: it reads
-        # the param group at every replay, and a clear_state restart zeroes the moments in place (_FlatAdam.reset_state)
+        # the param group at every replay, and a clear_state restart zeroes the moments in place (FlatAdam.reset_state)
         self.schedulers = build_schedulers(self.optimizers, train_opt)
         self.psnr_gate = bool(_get(train_opt, 'psnr_gate', default=True))   # IRNcrop_model.py:379-388
         # log side (IRNcrop_model.py:78,399-400: SummaryWriter scalars; :421-437: an image sheet every 500 steps at step % 500 == 10)

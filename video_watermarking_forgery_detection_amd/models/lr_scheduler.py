@@ -1,6 +1,6 @@
 """MultiStepLR_Restart and CosineAnnealingLR_Restart -- the learning-rate schedules of the reference's models/lr_scheduler.py:8-62 (which
 every option file selects with train.lr_scheme and its models build per optimiser, IRNrhi_model.py:341-360), written against `param_groups`
-directly: the optimisers here (hidden_models.hidden._FlatAdam, glayers.FlatAdamW) are flat-buffer objects, no torch.optim.Optimizer, so
+directly: the optimisers here (optim.FlatAdam and its one-module form glayers.FlatAdamW) are flat-buffer objects, no torch.optim.Optimizer, so
 torch's scheduler base cannot wrap them.  Any object with `param_groups` (a list of dicts with 'lr') works, torch's optimisers included.
 
 What torch's base class does for the reference is reproduced by `_Schedule`: 'initial_lr' is set in every group at last_epoch == -1 and
