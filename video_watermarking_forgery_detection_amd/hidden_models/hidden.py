@@ -11,10 +11,9 @@ Adam launch, one RCCL bucket for data parallel), and the seven logged scalars ar
 single asynchronous copy that the host waits for only when a value is read (StepLosses).
 """
 import collections.abc
+import itertools
 
-import numpy as np
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import engine, ops
@@ -210,6 +209,31 @@ class _StepGraph:
         return h._wrap_losses(vals, extra_logs), outs
 
 
+class _Step:
+    """What the stages of one training step (Hidden._d_cover ... _g_update) hand to one another: the batch, the caller's callables, the networks
+    and their gradient dictionaries, and every tensor one stage leaves for a later one.  It lives until the step returns, and the two-chain
+    schedule's memory safety rests on that: the caching allocator hands a freed block back to the pool of the stream that allocated it.  Every
+    tensor one stream allocates and ANOTHER reads (encoded -- engine.share_image_acts holds its NHWC form --, g_enc, g_from_noise, the encoder's
+    activations in cE, the loss scalars) is referenced from here until the chains have been joined, and a side stream is given work only between
+    a fork and the next join (Hidden._run) -- so a block that returns to a side stream's pool is not handed out again before the caller's
+    stream's readers of it are ordered ahead.  What never leaves its stage is used on one stream only and may be freed with the stage."""
+    fidelity = head_logs = extra_logs = ()   # fidelity: [(log name, value, gradient wrt encoded)] of the terms switched on, SSFW, RecFW, SS3FW
+    g_from_noise = pending_d = None
+
+    def __init__(self, h, images, messages, extra_encoded_grad, clip, enc_gate):
+        ed = h.encoder_decoder
+        self.images, self.messages = images, messages
+        self.extra_encoded_grad, self.clip, self.enc_gate = extra_encoded_grad, clip, enc_gate
+        self.noiser, self.enc_net, self.dec_net, self.D = ed.noiser, ed.encoder, ed.decoder, h.discriminator
+        self.gD, self.gE, self.gDec = engine.grad_dict(self.D), engine.grad_dict(self.enc_net), engine.grad_dict(self.dec_net)
+        self.fidelity_on = h.ssim_weight > 0 or h.recon_weight > 0 or h.ssim3_weight > 0
+
+
+# one entry of a schedule: the stage (a Hidden method), the chain it is enqueued on ("A" / "B", None = the caller's stream), the stages of
+# OTHER chains it must wait for, and an optional condition (attribute of the _Step, the value it must have for the slot to run)
+_Slot = collections.namedtuple("_Slot", "stage chain after when", defaults=(None, (), None))
+
+
 class Hidden:
     recon_weight, recon_type = 0.0, 'l2'   # (class-level defaults: the graph key and _recon_term read them on any instance)
     ssim3_weight = 0.0                     # (likewise, for _ssim3_term)
@@ -295,7 +319,7 @@ class Hidden:
         # by the weight-gradient-only kernel instead of the one-pass kernel -- the same sum in another order (tests/test_gpu_graph.py).
         # False = launch it all, as the reference's autograd does
         self.skip_zero_attack_gradient = True
-        self.two_streams = False  # the step's two independent chains on two streams (_train_step_two_chains); same results bit for bit
+        self.two_streams = False  # the step's two independent chains on two streams (the _TWO_CHAINS schedule); same results bit for bit
         self._streams = None
 
     MAX_GRAPHS = 32   # captured variants kept per model (shapes x attack variants x ...); calls beyond that run eagerly
@@ -405,220 +429,192 @@ class Hidden:
 
     def _step_launches(self, images, messages, extra_encoded_grad=None, clip=None, enc_gate=None):
         """every launch of one step, no host synchronisation -> ([7] device tensor of the logged scalars, extra logs, (encoded, noised, decoded))"""
-        B = images.shape[0]
-        cfg = self.config
-        ed = self.encoder_decoder
-        enc_net, dec_net, D = ed.encoder, ed.decoder, self.discriminator
-        ed.train()
-        D.train()
-        gD = engine.grad_dict(D)
-        gE = engine.grad_dict(enc_net)
-        gDec = engine.grad_dict(dec_net)
+        self.encoder_decoder.train()
+        self.discriminator.train()
+        st = _Step(self, images, messages, extra_encoded_grad, clip, enc_gate)
+        two = (self.two_streams and self.grad_sync is None and extra_encoded_grad is None and clip is None and enc_gate is None
+               and hasattr(st.noiser, "fwd") and hasattr(st.noiser, "bwd"))
         # packed conv weights: one launch per network here (+ one for D after its optimiser step) instead of one per
         # conv call; valid only inside this step (the parameters are ours to change until it returns)
-        nets = (enc_net, dec_net, D)
+        nets = (st.enc_net, st.dec_net, st.D)
         try:
             for n in nets:
                 n.refresh_packs()
-            with engine.defer_bn_counters(), engine.share_image_acts(dec_net.compute_dtype):
-                return self._train_step(images, messages, B, cfg, ed, enc_net, dec_net, D, gD, gE, gDec, extra_encoded_grad, clip, enc_gate)
+            with engine.defer_bn_counters(), engine.share_image_acts(st.dec_net.compute_dtype):
+                self._run(self._TWO_CHAINS if two else self._ONE_STREAM, st)
+            return st.vals, st.logs, (st.encoded, st.noised, st.decoded)
         finally:
             for n in nets:
                 n.invalidate_packs()
 
-    def _train_step(self, images, messages, B, cfg, ed, enc_net, dec_net, D, gD, gE, gDec, extra_encoded_grad, clip, enc_gate=None):
-        if (self.two_streams and self.grad_sync is None and extra_encoded_grad is None and clip is None and enc_gate is None
-                and hasattr(ed.noiser, "fwd") and hasattr(ed.noiser, "bwd")):
-            return self._train_step_two_chains(images, messages, B, cfg, ed, enc_net, dec_net, D, gD, gE, gDec)
-        # ---------------- train the discriminator (hidden.py:68-83)
+    # ------------------------------------------------------------------ the stages of the step, each written once
+    # (issued on whatever stream is current; what later stages read is left on the _Step.  Streams and events are the schedules' business, below)
+    def _d_cover(self, st):
         # (fwd_loss: the forward, the loss on its output and the head's share of the backward -- one launch behind the pool instead of four)
-        d_on_cover, d_loss_on_cover, c = D.fwd_loss(images, self.cover_label, 1.0, gD, accumulate=False, gscale_dev=self._gsd())
-        D.bwd(c, None, gD, accumulate=False, need_input_grad=False)       # zero_grad + backward
+        _, st.d_loss_on_cover, c = st.D.fwd_loss(st.images, self.cover_label, 1.0, st.gD, accumulate=False, gscale_dev=self._gsd())
+        st.D.bwd(c, None, st.gD, accumulate=False, need_input_grad=False)
 
-        encoded, cE = enc_net.fwd(images, messages)
-        ssim_val, g_ssim = self._ssim_term(encoded, images)   # (before the attack: the order of the two-chain schedule)
-        rec_val, g_rec = self._recon_term(encoded, images)
-        s3_val, g_s3 = self._ssim3_term(encoded, images)
-        noised, cN = self._run_noiser(encoded, images)
+    def _share_images(self, st):
+        for dt in {st.D.compute_dtype, st.enc_net.compute_dtype}:
+            engine.image_to_act(st.images, dt)
 
-        d_on_encoded, d_loss_on_encoded, c = D.fwd_loss(encoded, self.encoded_label, 1.0, gD, accumulate=True, gscale_dev=self._gsd())   # encoded.detach()
-        D.bwd(c, None, gD, accumulate=True, need_input_grad=False)
-        gs = self.grad_sync
+    def _encode(self, st):
+        st.encoded, st.cE = st.enc_net.fwd(st.images, st.messages)
+
+    def _share_encoded(self, st):
+        for dt in {st.D.compute_dtype, st.dec_net.compute_dtype}:
+            engine.image_to_act(st.encoded, dt)
+
+    def _fidelity(self, st):
+        """the fidelity terms that are switched on, each into a gradient buffer of its own: they need only encoded and the cover"""
+        terms = (('SSFW', self._ssim_term), ('RecFW', self._recon_term), ('SS3FW', self._ssim3_term))
+        st.fidelity = [t for t in ((name, *term(st.encoded, st.images)) for name, term in terms) if t[2] is not None]
+
+    def _attack(self, st):
+        st.noised, st.cN = self._run_noiser(st.encoded, st.images)
+        st.zero_attack = bool(self.skip_zero_attack_gradient and _noise_bwd_is_zero(st.noiser, st.cN))
+
+    def _d_encoded(self, st):
+        """train the discriminator on the encoded image (hidden.py:76-83)"""
+        _, st.d_loss_on_encoded, c = st.D.fwd_loss(st.encoded, self.encoded_label, 1.0, st.gD, accumulate=True, gscale_dev=self._gsd())   # encoded.detach()
+        st.D.bwd(c, None, st.gD, accumulate=True, need_input_grad=False)
         # data parallel: the discriminator's bucket travels under the decoder's forward (independent of D; the reference runs it
         # before D(encoded), the results are the same)
-        pending_d = gs.start(D.flat_grads) if gs is not None else None
-        decoded, msg_out, cDec = dec_net.fwd_loss(noised, messages, 2.0 * cfg.decoder_loss / (B * cfg.message_length), gDec, accumulate=False,
-                                                  gscale_dev=self._gsd())     # mse, bit error, and the head's backward
-        gscale = 1.0
-        if gs is not None:
-            gs.finish(pending_d)
-            gscale = gs.scale
-            if clip is not None:
-                gs.average_(D.flat_grads)
-                gscale = 1.0
-        if clip is not None:
-            clip([D.flat_grads])
-        self.optimizer_discrim.step(grad_scale=gscale)
-        D.refresh_packs()
+        if self.grad_sync is not None:
+            st.pending_d = self.grad_sync.start(st.D.flat_grads)
 
-        # ---------------- train the generator (hidden.py:85-103)
-        d_on_encoded_for_enc, g_loss_adv, c = D.fwd_loss(encoded, self.cover_label, cfg.adversarial_loss, gD, accumulate=True, gscale_dev=self._gsd())
-        g = None
+    def _decode(self, st):
+        cfg, B = self.config, st.images.shape[0]
+        st.decoded, st.msg_out, st.cDec = st.dec_net.fwd_loss(st.noised, st.messages, 2.0 * cfg.decoder_loss / (B * cfg.message_length), st.gDec,
+                                                             accumulate=False, gscale_dev=self._gsd())     # mse, bit error, and the head's backward
+
+    def _grad_scale(self, st, flats):
+        """what the optimiser multiplies these reduced buffers by: 1 / world -- or 1 after a clip callable, which gets them averaged, and TOGETHER"""
+        gs = self.grad_sync
+        if st.clip is None:
+            return 1.0 if gs is None else gs.scale
+        if gs is not None:
+            for f in flats:
+                gs.average_(f)
+        st.clip(flats)
+        return 1.0
+
+    def _d_update(self, st):
+        if self.grad_sync is not None:
+            self.grad_sync.finish(st.pending_d)
+        self.optimizer_discrim.step(grad_scale=self._grad_scale(st, [st.D.flat_grads]))
+        st.D.refresh_packs()
+
+    def _generator(self, st):
+        """train the generator (hidden.py:85-103), down to the gradient wrt the encoded image: adversarial + image fidelity (+ the fidelity terms)"""
+        cfg, D, encoded, images = self.config, st.D, st.encoded, st.images
+        _, st.g_loss_adv, c = D.fwd_loss(encoded, self.cover_label, cfg.adversarial_loss, st.gD, accumulate=True, gscale_dev=self._gsd())
         # the reference's g_loss.backward() also accumulates into the discriminator's .grad (zeroed at the start of the next step, never
         # read): kept by default so the .grad state matches; keep_dead_discriminator_grads=False computes the image gradient alone
-        n_img = encoded.numel()
-        gate = enc_gate(encoded, images) if enc_gate is not None else None
+        st.n_img = encoded.numel()
+        gate = st.enc_gate(encoded, images) if st.enc_gate is not None else None
         if gate is None:
             # the adversarial term's gradient (NHWC, as the discriminator's first layer wrote it) + the image-fidelity term's, and that
             # term's loss, in one pass
-            g_img = D.bwd(c, g, gD, accumulate=True, need_input_grad=True, weight_grads=self.keep_dead_discriminator_grads, raw_input_grad=True)
-            g_enc, enc_part = ops.image_grad_mse(g_img, encoded, images, 2.0 * cfg.encoder_loss / n_img, gscale_dev=self._gsd())
+            g_img = D.bwd(c, None, st.gD, accumulate=True, need_input_grad=True, weight_grads=self.keep_dead_discriminator_grads, raw_input_grad=True)
+            st.g_enc, st.enc_part = ops.image_grad_mse(g_img, encoded, images, 2.0 * cfg.encoder_loss / st.n_img, gscale_dev=self._gsd())
         else:
-            g_enc = D.bwd(c, g, gD, accumulate=True, need_input_grad=True, weight_grads=self.keep_dead_discriminator_grads)
-            enc_part, g_mse = ops.mse_fwd_bwd_gated(encoded, images, 2.0 * cfg.encoder_loss / n_img, gate[1:2], gscale_dev=self._gsd())
-            ops.axpy_(g_enc, g_mse)
-        if g_ssim is not None:
-            ops.axpy_(g_enc, g_ssim)
-        if g_rec is not None:
-            ops.axpy_(g_enc, g_rec)
-        if g_s3 is not None:
-            ops.axpy_(g_enc, g_s3)
-        zero_attack = self.skip_zero_attack_gradient and _noise_bwd_is_zero(ed.noiser, cN)
-        g_noised = dec_net.bwd(cDec, None, gDec, accumulate=False, need_input_grad=not zero_attack)
+            st.g_enc = D.bwd(c, None, st.gD, accumulate=True, need_input_grad=True, weight_grads=self.keep_dead_discriminator_grads)
+            st.enc_part, g_mse = ops.mse_fwd_bwd_gated(encoded, images, 2.0 * cfg.encoder_loss / st.n_img, gate[1:2], gscale_dev=self._gsd())
+            ops.axpy_(st.g_enc, g_mse)
+            st.head_logs = [('PF', gate[0:1])]
+        for _, _, g in st.fidelity:
+            ops.axpy_(st.g_enc, g)
+
+    def _decode_bwd(self, st):
+        st.g_noised = st.dec_net.bwd(st.cDec, None, st.gDec, accumulate=False, need_input_grad=not st.zero_attack)
         # data parallel: the decoder's bucket goes out now and travels while the attack and the encoder run their backward
-        pending = [gs.start(dec_net.flat_grads)] if gs is not None else []
-        if not zero_attack:
-            g_from_noise = _noise_bwd(ed.noiser, cN, g_noised)
-            ops.axpy_(g_enc, g_from_noise.contiguous())
-        extra_logs = []
-        if extra_encoded_grad is not None:
-            extra_logs = extra_encoded_grad(encoded, images, g_enc)
-        if gate is not None:
-            extra_logs = [('PF', gate[0:1])] + list(extra_logs)
-        if ssim_val is not None:
-            extra_logs = list(extra_logs) + [('SSFW', ssim_val.reshape(1))]
-        if rec_val is not None:
-            extra_logs = list(extra_logs) + [('RecFW', rec_val.reshape(1))]
-        if s3_val is not None:
-            extra_logs = list(extra_logs) + [('SS3FW', s3_val.reshape(1))]
-        if gs is not None:
+        if self.grad_sync is not None:
+            st.pending = [self.grad_sync.start(st.dec_net.flat_grads)]
+
+    def _attack_bwd(self, st):
+        st.g_from_noise = _noise_bwd(st.noiser, st.cN, st.g_noised).contiguous()
+
+    def _encoder_bwd(self, st):
+        gs, enc_net = self.grad_sync, st.enc_net
+        if st.g_from_noise is not None:
+            ops.axpy_(st.g_enc, st.g_from_noise)
+        if st.extra_encoded_grad is not None:
+            st.extra_logs = st.extra_encoded_grad(st.encoded, st.images, st.g_enc)
+        if gs is None:
+            enc_net.bwd(st.cE, st.g_enc, st.gE, accumulate=False)
+        else:
             # the encoder in two reverse-order buckets: [after_concat, final] leaves under the body layers' backward
             cut = enc_net.body_param_count()
-            enc_net.bwd(cE, g_enc, gE, accumulate=False, after_head=lambda: pending.append(gs.start(enc_net.flat_grads[cut:])))
-            pending.append(gs.start(enc_net.flat_grads[:cut]))
-            gs.finish_all(pending)
-        else:
-            enc_net.bwd(cE, g_enc, gE, accumulate=False)
-        gscale = 1.0
-        if gs is not None:
-            gscale = gs.scale
-            if clip is not None:
-                gs.average_(enc_net.flat_grads)
-                gs.average_(dec_net.flat_grads)
-                gscale = 1.0
-        if clip is not None:
-            clip([enc_net.flat_grads, dec_net.flat_grads])   # one norm over encoder_decoder.parameters()
-        self.optimizer_enc_dec.step(grad_scale=gscale)
+            enc_net.bwd(st.cE, st.g_enc, st.gE, accumulate=False, after_head=lambda: st.pending.append(gs.start(enc_net.flat_grads[cut:])))
+            st.pending.append(gs.start(enc_net.flat_grads[:cut]))
+            gs.finish_all(st.pending)
+
+    def _g_update(self, st):
+        cfg = self.config
+        self.optimizer_enc_dec.step(grad_scale=self._grad_scale(st, [st.enc_net.flat_grads, st.dec_net.flat_grads]))
         if self.amp is not None and self.amp_owner:
             self.amp.update()   # scaler.update(), IRNcrop_model.py:416
+        # metrics: one host sync for all seven scalars (hidden.py:105-117)
+        st.vals = ops.hidden_metrics(st.enc_part, st.n_img, st.msg_out, st.g_loss_adv, st.d_loss_on_cover, st.d_loss_on_encoded,
+                                     cfg.adversarial_loss, cfg.encoder_loss, cfg.decoder_loss)
+        st.logs = list(st.head_logs) + list(st.extra_logs or ()) + [(name, val.reshape(1)) for name, val, _ in st.fidelity]
 
-        # ---------------- metrics: one host sync for all seven scalars (hidden.py:105-117)
-        vals = ops.hidden_metrics(enc_part, n_img, msg_out, g_loss_adv, d_loss_on_cover, d_loss_on_encoded, cfg.adversarial_loss,
-                                  cfg.encoder_loss, cfg.decoder_loss)
-        return vals, extra_logs, (encoded, noised, decoded)
+    # ------------------------------------------------------------------ the two schedules: the same stages, placed differently
+    # One stream: hidden.py:54-118's order on the caller's stream (the fidelity terms before the attack, where both schedules have them).
+    _ONE_STREAM = (_Slot(_d_cover), _Slot(_encode), _Slot(_fidelity, when=("fidelity_on", True)), _Slot(_attack), _Slot(_d_encoded), _Slot(_decode),
+                   _Slot(_d_update), _Slot(_generator), _Slot(_decode_bwd), _Slot(_attack_bwd, when=("zero_attack", False)), _Slot(_encoder_bwd),
+                   _Slot(_g_update))
+    # Two chains (Hidden.two_streams; why, and what it measured: DESIGN.md §4): the discriminator's passes (A) beside encoder -> attack ->
+    # decoder and back (B), one edge between them (A's second pass waits for encoded) until they join at the encoder's backward.  Listed in
+    # host enqueue order, which is behaviour: A's first stage, ALL of B, then the rest of A (a replayed hipGraph ran its branches side by side
+    # only when the forked branch was captured first: DESIGN.md §9).
+    _TWO_CHAINS = (
+        _Slot(_share_images),                                     # converted once, before the fork: both chains read it
+        _Slot(_d_cover, "A"),
+        _Slot(_encode, "B"),
+        _Slot(_share_encoded, "B"),                               # on the producing stream: chain A and -- under an Identity attack -- the decoder read it
+        _Slot(_fidelity, "B", when=("fidelity_on", True)),        # in stream order ahead of the attack's kernels, never beside them
+        _Slot(_attack, "B"), _Slot(_decode, "B"), _Slot(_decode_bwd, "B"), _Slot(_attack_bwd, "B", when=("zero_attack", False)),
+        _Slot(_d_encoded, "A", after=(_share_encoded,)),
+        _Slot(_d_update, "A"),
+        _Slot(_generator, "A", after=(_fidelity,)),               # (its gradients: before the encoder's backward wherever that runs)
+        # an attack that passes back zeros (Jpeg's torch.round, skip_zero_attack_gradient) leaves chain B without a successor in the encoder:
+        # the encoder's backward continues chain A, beside the decoder's backward on chain B, and the chains meet only at the optimiser step
+        _Slot(_encoder_bwd, "A", when=("zero_attack", True)),
+        _Slot(_encoder_bwd, when=("zero_attack", False)),
+        _Slot(_g_update))
 
-    def _train_step_two_chains(self, images, messages, B, cfg, ed, enc_net, dec_net, D, gD, gE, gDec):
-        """The same step, same launches, same arithmetic -- enqueued as the TWO independent chains hidden.py:54-118 consists of until the encoder's
-        backward: the discriminator's passes (stream A) beside encoder -> attack -> decoder forward and the decoder's backward (stream B).
-
-            A: D(cover) fwd/bwd . . . . . . | wait encoded | D(enc.detach()) fwd/bwd, Adam(D), D(enc) fwd, dgrad to the image, + MSE gradient
-            B: encoder fwd | attack fwd, decoder fwd, message loss, decoder bwd, attack bwd
-            join: g_enc += attack gradient; encoder bwd; Adam(enc + dec); the seven scalars
-        (ssim_weight > 0: SSIM forward and backward on B right after the encoder's forward, into a buffer of their own; A adds it to g_enc
-        with an axpy after the MSE gradient -- the one-chain step issues the same launches, so the two stay bit-identical)
-        (an attack that passes back zeros -- Jpeg's torch.round, skip_zero_attack_gradient -- leaves chain B without a successor in the
-        encoder: the encoder's backward then runs on chain A right behind the discriminator's, beside the decoder's backward)
-
-        Why: every persistent kernel spends a fixed part of its launch outside its tile loop (filter -> LDS, first HBM round trip, for the
-        one-pass backward the weight-gradient slabs) and the chip idles through each launch's ramp and tail; a second, independent launch fills
-        those.  Measured on the step itself: 5.25 ms against 5.35 ms enqueued, 5.21 against 5.34 replayed from the graph (-1.7 ... -2.4 %,
-        profiles/r04_step_modes.txt).  The kernels alone promised more (24 launches of the forward 64 -> 64 kernel 1.75 ms from two streams
-        against 2.02 from one, of the one-pass backward 3.93 against 4.17: tools/bench_two_chains.py, profiles/r04_two_chains.txt), but that
-        comparison's one-stream arm carries host gaps the step does not have.  Results are bit-identical to the one-stream order: no kernel's
-        inputs or reduction order change, only when it runs."""
-        main = torch.cuda.current_stream()
-        sA, sB = self._chain_streams()
-        dts = {D.compute_dtype, enc_net.compute_dtype}
-        for dt in dts:
-            engine.image_to_act(images, dt)              # converted once, before the fork: both chains read it
-        sA.wait_stream(main); sB.wait_stream(main)
-        with torch.cuda.stream(sA):
-            d_on_cover, d_loss_on_cover, c = D.fwd_loss(images, self.cover_label, 1.0, gD, accumulate=False, gscale_dev=self._gsd())
-            D.bwd(c, None, gD, accumulate=False, need_input_grad=False)
-        with torch.cuda.stream(sB):
-            encoded, cE = enc_net.fwd(images, messages)
-            for dt in {D.compute_dtype, dec_net.compute_dtype}:
-                engine.image_to_act(encoded, dt)         # (on the producing stream: chain A and -- under an Identity attack -- the decoder read it)
-            ev_enc = torch.cuda.Event()
-            ev_enc.record(sB)
-            # the SSIM term needs only encoded and the cover: here, in stream order ahead of the attack's kernels (never beside them), while
-            # chain A runs the discriminator; chain A waits for ev_ssim before it adds the term's gradient
-            ssim_val, g_ssim = self._ssim_term(encoded, images)
-            rec_val, g_rec = self._recon_term(encoded, images)    # (the reconstruction term likewise, right behind it)
-            s3_val, g_s3 = self._ssim3_term(encoded, images)      # (and the 3 x 3 structure term)
-            if g_ssim is not None or g_rec is not None or g_s3 is not None:
-                ev_ssim = torch.cuda.Event()
-                ev_ssim.record(sB)
-            noised, cN = self._run_noiser(encoded, images)
-            decoded, msg_out, cDec = dec_net.fwd_loss(noised, messages, 2.0 * cfg.decoder_loss / (B * cfg.message_length), gDec, accumulate=False,
-                                                      gscale_dev=self._gsd())
-            zero_attack = self.skip_zero_attack_gradient and _noise_bwd_is_zero(ed.noiser, cN)
-            g_noised = dec_net.bwd(cDec, None, gDec, accumulate=False, need_input_grad=not zero_attack)
-            g_from_noise = None if zero_attack else _noise_bwd(ed.noiser, cN, g_noised).contiguous()
-        with torch.cuda.stream(sA):
-            sA.wait_event(ev_enc)
-            d_on_encoded, d_loss_on_encoded, c = D.fwd_loss(encoded, self.encoded_label, 1.0, gD, accumulate=True, gscale_dev=self._gsd())
-            D.bwd(c, None, gD, accumulate=True, need_input_grad=False)
-            self.optimizer_discrim.step(grad_scale=1.0)
-            D.refresh_packs()
-            d_on_encoded_for_enc, g_loss_adv, c = D.fwd_loss(encoded, self.cover_label, cfg.adversarial_loss, gD, accumulate=True, gscale_dev=self._gsd())
-            g = None
-            g_img = D.bwd(c, g, gD, accumulate=True, need_input_grad=True, weight_grads=self.keep_dead_discriminator_grads, raw_input_grad=True)
-            n_img = encoded.numel()
-            g_enc, enc_part = ops.image_grad_mse(g_img, encoded, images, 2.0 * cfg.encoder_loss / n_img, gscale_dev=self._gsd())
-            if g_ssim is not None or g_rec is not None or g_s3 is not None:   # before the encoder's backward wherever that runs (zero_attack: right below, on this chain)
-                sA.wait_event(ev_ssim)
-            if g_ssim is not None:
-                ops.axpy_(g_enc, g_ssim)
-            if g_rec is not None:
-                ops.axpy_(g_enc, g_rec)
-            if g_s3 is not None:
-                ops.axpy_(g_enc, g_s3)
-            if zero_attack:
-                # nothing of chain B reaches the encoder's gradient (the attack passes back zeros): the encoder's backward continues chain A,
-                # beside the decoder's backward on chain B, and the chains meet only at the optimiser step
-                enc_net.bwd(cE, g_enc, gE, accumulate=False)
-        main.wait_stream(sA); main.wait_stream(sB)
-        if not zero_attack:
-            ops.axpy_(g_enc, g_from_noise)
-            enc_net.bwd(cE, g_enc, gE, accumulate=False)
-        self.optimizer_enc_dec.step(grad_scale=1.0)
-        if self.amp is not None and self.amp_owner:
-            self.amp.update()
-        vals = ops.hidden_metrics(enc_part, n_img, msg_out, g_loss_adv, d_loss_on_cover, d_loss_on_encoded, cfg.adversarial_loss,
-                                  cfg.encoder_loss, cfg.decoder_loss)
-        # Memory: the caching allocator hands a freed block back to the pool of the stream that allocated it.  Every tensor one stream
-        # allocates and ANOTHER reads (encoded and its NHWC form, g_enc, g_from_noise, the encoder's activations in cE, the loss scalars) is
-        # referenced until this function returns, and a side stream is given work only between a fork (wait_stream(main)) and the join
-        # above -- so a block that returns to a side stream's pool is not handed out again before main's readers of it are ordered ahead
-        extra_logs = ([('SSFW', ssim_val.reshape(1))] if ssim_val is not None else []) + ([('RecFW', rec_val.reshape(1))] if rec_val is not None else [])
-        extra_logs += [('SS3FW', s3_val.reshape(1))] if s3_val is not None else []
-        return vals, extra_logs, (encoded, noised, decoded)
-
-    def _chain_streams(self):
-        if self._streams is None:
-            self._streams = (torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device))
-        return self._streams
+    def _run(self, schedule, st):
+        """Run a schedule's stages in the order listed -- the only stream code of the step.  Slots without a chain run on the caller's stream;
+        the first slot on a chain forks A and B from it, the next slot without a chain joins them.  A stage some slot names in `after` gets
+        an event recorded behind it, and that slot's stream waits for it (a stage that did not run is not waited for)."""
+        caller = torch.cuda.current_stream()
+        awaited = {dep for slot in schedule for dep in slot.after}
+        side, events = {}, {}
+        for chain, slots in itertools.groupby(schedule, key=lambda slot: slot.chain):
+            if chain is None:
+                for s in side.values():
+                    caller.wait_stream(s)
+                side = {}
+            elif not side:
+                if self._streams is None:
+                    self._streams = (torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device))
+                side = dict(zip("AB", self._streams))
+                for s in side.values():
+                    s.wait_stream(caller)
+            stream = side.get(chain, caller)
+            with torch.cuda.stream(side.get(chain)):   # (None on the caller's stream: no switch)
+                for slot in slots:
+                    if slot.when is not None and getattr(st, slot.when[0]) != slot.when[1]:
+                        continue
+                    for dep in slot.after:
+                        if dep in events:
+                            stream.wait_event(events[dep])
+                    slot.stage(self, st)
+                    if slot.stage in awaited:
+                        events[slot.stage] = torch.cuda.Event()
+                        events[slot.stage].record(stream)
 
     def validate_on_batch(self, batch: list):
         """hidden.py:120-182: eval-mode BatchNorm (running statistics), no parameter update."""

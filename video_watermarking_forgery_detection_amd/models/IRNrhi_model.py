@@ -309,7 +309,7 @@ class IRNrhiModel(BaseModel):
         # train.eval_metrics (default false): evaluate() appends robustness_report() to its logs
         self.eval_metrics = bool(_get(train_opt, 'eval_metrics', default=False))
         # train.two_streams (default true): the step's two independent chains on two streams wherever a step has them to itself (one GPU, no
-        # localisation branch / clipping / PSNR gate: Hidden._train_step_two_chains); same results bit for bit
+        # localisation branch / clipping / PSNR gate: Hidden._TWO_CHAINS); same results bit for bit
         self.hidden.two_streams = bool(_get(train_opt, 'two_streams', default=True))
         # train.graph (default true): a step WITHOUT the localiser branch, gradient clipping and PSNR gate (configuration C3) is replayed from a
         # hipGraph, one graph per layer of the attack cycle (Hidden.enable_graph; same results bit for bit, tests/test_gpu_graph.py); one GPU only
