@@ -121,6 +121,25 @@ int wm_resample_bwd_sep(const float* gy, const float* y_clamped, float* gx, floa
 /* Quantization: round(255 x)/255; replaces models/modules/Quantization.py:7-14 (the backward
  * is the identity and needs no kernel). */
 int wm_quant_fwd(const float* x, float* y, size_t n, void* stream);
+/* Separable k x k blur, k odd in 3..WM_GAUSS_SEP_MAX_K, r = k/2: replaces noise_layers/gaussian_blur.py:44-56 at any kernel size
+ * (WM_BORDER_ZERO: Conv2d padding (k-1)/2) and noise_layers/gaussian_filter.py (kornia GaussianBlur2d, WM_BORDER_REFLECT); the 2-D weights
+ * are outer(taps, taps).  taps = host pointer to k f32 values, read before the call returns.
+ *   y[h,w] = sum_i taps[i] * (sum_j taps[j] * xpad[h+i-r, w+j-r]),  inner (row) sum first, each sum a chain of fmaf from 0, left to right.
+ * One launch: a workgroup stages its tile and halo in LDS, row pass LDS -> LDS, column pass LDS -> registers -> y; float4 global access
+ * where W % 4 == 0 and the base is 16-byte aligned, element by element elsewhere, same bits either way.
+ * Backward = the exact transpose in gather form (deterministic): zero border = the forward with reversed taps; reflected border = with
+ * Z(p) = sum_i taps[k-1-i] * G[p+i-r] on the zero-extended gradient G, gx[q] = Z(q) + [1<=q<=r] Z(-q) + [n-1-r<=q<=n-2] Z(2(n-1)-q) per axis
+ * (row axis first).  Any other k, or WM_BORDER_REFLECT with r >= H or r >= W (torch's reflect-pad limit): WM_E_BADARG, nothing is launched. */
+#define WM_BORDER_ZERO 0
+#define WM_BORDER_REFLECT 1
+#define WM_GAUSS_SEP_MAX_K 15
+int wm_gauss_sep_fwd(const float* x, float* y, int N, int H, int W, const float* taps, int k, int border, void* stream);
+int wm_gauss_sep_bwd(const float* gy, float* gx, int N, int H, int W, const float* taps, int k, int border, void* stream);
+/* Cropout: replaces noise_layers/crop.py:128-134.  y = x inside [h0,h1) x [w0,w1) and cover elsewhere (a fresh tensor: cover is only read).
+ * Backward: gx = g inside, 0 outside; gcover (may be NULL) = 0 inside, g outside, in the same launch.  Selections: every output is bit-exact.
+ * An empty rectangle, or one not inside the plane: WM_E_BADARG. */
+int wm_cropout_fwd(const float* x, const float* cover, float* y, int N, int H, int W, int h0, int h1, int w0, int w1, void* stream);
+int wm_cropout_bwd(const float* g, float* gx, float* gcover, int N, int H, int W, int h0, int h1, int w0, int w1, void* stream);
 
 /* The clip loader's device path (replaces: /root/reference/data/Dataloader.py:22-57, the per-frame numpy -> cv2.resize -> torch chain):
  * decoded frames uint8 x[N][H][W][C] (C <= 4) -> float planes y[N][C][H][W] = x * scale (1/255 for images); the resize itself is

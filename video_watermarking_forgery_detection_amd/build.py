@@ -34,6 +34,7 @@ NO_SPILL = ("conv3x3_ws.hip", "bwd_ws.hip", "bwd_ws8.hip", "bwd_ws16.hip", "wgra
             "mask_head.hip",                             # (a streaming head: its per-lane filter rows and sums are register arrays indexed by unrolled constants)
             "instnorm.hip",                              # (per-lane channel constants and double sums of one 16-byte vector: register arrays, unrolled)
             "invblock.hip",                              # (streaming couplings: the 16-byte vectors' elements are register arrays indexed by unrolled constants)
+            "gauss_sep.hip",                             # (the staged taps and the column pass's rows are register arrays indexed by unrolled constants)
             "swin.hip")                                  # (LayerNorm rows and attention tiles live in LDS; the MFMA fragments are filled by unrolled constants)
 # (file, f16 twin?, substring of the mangled kernel name) known and accepted to spill, with the reason
 SPILL_OK = (("wgrad_ws.hip", True, "wgrad_ws16_kernelILi64ELb1ELi2EE"),)    # f16 twin of the pooled-layer weight gradient: 11 VGPRs; superseded on the step by bwd_ws8<GVEC>

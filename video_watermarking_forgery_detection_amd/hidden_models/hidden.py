@@ -327,9 +327,10 @@ class Hidden:
     def enable_graph(self, on=True):
         """replay the step from a hipGraph instead of enqueueing its ~190 launches every call (same results bit for bit: _StepGraph).
         Used for plain train_on_batch(batch) calls on one GPU with an attack layer that has an explicit fwd / bwd and declares itself
-        `capturable` (the same launches with the same arguments every call: the Jpeg family, GaussianBlur, MiddleBlur, Identity -- not the
-        layers that draw their arguments on the host, Resize / Crop / Combined) or names the deterministic variant this call runs through
-        `capture_key()` (one graph per variant: the model surface's attack cycle, which calls Resize / Crop with fixed arguments); a call with
+        `capturable` (the same launches with the same arguments every call: the Jpeg family, GaussianBlur at any size, GF, MiddleBlur, Identity -- not the
+        layers that draw their arguments on the host, Resize / Crop / Cropout / Combined) or names the deterministic variant this call runs through
+        `capture_key()` (one graph per variant: the model surface's attack cycle, which calls Resize / Crop with fixed arguments and answers None, "run
+        this one eagerly", for a layer that says capturable = False: Cropout); a call with
         extra_encoded_grad / clip / enc_gate, with a grad_sync, or while a kernel timer is installed runs eagerly as before."""
         self._graphs = {} if on else None
         return self

@@ -31,8 +31,10 @@ from ..hidden_models import Hidden
 from ..network.UNet import UNet
 from ..noise_layers import Combined, Crop, GaussianBlur, Hybrid, Identity, Jpeg, JpegMask, JpegSS, MiddleBlur, Resize
 from ..noise_layers._device_rng import call_fwd
+from ..noise_layers.crop import Cropout
 from ..noise_layers.dropout import Dropout
 from ..noise_layers.gaussian import Gaussian
+from ..noise_layers.gaussian_filter import GF
 from ..noise_layers.jpeg_compression import JpegCompression
 from ..noise_layers.salt_pepper_noise import SaltPepper
 from ..optim import FlatAdam
@@ -200,6 +202,8 @@ class _AttackCycle:
         through layer i launches the same kernels every time -- one captured graph per layer.  (Also names the layer, as fwd does: a
         replayed step does not call fwd.)"""
         i, layer = self._choose()
+        if getattr(layer, "capturable", None) is False:
+            return None     # a layer that says it draws its arguments on the host per call (Cropout's rectangle): this step runs eagerly
         return ("cycle", i, type(layer).__name__)
 
     def fwd(self, image, id=None, exclude=(), cover=None):
@@ -262,12 +266,15 @@ class IRNrhiModel(BaseModel):
         attacks = _get(train_opt, 'attacks', default=None)
         table = {
             "Jpeg": lambda q: Jpeg(q), "JpegSS": lambda q: JpegSS(q), "JpegMask": lambda q: JpegMask(q),
-            "GaussianBlur": lambda q: GaussianBlur(), "MiddleBlur": lambda q: MiddleBlur(q or 3),
+            "GaussianBlur": lambda q: GaussianBlur(q or 3), "MiddleBlur": lambda q: MiddleBlur(q or 3),
             "Resize": lambda q: Resize(), "Crop": lambda q: Crop(), "Identity": lambda q: Identity(),
             # the stochastic / JPEG-Drop attacks every reference trainer constructs (IRNrhi_model.py:134-136): dropout.Dropout(),
             # Gaussian(), SaltPepper(prob=0.01), JpegCompression; their draws come from the device generator, seeded from torch's
             "Dropout": lambda q: Dropout(), "Gaussian": lambda q: Gaussian(), "SaltPepper": lambda q: SaltPepper(prob=0.01),
             "JpegCompression": lambda q: JpegCompression(self.device),
+            # GaussianBlur<k> (above): the k x k blur, k odd in 3..15; GF<k>: the reference's kornia blur (noise_layers/gaussian_filter.py) at
+            # sigma 2, kernel k or 7; Cropout: crop.py:121-134 at half the frame each way (its rectangle is drawn per call: such a step runs eagerly)
+            "GF": lambda q: GF(sigma=2.0, kernel=q or 7), "Cropout": lambda q: Cropout(0.5, 0.5),
         }
         if attacks is None:
             attacks = ["Jpeg50"]

@@ -3,7 +3,13 @@
 the interpolation are one gather kernel (the rectangle is an offset into the source planes).
 
 Dropout -- mirror of crop.py:136-147 (the Dropout the reference's noise_layers package exports):
-per-element u ~ U[0,1), where(u > prob, cover, image), from the layer's device generator (csrc/noise.hip)."""
+per-element u ~ U[0,1), where(u > prob, cover, image), from the layer's device generator (csrc/noise.hip).
+
+Cropout -- mirror of crop.py:121-134: the image inside a random rectangle of (height_ratio, width_ratio) of the frame, the cover elsewhere
+(csrc/gauss_sep.hip: wm_cropout_fwd / wm_cropout_bwd, one selection launch each way).  Two things differ from the reference, on purpose:
+its forward calls self.get_random_rectangle_inside, which the class never defines (crop.py:131) -- Crop's method (crop.py:13-30, numpy RNG)
+is used; and it writes the rectangle into cover_image in place and returns that tensor -- here the result is a fresh tensor with the same
+values and the cover is left untouched.  Importable from this submodule only (noise_layers.crop.Cropout)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -110,3 +116,56 @@ class Dropout(nn.Module):
 
     def bwd(self, ctx, g):
         return ops.noise_bwd(ops.NOISE_DROP, g, self._prob, 0.0, ctx)[0]
+
+
+class _CropoutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, cover, rect):
+        ctx.rect = rect
+        return ops.cropout_fwd(image.float(), cover.float(), rect)
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, gc = ops.cropout_bwd(g.float(), ctx.rect, want_cover=ctx.needs_input_grad[1])
+        return gx, gc, None
+
+
+class Cropout(nn.Module):
+    capturable = False   # the rectangle is drawn on the host (numpy RNG) on every call
+    needs_cover = True
+
+    def __init__(self, height_ratio, width_ratio):
+        super(Cropout, self).__init__()
+        self.height_ratio = height_ratio
+        self.width_ratio = width_ratio
+        self.name = "Cropout"
+        self.last_rect = None
+
+    get_random_rectangle_inside = Crop.get_random_rectangle_inside   # (the reference's Cropout calls this method without defining it)
+
+    def _rect(self, image):
+        rect = self.get_random_rectangle_inside(image.shape, self.height_ratio, self.width_ratio)
+        if rect[0] >= rect[1] or rect[2] >= rect[3]:
+            raise ValueError(f"Cropout: ratios ({self.height_ratio}, {self.width_ratio}) leave an empty rectangle of a "
+                             f"{image.shape[2]} x {image.shape[3]} image")
+        self.last_rect = rect
+        return rect
+
+    def forward(self, image_and_cover):
+        image, cover_image = image_and_cover
+        if cover_image is None:
+            raise ValueError("Cropout mixes in the cover image: forward([image, cover]) / apply_attack(image, cover)")
+        need_cuda(self.name, image, cover_image)
+        return _CropoutFn.apply(image, cover_image, self._rect(image))
+
+    def apply_attack(self, image, cover=None):
+        return self.forward([image, cover])
+
+    def fwd(self, image, cover=None):
+        if cover is None:
+            raise ValueError("Cropout mixes in the cover image: fwd(image, cover=...)")
+        rect = self._rect(image)
+        return ops.cropout_fwd(image, cover, rect), rect
+
+    def bwd(self, ctx, g):
+        return ops.cropout_bwd(g, ctx)[0]

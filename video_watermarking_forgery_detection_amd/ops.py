@@ -1242,6 +1242,59 @@ def stencil3(x, w9):
     return y
 
 
+BORDER_ZERO, BORDER_REFLECT = 0, 1
+GAUSS_SEP_MAX_K = 15
+GAUSS_SEP_TILE = (32, 64)       # (rows, columns) of the output tile a workgroup of csrc/gauss_sep.hip owns: the tests put planes on its seams
+
+
+def _gauss_sep_out(x, out):
+    if out is None:
+        return torch.empty_like(x)
+    _need_cuda(out)
+    if out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("gauss_sep: out must be a contiguous float32 tensor of the input's shape")
+    return out
+
+
+def gauss_sep(x, taps, border=BORDER_ZERO, out=None):
+    """separable blur of x [B,C,H,W] with outer(taps, taps), len(taps) odd in 3..15; border: BORDER_ZERO | BORDER_REFLECT"""
+    x, N, H, W = _planes(x)
+    y = _gauss_sep_out(x, out)
+    _lib.checked().wm_gauss_sep_fwd(_p(x), _p(y), N, H, W, _host_floats(taps), len(taps), border, _stream())
+    return y
+
+
+def gauss_sep_bwd(gy, taps, border=BORDER_ZERO, out=None):
+    """the transpose of gauss_sep (same taps, not reversed by the caller)"""
+    gy, N, H, W = _planes(gy)
+    gx = _gauss_sep_out(gy, out)
+    _lib.checked().wm_gauss_sep_bwd(_p(gy), _p(gx), N, H, W, _host_floats(taps), len(taps), border, _stream())
+    return gx
+
+
+def cropout_fwd(x, cover, rect):
+    """rect = (h0, h1, w0, w1): x inside [h0,h1) x [w0,w1), cover elsewhere; a fresh tensor, cover is only read"""
+    x, N, H, W = _planes(x)
+    _need_cuda(cover)
+    if cover.shape != x.shape or cover.dtype != torch.float32:
+        raise ValueError("cropout_fwd: cover must be a float32 tensor of the image's shape")
+    cover = cover.contiguous()
+    h0, h1, w0, w1 = (int(v) for v in rect)
+    y = torch.empty_like(x)
+    _lib.checked().wm_cropout_fwd(_p(x), _p(cover), _p(y), N, H, W, h0, h1, w0, w1, _stream())
+    return y
+
+
+def cropout_bwd(g, rect, want_cover=False):
+    """-> (gx, gcover or None): g inside the rectangle and 0 outside; 0 inside and g outside"""
+    g, N, H, W = _planes(g)
+    h0, h1, w0, w1 = (int(v) for v in rect)
+    gx = torch.empty_like(g)
+    gc = torch.empty_like(g) if want_cover else None
+    _lib.checked().wm_cropout_bwd(_p(g), _p(gx), _p(gc), N, H, W, h0, h1, w0, w1, _stream())
+    return gx, gc
+
+
 def median_fwd(x, k, want_idx=True):
     x, N, H, W = _planes(x)
     y = torch.empty_like(x)
